@@ -4,7 +4,12 @@
 A "step" = one pass of the hot path (the mining kernel(s) of one workload over every task edge of the graph, plus the
 RCCL all-reduce of the 64-bit counts when --gpus > 1), inputs resident in HBM before the timed region.
 
-Default run = ALL FIVE BASELINE.json configs on one JSON line:
+Default run = the HEADLINE alone (configs[1], triangle counting on the LiveJournal stand-in below): the graph, W warm-up steps, K timed
+steps, `--dump-outputs DIR` (the count(s) of the last timed step as DIR/count.npy), and one JSON line with `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (wall time of one timed step), the count and the kernel time. `--workload` & co. pick another
+workload / graph for it.
+
+`--full` = ALL FIVE BASELINE.json configs on one JSON line (+ the full record in the --detail file):
   * the top-level keys (`value`, `ms_per_step`, `roofline`, `cpu_baseline`, ...) are the HEADLINE: configs[1], triangle
     counting on LiveJournal. The real LiveJournal / Orkut files are not in the image, so the graphs
     are the stand-ins SURVEY.md section 8d names: R-MAT scale 22 ef 10 (TC, diamond), scale 22 ef 28 (4-clique),
@@ -14,7 +19,8 @@ Default run = ALL FIVE BASELINE.json configs on one JSON line:
     5: 3-motif R-MAT-24 -- the largest single-GPU configuration), each with its count, count check, algorithmic and
     counter-traffic bandwidth, the compulsory floor, and a CPU baseline timed on this box's host cores.
 
-  python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3                            # the headline alone
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full                     # everything below
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
          --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3
   python bench.py --workload diamond --scale 20 --ef 16          # one workload (development / profiling)
@@ -119,7 +125,14 @@ def parse():
     ap.add_argument("--first-call-repeats", type=int, default=2, help="extra FRESH handles over the same device arrays whose first call (setup + one count) is timed "
                     "beside the first one (N = 1): first_call_ms = the median, every run listed")
     ap.add_argument("--detail", default="", help="where the FULL record goes (default gpurun_out/bench_detail.json); stdout carries one compact line")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: the five BASELINE configs, CPU baselines, stand-in graphs, "
+                    "counter / roofline passes, fresh-handle first calls and the detail file (without it: the headline workload alone)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step "
+                    "to DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1195,7 +1208,7 @@ def known_answer(a, workload, graph_name):
 
 def self_launch(a):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks here (the reference's *_multigpu binaries take
-    n_gpu as an argument and spawn their own threads, src/clique/multigpu.cu:20,109-115) -- re-exec under torch.distributed.run, one
+    n_gpu as an argument and spawn their own threads, src/clique/multigpu.cu:20,109-115) -- a child torch.distributed.run, one
     process per GPU, rendezvous on 127.0.0.1. Under an external launcher (WORLD_SIZE set) nothing happens here."""
     if a.gpus <= 1 or "WORLD_SIZE" in os.environ or a.traffic_worker:
         return
@@ -1218,7 +1231,8 @@ def self_launch(a):
            "--master-port", port, os.path.abspath(__file__), *sys.argv[1:]]
     print(f"[bench] --gpus {a.gpus} without a launcher: starting {a.gpus} ranks: {' '.join(cmd[1:9])} ...", file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    # a child process, not an exec: this process has already opened the GPU (device_count above); it only waits and passes the exit status on
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 SHORT_BASIS = (("counter traffic", "counter_traffic: rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE / HIP-event kernel time / 8 TB/s"),
@@ -1305,11 +1319,63 @@ def compact_line(out, detail_path):
     return line
 
 
+METRIC = "million edges processed/sec + total match count"
+DTYPE = "int32 (vertex ids, offsets; uint64 counts)"
+
+
+def data_kind(a, graph_name):
+    return "file" if graph_name.startswith("file:") else ("synthetic uniform random graph (torch RNG)" if a.uniform else
+                                                          "synthetic Chung-Lu power-law graph (torch RNG)" if a.powerlaw else
+                                                          "synthetic planted communities + power-law background (torch RNG)" if a.community else
+                                                          "synthetic R-MAT (0.57,0.19,0.19,0.05), SplitMix64 counter stream")
+
+
+def dump_outputs(out_dir, rec):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last timed step -- the workload's match count(s), the library's
+    uint64 counts (all ranks summed) -- as DIR/count.npy, float64 (exact below 2^53). The inputs are seeded: equal arguments, equal arrays."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "count.npy"), np.atleast_1d(np.asarray(rec["count"], dtype=np.float64)))
+
+
+def plain_run(a):
+    """The default run (no --full): the headline workload alone -- the graph, W warm-up steps, K timed steps, --dump-outputs, ONE line with
+    the headline keys of the --full line (same meaning: `value` = tasks / step time, `ms_per_step` = wall time of one timed step)."""
+    r = Runner(a)
+    a.first_call_repeats = 0  # (the fresh-handle first calls are --full's)
+    w = a.workload or "tc"
+    scale, ef = (a.scale or WORKLOADS[w][0]), (a.ef or WORKLOADS[w][1])
+    bg = build_graph(a, r.local_rank, scale, ef, dataset_prefix(a, w))
+    progress(f"{w} on {bg.name}: {a.warmup} + {a.steps} steps")
+    x = r.run(w, bg, a.steps, a.warmup)
+    line = None
+    if r.rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, x)
+        line = {"metric": METRIC, "value": round(x["tasks"] / (x["elapsed"] / x["steps"]) / 1e6, 3), "unit": "Medges/s", "n_gpus": r.world,
+                "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(x["ms_per_step"], 4), "higher_is_better": True, "scaling": "strong",
+                "vs_baseline": None, "dtype": DTYPE, "data": data_kind(a, bg.name),
+                "config": {"workload": f"{w}: {WORKLOADS[w][3]}", "graph": bg.name, "nv": x["nv"], "ne_sym": x["ne_sym"], "tasks": x["tasks"],
+                           "max_degree": x["max_degree"], "parallelism": f"task-chunk round-robin x{r.world}, replicated CSR",
+                           "input_build_s": round(bg.build_s, 2)},
+                "count": x["count"], "kernel_ms_avg": round(x["kernel_ms_avg"], 4), "first_call_ms": round(x["first_call_ms"], 2),
+                "per_gpu_kernel_ms": {"max": round(max(x["per_gpu_kernel_ms"]), 4), "mean": round(sum(x["per_gpu_kernel_ms"]) / len(x["per_gpu_kernel_ms"]), 4)},
+                "rccl_ranks_seen": r.ranks_seen, "bench_wall_s": round(time.perf_counter() - _T0, 1)}
+    r.close()
+    if r.rank == 0:
+        if r.use_dist and r.world > 1:
+            time.sleep(1.0)
+        print(json.dumps(line, separators=(",", ":")), flush=True)
+
+
 def main():
     a = parse()
     if a.traffic_worker:
         return traffic_worker(a)
     self_launch(a)
+    if not a.full:
+        return plain_run(a)
     r = Runner(a)
     world, rank = r.world, r.rank
     single = bool(a.workload or a.graph or a.uniform or a.powerlaw or a.community)
@@ -1340,6 +1406,8 @@ def main():
             # (diamond across ranks through the shared triangle pass: the one-GPU byte model, a rank's share of it)
             own_of[w] = own_bytes_device(w, bg, 1 if rec.get("diamond_supports_across_ranks") else r.world)
         recs.append(rec)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, recs[0])  # (the headline's timed path, as in the default run)
 
     out = None
     if rank == 0:
@@ -1449,14 +1517,10 @@ def main():
                 tc24 = {"error": str(e)}
         head = subs[0]
         out = {
-            "metric": "million edges processed/sec + total match count",
+            "metric": METRIC,
             "value": head["value"], "unit": "Medges/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "int32 (vertex ids, offsets; uint64 counts)",
-            "data": "file" if head["graph"].startswith("file:") else ("synthetic uniform random graph (torch RNG)" if a.uniform else
-                                                                     "synthetic Chung-Lu power-law graph (torch RNG)" if a.powerlaw else
-                                                                     "synthetic planted communities + power-law background (torch RNG)" if a.community else
-                                                                     "synthetic R-MAT (0.57,0.19,0.19,0.05), SplitMix64 counter stream"),
+            "dtype": DTYPE, "data": data_kind(a, head["graph"]),
             "config": {"workload": f"{head['workload']}: {WORKLOADS[head['workload']][3]}", "graph": head["graph"], "nv": head["nv"],
                        "ne_sym": head["ne_sym"], "tasks": head["tasks"], "max_degree": head["max_degree"],
                        "parallelism": f"task-chunk round-robin x{world}, replicated CSR", "input_build_s": head["input_build_s"]},

@@ -12,7 +12,7 @@ for case in cases:
         env = dict(os.environ)
         if v != "default":
             env["GM_LIB_PATH"] = os.path.join(ROOT, "graphminer_amd", "variants", f"lib_{v}.so")
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--traffic", "off", *args.split(";")]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--traffic", "off", *args.split(";")]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -47,7 +47,7 @@ def main():
     rows = []
     for w in a.workloads.split(","):
         detail = os.path.join(tmp, f"{w}.json")
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", w, "--scale", str(a.scale), "--ef", str(a.ef), "--steps", "3", "--warmup", "1",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", w, "--scale", str(a.scale), "--ef", str(a.ef), "--steps", "3", "--warmup", "1",
                "--no-cpu-baseline", "--first-call-repeats", "0", "--detail", detail]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=3600)
         row = {"workload": w, "graph": f"rmat_s{a.scale}_ef{a.ef}_seed42"}

@@ -10,4 +10,4 @@ cd "$(dirname "$0")/.."
 N=${1:-2}; shift || true
 export GM_BENCH_ONE_GPU=1 GM_BENCH_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0
 exec python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "${MASTER_PORT:-29541}" \
-     bench.py --gpus "$N" "$@"
+     bench.py --gpus "$N" --full "$@"

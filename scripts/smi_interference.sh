@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 OUT=${1:-gpurun_out/r05}; RUNS=${2:-3}
 mkdir -p "$OUT"
 one() {  # $1 = tag
-  python bench.py --configs motif3 --steps 3 --warmup 1 --traffic off --no-cpu-baseline --no-standins --detail "$OUT/smi_$1.json" > /dev/null 2> "$OUT/smi_$1.err"
+  python bench.py --full --configs motif3 --steps 3 --warmup 1 --traffic off --no-cpu-baseline --no-standins --detail "$OUT/smi_$1.json" > /dev/null 2> "$OUT/smi_$1.err"
   python - "$OUT/smi_$1.json" "$1" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -10,6 +10,7 @@ and stores the printed counts. EXTRA lists graphs that only get selected (afford
 vector of R-MAT-16 from motif_omp_formula.
 
     python tests/golden/make_golden.py            regenerate everything (hours: house / pentagon of R-MAT-14)
+    python tests/golden/make_golden.py --vs-ref   only tests/golden/oracle_vs_ref.json (the answers behind tests/test_oracle_vs_ref.py)
     python tests/golden/make_golden.py --update   keep what golden.json already holds, run only what is missing Graphs: the two data fixtures (tests/fixtures/{citeseer,cora}) and
 seeded R-MAT graphs produced by graphminer_amd.rmat (only their parameters + a SHA-256 of the
 CSR arrays are stored; the graphs are regenerated deterministically by the tests).
@@ -209,5 +210,31 @@ def main():
         f.write("\n")
 
 
+def vs_ref():
+    """tests/golden/oracle_vs_ref.json: the reference's answers on the seeded graphs of tests/test_oracle_vs_ref.py (+ the first and last
+    line of tc_omp_base on citeseer), so that the oracle is checked against them where the reference binaries are not built"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle as O
+    import test_oracle_vs_ref as T
+    from common import csr_sha as sha
+
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for case in T.CASES:
+            g = T.case_graph(case)
+            if not (0 < g.max_degree < g.V()):
+                continue
+            prefix = os.path.join(td, T.case_key(case), "graph")
+            os.makedirs(os.path.dirname(prefix))
+            g.save(prefix)
+            out[T.case_key(case)] = {"csr_sha256": sha(g), **T.ref_answers(prefix)}
+            print(T.case_key(case), out[T.case_key(case)])
+    lines = O.run_ref("tc_omp_base", os.path.join(ROOT, "tests", "fixtures", "citeseer", "graph"))
+    out["citeseer_tc_omp_base"] = {"first_line": lines[0], "last_line": lines[-1]}
+    with open(os.path.join(ROOT, "tests", "golden", "oracle_vs_ref.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    vs_ref() if "--vs-ref" in sys.argv else main()

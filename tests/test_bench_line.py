@@ -69,3 +69,30 @@ def test_self_launch_is_a_no_op_under_a_launcher(monkeypatch):
     assert bench.self_launch(argparse.Namespace(gpus=8, traffic_worker=False)) is None  # torch.distributed.run already started the ranks
     monkeypatch.delenv("WORLD_SIZE")
     assert bench.self_launch(argparse.Namespace(gpus=1, traffic_worker=False)) is None
+
+
+def test_full_is_off_by_default_and_steps_are_checked(monkeypatch):
+    import pytest
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs == "" and a.steps == 5 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_the_counts_as_float64(tmp_path):
+    import numpy as np
+
+    import bench
+
+    bench.dump_outputs(str(tmp_path / "tc"), {"count": 750506260})
+    bench.dump_outputs(str(tmp_path / "m3"), {"count": [23380, 1166]})
+    tc, m3 = np.load(tmp_path / "tc" / "count.npy"), np.load(tmp_path / "m3" / "count.npy")
+    assert tc.dtype == m3.dtype == np.float64 and tc.tolist() == [750506260.0] and m3.tolist() == [23380.0, 1166.0]

@@ -33,12 +33,12 @@ def check_line(line, raw):
 
 
 def run_bench(*args, env=None, launcher=None):
-    """runs bench.py; returns the FULL record (the --detail file) with the parsed stdout line under "_line" """
+    """runs bench.py --full; returns the FULL record (the --detail file) with the parsed stdout line under "_line" """
     import tempfile
 
     with tempfile.TemporaryDirectory(prefix="gm_bench_test_") as tmp:
         detail = os.path.join(tmp, "detail.json")
-        cmd = (launcher or [sys.executable]) + [os.path.join(ROOT, "bench.py"), *args, "--detail", detail]
+        cmd = (launcher or [sys.executable]) + [os.path.join(ROOT, "bench.py"), *args, "--full", "--detail", detail]
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=dict(os.environ, **(env or {})))
         assert out.returncode == 0, out.stderr[-2000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -361,7 +361,7 @@ def test_scale_dryrun_two_ranks_on_one_gpu():
 
 
 def test_bench_gpus_n_starts_its_own_ranks():
-    """`python bench.py --gpus 2` with NO launcher around it: bench.py re-execs under torch.distributed.run. On this
+    """`python bench.py --gpus 2` with NO launcher around it: bench.py starts torch.distributed.run as a child. On this
     one-GPU box through GM_BENCH_ONE_GPU=1 (both ranks on GPU 0, gloo); without that switch the same command must refuse clearly."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     d = run_bench("--gpus", "2", "--scale", "12", "--ef", "8", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--traffic", "off",
@@ -376,3 +376,43 @@ def test_bench_gpus_n_starts_its_own_ranks():
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale", "12"], capture_output=True, text=True, timeout=300,
                              cwd=ROOT, env=env)
         assert out.returncode != 0 and "only 1 HIP device" in out.stderr and not out.stdout.strip()
+
+
+def run_plain(*args):
+    """runs bench.py WITHOUT --full; returns (parsed stdout line, stderr)"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and out.stdout.rstrip().splitlines()[-1] == lines[0], out.stdout[-2000:]
+    return json.loads(lines[0]), out.stderr
+
+
+def test_plain_run_times_the_headline_alone_and_dumps_its_count(tmp_path):
+    """the default run (no --full): the headline workload only, K timed steps, the headline keys with the meaning of the --full line, and
+    --dump-outputs: the count of the last timed step, equal from run to run and equal to the --full run's headline count"""
+    import numpy as np
+
+    args = ("--gpus", "1", "--scale", "14", "--ef", "8", "--warmup", "1")
+    line, err = run_plain(*args, "--steps", "7", "--dump-outputs", str(tmp_path / "a"))
+    assert "CPU baselines" not in err and "stream ceiling" not in err  # nothing of --full ran
+    assert line["metric"] == "million edges processed/sec + total match count" and line["unit"] == "Medges/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "int32 (vertex ids, offsets; uint64 counts)" and line["steps"] == 7 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["config"]["workload"].startswith("tc") and line["config"]["graph"] == "rmat_s14_ef8_seed42"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - line["config"]["tasks"] / line["ms_per_step"] / 1e3) <= 1e-3 * line["value"] + 1e-3
+    assert line["kernel_ms_avg"] <= line["ms_per_step"] * 1.05
+    for k in ("roofline", "cpu_baseline", "configs", "detail"):
+        assert k not in line, k
+    got = np.load(tmp_path / "a" / "count.npy")
+    assert got.dtype == np.float64 and got.tolist() == [float(line["count"])] and line["count"] > 0
+    line2, _ = run_plain(*args, "--steps", "2", "--dump-outputs", str(tmp_path / "b"))
+    assert line2["steps"] == 2 and np.array_equal(np.load(tmp_path / "b" / "count.npy"), got)
+    full = run_bench(*args, "--steps", "2", "--workload", "tc", "--no-cpu-baseline", "--traffic", "off", "--first-call-repeats", "0")
+    assert full["count"] == line["count"] and full["config"]["graph"] == line["config"]["graph"]
+
+
+def test_plain_run_dumps_every_count_of_a_workload(tmp_path):
+    import numpy as np
+
+    line, _ = run_plain("--workload", "motif3", "--scale", "12", "--ef", "8", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert isinstance(line["count"], list) and len(line["count"]) == 2
+    assert np.load(tmp_path / "count.npy").tolist() == [float(x) for x in line["count"]]
