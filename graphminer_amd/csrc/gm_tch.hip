@@ -33,12 +33,23 @@ constexpr int kTchTilesSmall = GM_TCH_TILES_SMALL;  // ... 1024-bucket kernel
 // R-MAT-24 formula 3-motif, ms: 4 tiles 3.02 / 1.08 / 0.86 / 42.9, 8 tiles 3.04 / 1.12 / 0.90 / 42.1 -- the 2048-bucket kernel has the registers for 8)
 constexpr int kTchFlatTilesSmall = 4, kTchFlatTilesBig = 8;
 
+// lookup lists of at least this many keys are streamed one task at a time, shorter ones flattened 64 to a batch.  Its own threshold
+// (kLongList, 192, also sizes the edge supports' masks and the motif trims of the other kernels): with the hub corner on the matrix
+// cores the lists of 192 .. 383 keys are streamed faster flattened -- one at a time, a list of two or three tile groups waits for
+// its keys with nothing else in flight (R-MAT-22 TC, ms per step: 192: 1.85, 256: 1.73, 384: 1.70, 512: 1.70, 1024: 1.70; R-MAT-24
+// formula 3-motif 24.3 -> 21.7 at 384)
+#ifndef GM_TCH_LONG_LIST
+#define GM_TCH_LONG_LIST 384
+#endif
+constexpr int kTchLongList = GM_TCH_LONG_LIST;
+
 constexpr int kTchOvfCap = 128;
 constexpr unsigned kTchEmpty = 0xffffffffu, kTchMarker = 0xfffffffeu;  // (ids are < 2^31 - 1)
 constexpr unsigned kTchMul = 0x9E3779B1u;
 
-// flattened positions per mark window (a batch of 64 lists below kLongList keys: <= 12224): 8192 beside the 1024-bucket table, 4096
-// beside the 2048-bucket one (the LDS budget of six / four workgroups per CU)
+// flattened positions per mark window (a batch of 64 lists below kTchLongList keys: <= 24512, most have far fewer; a longer batch is
+// streamed window after window): 8192 beside the 1024-bucket table, 4096 beside the 2048-bucket one (the LDS budget of six / four
+// workgroups per CU)
 template <int BITWIN>
 struct alignas(16) TchWave {
   int2 desc[GM_WAVE];              // per non-empty list of the batch: {key_base - offset among the flattened positions, salt of the host row}
@@ -155,7 +166,7 @@ __device__ __forceinline__ unsigned tch_pass(TchLds<STAGE> &B, TchWave<TchLds<ST
   constexpr int TF = STAGE <= 1024 ? kTchFlatTilesSmall : kTchFlatTilesBig;
   unsigned cnt = 0;
   if (wave_max_nonneg(llen_all) == 0) return 0u;  // wave-uniform
-  const bool is_long = llen_all >= kLongList;
+  const bool is_long = llen_all >= kTchLongList;
   const int llen = is_long ? 0 : llen_all;
 
   // ---- long lists: one task at a time, wave-uniform base / salt; the keys of the NEXT tile group are requested before the current
