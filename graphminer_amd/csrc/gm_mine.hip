@@ -442,7 +442,6 @@ __global__ __launch_bounds__(kRectLdsWaves *GM_WAVE) void rect_lds_kernel(const 
       const int lo = p.r.rb[k], lb = p.r.lb[k], sh = 5 - lb;
       const unsigned fm = (1u << sh) - 1u;
       const int words = (min(p.r.rb[k + 1], v0) - lo + (int)fm) >> sh;
-      const unsigned cm = lb == 5 ? 0xffffffffu : (1u << (1 << lb)) - 1u;
       uint4 *m4 = reinterpret_cast<uint4 *>(S.map);
       if (RTN) {
         for (int i = tid; i < ((words + 3) >> 2); i += nthreads) m4[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -455,15 +454,23 @@ __global__ __launch_bounds__(kRectLdsWaves *GM_WAVE) void rect_lds_kernel(const 
         if (lb == 5) {
 #pragma unroll
           for (int u = 0; u < 4; ++u) cnt += (unsigned long long)vv[u] * (unsigned long long)(vv[u] - (vv[u] ? 1u : 0u)) / 2ull;
-        } else {  // packed counters are below 2^16: 32-bit arithmetic, the sum of a word's fields too
+        } else if (lb == 3) {  // 8-bit counters: C(c, 2) < 2^15, the sixteen fields of the uint4 sum below 2^19 in 32 bits
           unsigned s32 = 0u;
 #pragma unroll
           for (int u = 0; u < 4; ++u)
-            for (unsigned f = 0; f <= fm; ++f) {
-              const unsigned c = (vv[u] >> (f << lb)) & cm;
+#pragma unroll
+            for (unsigned f = 0; f < 32u; f += 8u) {
+              const unsigned c = (vv[u] >> f) & 0xffu;
               s32 += (c * (c - (c ? 1u : 0u))) >> 1;
             }
           cnt += (unsigned long long)s32;
+        } else {  // 16-bit counters: C(c, 2) < 2^31, so ONE word's two fields sum below 2^32 -- the four words add in 64 bits (eight ends
+                  // of more than 32.8 K 2-paths each pass 2^32)
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const unsigned c0 = vv[u] & 0xffffu, c1 = vv[u] >> 16;
+            cnt += (unsigned long long)(((c0 * (c0 - (c0 ? 1u : 0u))) >> 1) + ((c1 * (c1 - (c1 ? 1u : 0u))) >> 1));
+          }
         }
       }
     }
