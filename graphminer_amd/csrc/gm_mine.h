@@ -453,7 +453,7 @@ hipError_t launch_core_sym_fill(int nv, int base, int words, long long e0, long 
                                 unsigned short *first_pos, int cu_count, hipStream_t stream);
 bool core_tc_fast_path(const CoreTcParams &p);
 
-// ---- the same counts on the matrix cores (gm_cmma.hip; the default since round 4, tune[6] & 0x20000: the vector-ALU classes above) ----
+// ---- the same counts on the matrix cores (gm_cmma.hip; the default since round 4, tune[6] bit 0x20000: the vector-ALU classes above) ----
 // sum_{i,j} M_ij (M M^T)_ij as FP4 MFMA over 64 x 64 blocks of (i, j).  LDS copy: rows padded to a multiple of 64, row stride = the
 // (even) block width rounded up to 2 mod 4 words, so that the 64 lanes of an operand fragment (32 rows x 2 adjacent words) read 64
 // different banks.  Classes: 0 = whole matrix in 36 KB (d+ <= 512; 4 waves, four workgroups per CU), 1 = whole matrix in 144 KB

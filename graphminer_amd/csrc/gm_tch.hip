@@ -14,7 +14,7 @@
 //     compaction, no bisection;
 //   * a bucket that got more than four entries (0.4 % of them at this load) carries a marker in its last slot; its surplus
 //     entries sit in a list of <= 128 (id, salt) pairs that only the lanes missing in such a bucket consult.  A chunk that overflows
-//     the list (adversarial ids) is looked up by bisection of the row in global memory -- slow, exact (tune[6] & 0x800000 forces it).
+//     the list (adversarial ids) is looked up by bisection of the row in global memory -- slow, exact (tune[6] & GM_T6_HSET_FALLBACK forces it).
 // Chunk table, task lists, parts, dequeue order: those of tct_kernel (the kernel is chosen per launch, gm_launch.hip).
 #include <type_traits>
 #include "gm_flat.h"

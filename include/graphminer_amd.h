@@ -113,21 +113,52 @@ typedef struct gm_launch {
                          [0] task edges per chunk, [1] chunks per dequeue, [2] xs+1 and [3] ys+1 of the direction rule
                          b*(xb+xs*lg a) <= a*(yb+ys*lg b), [4] workgroups per CU, [5] 1 = never stage adjacency in LDS,
                          [7] bits 0..7 xb*16+yb, bits 8.. price of a pass-Y key against a bitmapped row (0 = as a bisection).
-                         [6] bit mask. Alternative implementations (same counts): 0x100 mining kernels ignore the hub bitmaps,
-                         0x200 SgL / TC / 4-clique on the graph as numbered (no degree / topological renumbering), 0x400 SgL wave-per-edge loop nests,
-                         0x800 rectangle / pentagon as wedges + flat intersections, house flattened over (v0,v1,v3), 0x1000 cut
-                         chunks into parts eagerly, 0x2000 swap the two dequeue orders, 0x4000 plain chunk-id order,
-                         0x10000000 diamond / 3-motif by one intersection of the two symmetric lists per edge (the reference's loop
-                         nests; default: from the triangles of the oriented copy), 0x4000000 TC by the chunked mining kernel (default: the shorter list
-                         of every edge against a hashed set, gm_tch.hip),
-                         0x20000 rectangle / house with every counter map in global memory,
-                         0x800000 hashed sets on their global-memory fallback lookup, 0x40000 4-clique in the mining kernel alone,
-                         0x40000000 edge supports (diamond) with one atomic per streamed edge instead of the match masks (gm_sup.hip);
-                         0x80000 / 0x100000 / 0x400000 / 0x1000000 / 0x2000000: variants of the per-edge class kernels (gm_launch.hip).
-                         Ablation (mining kernels): 0x1 skip clique phase 2, 0x2 skip bit-matrix writes, 0x4 no filter,
-                         0x8 / 0x10 / 0x20 filtered-pass stages, 0x40 skip SPLIT chunks, 0x80 only SPLIT chunks,
-                         0x400 skip pass X, 0x8000 skip pass Y (house: flattened form without the LDS S-bitmap) (gm_api.hip / gm_mine.hip). */
+                         [6] bit mask of GM_T6_* (below). */
 } gm_launch;
+
+/* The bits of gm_launch.tune[6]. The values are ABI (callers pass them as numbers): they never change.
+ * Two names may share a value where two solvers read the same bit differently. */
+enum {
+  /* ---- alternative implementations (same counts) ---- */
+  GM_T6_NO_HUB_BITMAPS = 0x100,        /* mining kernels ignore the hub bitmaps */
+  GM_T6_AS_NUMBERED = 0x200,           /* SgL / TC / 4-clique on the graph as numbered (no degree / topological renumbering) */
+  GM_T6_SGL_NESTED = 0x400,            /* SgL wave-per-edge loop nests (diamond: the reference's listing form) */
+  GM_T6_SGL_FLAT = 0x800,              /* rectangle / pentagon as wedges + flat intersections, house flattened over (v0,v1,v3) */
+  GM_T6_EAGER_PARTS = 0x1000,          /* cut every chunk above 4096 estimated entries into parts */
+  GM_T6_SWAP_ORDERS = 0x2000,          /* swap the two dequeue orders */
+  GM_T6_CHUNK_ID_ORDER = 0x4000,       /* plain chunk-id order */
+  GM_T6_HOUSE_NO_BITMAP = 0x8000,      /* house: flattened form without the LDS S-bitmap */
+  GM_T6_GLOBAL_MAPS = 0x20000,         /* rectangle / house with every counter map in global memory */
+  GM_T6_CLIQUE4_MINING = 0x40000,      /* 4-clique in the mining kernel alone (its arena path; no two-phase re-hosted build) */
+  GM_T6_NO_CLASSES = 0x80000,          /* per-edge kernels: every row through the general kernel (SPLIT chunks, dense HBM bitmaps) */
+  GM_T6_FORCE_CLASSES = 0x100000,      /* per-edge kernels: the workgroup classes also on a graph without long rows */
+  GM_T6_KCLIQUE_ANY_WIDTH = 0x200000,  /* k >= 5: the any-width pair count instead of the tile walk */
+  GM_T6_CLASSES_SORTED_COPY = 0x400000, /* class kernels: the sorted LDS copy + bit filter + bisection instead of the hashed set */
+  GM_T6_HSET_FALLBACK = 0x800000,      /* hashed sets on their global-memory fallback lookup */
+  GM_T6_GIANT_SPLIT = 0x1000000,       /* giant rows stay SPLIT chunks of the general kernel (no hashed sets of row pieces) */
+  GM_T6_HROW_MUL32 = 0x2000000,        /* hashed-row classes: the 32-bit multiply of id spaces beyond 2^24 */
+  GM_T6_TC_CHUNKED = 0x4000000,        /* TC by the chunked mining kernel (default: the shorter list of every edge against a
+                                          hashed set, gm_tch.hip) */
+  GM_T6_CLIQUE4_ROW_GATHER = 0x8000000, /* 4-clique: the wide rows of the hub core gathered row by row from the core bitmap
+                                           (default: by blocks of core rows resident in LDS) */
+  GM_T6_PER_EDGE = 0x10000000,         /* diamond / 3-motif by one intersection of the two symmetric lists per edge (the reference's
+                                          loop nests; default: from the triangles of the oriented copy) */
+  GM_T6_NO_KEYSTREAM = 0x20000000,     /* TC / edge supports without the key stream: every edge a task of the lists, read from their rows */
+  GM_T6_SUP_ATOMICS = 0x40000000,      /* edge supports (diamond) with one atomic per streamed edge instead of the match masks (gm_sup.hip) */
+  /* ---- ablation (mining kernels: work is skipped, counts wrong) ---- */
+  GM_T6_ABL_SKIP_CLIQUE_PHASE2 = 0x1,  /* skip clique phase 2 */
+  GM_T6_ABL_SKIP_BITMATRIX = 0x2,      /* skip bit-matrix writes */
+  GM_T6_ABL_NO_FILTER = 0x4,           /* no filter */
+  GM_T6_ABL_FILTER_STAGE0 = 0x8,       /* filtered-pass stages, first */
+  GM_T6_ABL_FILTER_STAGE1 = 0x10,      /* filtered-pass stages, second */
+  GM_T6_ABL_FILTER_STAGE2 = 0x20,      /* filtered-pass stages, third (k >= 5: the per-sub-tree walk everywhere, same counts) */
+  GM_T6_ABL_SKIP_SPLIT = 0x40,         /* skip SPLIT chunks */
+  GM_T6_ABL_ONLY_SPLIT = 0x80,         /* only SPLIT chunks */
+  GM_T6_ABL_SKIP_PASS_X = 0x400,       /* skip pass X */
+  GM_T6_ABL_SKIP_PASS_Y = 0x8000,      /* skip pass Y */
+  /* ---- the low 16 bits reach the mining kernels as they are (MineParams::flags bits 1..16, gm_mine.hip) ---- */
+  GM_T6_KERNEL_FLAGS_MASK = 0xffff
+};
 
 typedef struct gm_stats {
   double kernel_ms;  /* HIP-event time of the mining kernel(s) on the launch stream (0 when d_counts is set
@@ -194,11 +225,11 @@ int gm_tc_core_info(const gm_graph *dag, int64_t info[4]);
  * src/sgl/omp_base.cc:33-49 beyond house / pentagon) -> GM_ERR_UNSUPPORTED, *total = 0.
  * With world > 1 a rank's house / pentagon value is a partial MODULO 2^64 (a centre's positive and negative terms may be tasks of different
  * ranks): add the ranks' values as uint64 (an all-reduce does), do not compare a single rank's value with anything.
- * rectangle / house keep the counter maps of their heavy centres in LDS (gm_mine.hip rect_lds_kernel / house_lds_kernel; tune[6] & 0x20000:
+ * rectangle / house keep the counter maps of their heavy centres in LDS (gm_mine.hip rect_lds_kernel / house_lds_kernel; tune[6] & GM_T6_GLOBAL_MAPS:
  * in global memory, round 5's form).
  * diamond = sum over the edges of C(|N(v0) ^ N(v1)|, 2). One GPU: |N(v0) ^ N(v1)| of every edge -- its triangles -- from ONE pass over
  * the triangles of the oriented copy (edge supports, gm_sup.hip; the copy is built and cached on first use; also for a graph of
- * >= 2^31 entries); world > 1, a DAG row beyond 2048 entries, or tune[6] & 0x10000000: one intersection of the two symmetric lists per
+ * >= 2^31 entries); world > 1, a DAG row beyond 2048 entries, or tune[6] & GM_T6_PER_EDGE: one intersection of the two symmetric lists per
  * edge (gm_hrow.hip, gm_chunk.h). Same count. */
 int gm_sgl(const gm_graph *sym, const char *pattern, const gm_launch *launch, uint64_t *total, gm_stats *stats);
 
@@ -244,7 +275,7 @@ int gm_diamond_support_finish(const gm_graph *sym, const gm_launch *launch, cons
  * them with two words per lane, longer rows out of the workgroup's global scratch (slow, exact; the degree-ordered DAG of com-Orkut has
  * rows of at most 535 entries, of a scale-24 R-MAT graph 1744). The workgroups' scratch slots must fit the device memory, else
  * GM_ERR_TOO_LARGE -- a count is refused, never wrong. TC (k = 3) and k = 4 run on a topologically renumbered copy of a DAG whose
- * rows are long (cached on the handle; tune[6] & 0x200: as numbered). */
+ * rows are long (cached on the handle; tune[6] & GM_T6_AS_NUMBERED: as numbered). */
 int gm_clique(const gm_graph *dag, int k, const gm_launch *launch, uint64_t *total, gm_stats *stats);
 
 /* MotifSolver on the SYMMETRIC graph. k = 3: counts[0] = wedges, counts[1] = triangles
@@ -252,7 +283,7 @@ int gm_clique(const gm_graph *dag, int k, const gm_launch *launch, uint64_t *tot
  * src/motif/gpu_kernels/motif3_edge_warp.cuh:19-22). ncounts must be
  * num_possible_patterns[k] (include/pattern.hh:4-15): 2 for k = 3, 6 for k = 4 (see gm_motif4_partial).
  * k = 3 takes the reference's formula solver by default (gm_motif_formula below: the triangles of the oriented copy, wedges derived);
- * tune[6] & 0x10000000: automine_3motif's enumeration, one bounded intersection of the two symmetric lists per edge. Same counts;
+ * tune[6] & GM_T6_PER_EDGE: automine_3motif's enumeration, one bounded intersection of the two symmetric lists per edge. Same counts;
  * stats->tasks = the graph's directed entries either way.
  * With world > 1 a rank's wedge value is a partial modulo 2^64 (formula: rank 0 contributes sum C(d,2); enumeration: one intersection
  * per undirected edge serves both directed edges, which may belong to different ranks); the uint64 sum over ranks is the exact count. */

@@ -27,6 +27,27 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.gm_strerror(_lib.GM_ERR_UNSUPPORTED) == b"Not implemented"
 
 
+def test_tune6_bit_values_are_abi():
+    """The GM_T6_* names of include/graphminer_amd.h: callers pass the bits of gm_launch.tune[6] as numbers, so a renumbering must fail here."""
+    want = {
+        "NO_HUB_BITMAPS": 0x100, "AS_NUMBERED": 0x200, "SGL_NESTED": 0x400, "SGL_FLAT": 0x800, "EAGER_PARTS": 0x1000,
+        "SWAP_ORDERS": 0x2000, "CHUNK_ID_ORDER": 0x4000, "HOUSE_NO_BITMAP": 0x8000, "GLOBAL_MAPS": 0x20000,
+        "CLIQUE4_MINING": 0x40000, "NO_CLASSES": 0x80000, "FORCE_CLASSES": 0x100000, "KCLIQUE_ANY_WIDTH": 0x200000,
+        "CLASSES_SORTED_COPY": 0x400000, "HSET_FALLBACK": 0x800000, "GIANT_SPLIT": 0x1000000, "HROW_MUL32": 0x2000000,
+        "TC_CHUNKED": 0x4000000, "CLIQUE4_ROW_GATHER": 0x8000000, "PER_EDGE": 0x10000000, "NO_KEYSTREAM": 0x20000000,
+        "SUP_ATOMICS": 0x40000000,
+        "ABL_SKIP_CLIQUE_PHASE2": 0x1, "ABL_SKIP_BITMATRIX": 0x2, "ABL_NO_FILTER": 0x4, "ABL_FILTER_STAGE0": 0x8,
+        "ABL_FILTER_STAGE1": 0x10, "ABL_FILTER_STAGE2": 0x20, "ABL_SKIP_SPLIT": 0x40, "ABL_ONLY_SPLIT": 0x80,
+        "ABL_SKIP_PASS_X": 0x400, "ABL_SKIP_PASS_Y": 0x8000,
+        "KERNEL_FLAGS_MASK": 0xFFFF,
+    }
+    header = open(os.path.join(ROOT, "include", "graphminer_amd.h")).read()
+    got = {name: int(value, 0) for name, value in re.findall(r"^\s*GM_T6_([A-Z0-9_]+)\s*=\s*(0[xX][0-9a-fA-F]+|\d+)\s*,?", header, re.M)}
+    assert got == want
+    bits = [v for k, v in want.items() if k != "KERNEL_FLAGS_MASK"]
+    assert all(v > 0 and v & (v - 1) == 0 and v < (1 << 31) for v in bits)  # single bits of an int32
+
+
 def test_no_device_is_an_error_not_a_fallback():
     """On a box without a GPU every compute entry point must fail loudly."""
     import torch
