@@ -261,6 +261,8 @@ extern "C" void gm_graph_free(gm_graph *g) {
   if (g->d_trpl) dev_free(g->d_trpl);
   if (g->d_tdescl) dev_free(g->d_tdescl);
   if (g->d_sup) dev_free(g->d_sup);
+  for (void *q : {(void *)g->d_w5sup, (void *)g->d_w5ed, (void *)g->d_w5deg, (void *)g->d_w5tv2, (void *)g->d_w5out})
+    if (q) dev_free(q);
   free_clique_plans(g);
   if (g->d_wide_mat) dev_free(g->d_wide_mat);
   if (g->d_wide_sorted) dev_free(g->d_wide_sorted);
@@ -314,6 +316,7 @@ int finish_handle(gm_graph *g) {
     gm_touch_hrow();
     gm_touch_tch();
     gm_touch_sup();
+    gm_touch_wtri();
     gm_touch_cbuild();
     gm_touch_cmma();
     gm_touch_cgather();

@@ -310,6 +310,12 @@ struct gm_graph {
   int n_long_rows = -1;               // -1: not looked for yet
   long long long_edges = 0;
   unsigned *d_sup = nullptr;  // edge supports: one counter per DAG entry (gm_sup.hip)
+  // the 5-vertex closed forms (gm_wtri.hip, gm_sgl5_raw): a support array of their own (the diamond's d_sup is not touched), d(u) + d(v) per
+  // entry, the symmetric degrees (built once), 2 T_v per vertex, and the eight sums of one call
+  unsigned *d_w5sup = nullptr, *d_w5ed = nullptr;
+  int *d_w5deg = nullptr;
+  unsigned long long *d_w5tv2 = nullptr, *d_w5out = nullptr;
+  bool w5_tri = false, w5_vert = false;  // what the PAT_WTRI launch in flight was asked for (gm_sgl5_raw)
   // ... and the MATCH MASKS of the in-edge tasks with long tails (ensure_sup_masks, gm_tables.hip): per DAG entry / per task the offset of
   // the task's mask in the arena (64-bit words; kNoMask: the task keeps its atomics), the arena itself (written and read by every launch)
   unsigned *d_emoff = nullptr, *d_tmoff = nullptr;
@@ -528,6 +534,7 @@ void gm_touch_mine_wide();
 void gm_touch_hrow();
 void gm_touch_tch();
 void gm_touch_sup();
+void gm_touch_wtri();
 void gm_touch_cbuild();
 void gm_touch_cmma();
 void gm_touch_cgather();

@@ -206,7 +206,7 @@ static GraphView graph_view(const gm_graph *g) {
 // What a launch of run_pattern decided (plan_pattern) and the tables it runs on.
 struct PatternPlan {
   Pattern pat = PAT_TC;        // (the edge supports run as PAT_TC: the triangle pass of the task lists with another match handler)
-  bool support = false, sup_part = false, clique = false, sym_pat = false;
+  bool support = false, sup_part = false, wtri = false, clique = false, sym_pat = false;
   bool use_tct = false, split_stage = false, tct_long = false, use_kst = false, sup_masks = false, tc_core = false, sup_core = false;
   bool use_wide = false, use_classes = false, use_range = false;
   int target = 0, tct_stage = 0, corner_from = 0x7fffffff, cls_lo = 0;
@@ -300,7 +300,7 @@ static int plan_pattern(const LaunchCtx &c, PatternPlan &pl) {
     // match made the diamond 13.4 ms where the task lists take 2.8.  The density is estimated from a sample of the entries
     // (ensure_tri_per_edge): the stream below 0.5 triangles per entry (power law: 0.1, flat: 0).  GM_SUP_STREAM=0 / 1 forces it.
     bool sup_stream = false;
-    if (pl.support && !(la->tune[6] & GM_T6_NO_KEYSTREAM)) {
+    if (pl.support && !pl.wtri && !(la->tune[6] & GM_T6_NO_KEYSTREAM)) {  // (the weighted pass reads the full task lists)
       if (const char *e = gm_opt("GM_SUP_STREAM")) sup_stream = atoi(e) != 0;
       else sup_stream = ensure_mean_sq_deg(g) == GM_OK && g->mean_sq_deg < (double)kSupStreamMaxMeanRow && ensure_tri_per_edge(g) == GM_OK &&
                         g->tri_per_edge < 0.5;
@@ -312,10 +312,10 @@ static int plan_pattern(const LaunchCtx &c, PatternPlan &pl) {
       if (const int rc_t = ensure_tasklists(g, pl.support)) return rc_t;
     }
   }
-  if (pl.support && !pl.sup_part && !g->d_sup) HIP_TRY(dev_malloc(&g->d_sup, sizeof(unsigned) * (size_t)std::max<long long>(g->ne, 1)));
+  if (pl.support && !pl.sup_part && !pl.wtri && !g->d_sup) HIP_TRY(dev_malloc(&g->d_sup, sizeof(unsigned) * (size_t)std::max<long long>(g->ne, 1)));
   // match masks instead of one atomic per streamed edge (gm_sup.hip): one GPU, the task lists, a topologically numbered DAG
   // (tune[6] & GM_T6_SUP_ATOMICS: A/B switch, every streamed edge by an atomic)
-  if (pl.support && !pl.sup_part && world == 1 && pl.use_tct && !pl.use_kst && !(la->tune[6] & GM_T6_SUP_ATOMICS)) {
+  if (pl.support && !pl.sup_part && !pl.wtri && world == 1 && pl.use_tct && !pl.use_kst && !(la->tune[6] & GM_T6_SUP_ATOMICS)) {
     if (const int rc_m = ensure_sup_masks(g)) return rc_m;
     pl.sup_masks = g->smask_state == 1;
   }
@@ -339,7 +339,7 @@ static int plan_pattern(const LaunchCtx &c, PatternPlan &pl) {
   // the triangles of the hub corner on the matrix cores (gm_ctc.hip): this handle's key stream holds no task of the corner's rows
   pl.corner_from = pl.use_kst ? g->kst_skip_from : (pl.use_tct ? g->tl_skip_from : 0x7fffffff);  // the rows the stream / the task lists in use leave out
   pl.tc_core = pl.use_tct && !pl.support && pl.corner_from < g->nv;
-  pl.sup_core = pl.support && !pl.use_kst && pl.corner_from < g->nv;
+  pl.sup_core = pl.support && !pl.wtri && !pl.use_kst && pl.corner_from < g->nv;  // (the weighted pass walks the corner's out-edges itself)
   if (pl.sup_core) {
     if (const int rc_c = ensure_sup_corner(g)) return rc_c;
   }
@@ -860,14 +860,16 @@ static int launch_classes(PatternRun &r) {
 
 // The tables of the task-list kernels, one after the other on the launch stream.  support: the edge supports' kernel (launch_sup / sup_per_cu,
 // gm_sup.hip) instead of the triangle count's (launch_tch / tch_per_cu, gm_tch.hip).
-static int launch_task_tables(PatternRun &r, bool support) {
+enum TaskKernel : int { TK_TC = 0, TK_SUPPORT = 1, TK_WTRI = 2 };
+static int launch_task_tables(PatternRun &r, int kind) {
   gm_graph *g = r.ctx.g;
   hipStream_t stream = r.ctx.stream;
   const PatternPlan &pl = r.pl;
   const MineParams &p = r.p;
+  const WtriParams wp = {g->d_w5sup, g->d_w5ed, g->d_w5deg};
   auto launch = [&](const MineParams &q, int stage, long long dequeues) {
-    const int grid = grid_for(dequeues, g->cu_count, support ? sup_per_cu(stage) : tch_per_cu(stage));
-    return support ? launch_sup(q, stage, grid, stream) : launch_tch(q, stage, grid, stream);
+    const int grid = grid_for(dequeues, g->cu_count, kind == TK_WTRI ? wtri_per_cu(stage) : kind == TK_SUPPORT ? sup_per_cu(stage) : tch_per_cu(stage));
+    return kind == TK_WTRI ? launch_wtri(q, wp, stage, grid, stream) : kind == TK_SUPPORT ? launch_sup(q, stage, grid, stream) : launch_tch(q, stage, grid, stream);
   };
   if (pl.tab_big) {  // the hosts with rows of 1025 .. 2048 entries first (the heaviest tasks), on the 2048-entry kernel
     MineParams q = p;
@@ -915,7 +917,7 @@ static int launch_tc(PatternRun &r) {
       HIP_TRY(launch_mine(pl.pat, q, grid_for(wq, g->cu_count, r.per_cu), stream));
     }
   }
-  if (int rc = launch_task_tables(r, false)) return rc;
+  if (int rc = launch_task_tables(r, TK_TC)) return rc;
   if (pl.tc_core) {  // the out-edges of the hub corner: one masked bit-matrix product; a rank takes every world-th block
     CoreTcParams cp;
     memset(&cp, 0, sizeof cp);
@@ -940,7 +942,7 @@ static int launch_supports(PatternRun &r, unsigned *sup_out) {
   unsigned *sup = pl.sup_part ? sup_out : g->d_sup;
   HIP_TRY(hipMemsetAsync(sup, 0, sizeof(unsigned) * (size_t)(pl.sup_part ? diamond_support_entries(g->ne, world) : g->ne), stream));
   r.p.scratch = sup;
-  if (int rc = launch_task_tables(r, true)) return rc;
+  if (int rc = launch_task_tables(r, TK_SUPPORT)) return rc;
   if (pl.tct_long && g->n_long_rows > 0) {
     SupLongParams sl;
     memset(&sl, 0, sizeof sl);
@@ -987,6 +989,40 @@ static int launch_supports(PatternRun &r, unsigned *sup_out) {
   return GM_OK;
 }
 
+// The 5-vertex closed forms on the DAG (gm_wtri.hip; gm_sgl5_raw filled g->d_w5sup and says what it wants): the per-entry sums and the
+// scatter into 2 T_v, the support-weighted second pass over the triangles (A, B -> counters[0], [1]) -- the task tables, then the out-edges
+// no task list holds: the rows beyond the stage or the rows of the hub corner -- and the per-vertex sums.  All inside the timed region.
+static int launch_weighted(PatternRun &r) {
+  gm_graph *g = r.ctx.g;
+  hipStream_t stream = r.ctx.stream;
+  const PatternPlan &pl = r.pl;
+  HIP_TRY(hipMemsetAsync(g->d_w5out, 0, 64, stream));
+  HIP_TRY(hipMemsetAsync(g->d_w5tv2, 0, sizeof(unsigned long long) * (size_t)std::max(g->nv, 1), stream));
+  WtriEntryParams ep;
+  memset(&ep, 0, sizeof ep);
+  ep.nv = g->nv; ep.ne = g->ne; ep.rp = g->d_rp; ep.col = g->d_col; ep.sup = g->d_w5sup; ep.deg = g->d_w5deg;
+  ep.ed = g->d_w5ed; ep.tv2 = g->d_w5tv2; ep.out = g->d_w5out;
+  HIP_TRY(launch_wtri_entries(ep, g->cu_count, stream));
+  if (g->w5_tri) {
+    if (int rc = launch_task_tables(r, TK_WTRI)) return rc;
+    const WtriParams wp = {g->d_w5sup, g->d_w5ed, g->d_w5deg};
+    WtriEdgeParams we;
+    memset(&we, 0, sizeof we);
+    we.rp = g->d_rp; we.col = g->d_col; we.nv = g->nv; we.ne = g->ne;
+    we.topo = (g->topo_state == 1 && !gm_sweep_env("GM_TC_NO_TRIM")) ? 1 : 0;
+    we.counters = g->d_counters;
+    if (pl.tct_long && g->n_long_rows > 0) {
+      we.rows = g->d_long_rows; we.prefix = g->d_long_prefix; we.nrows = g->n_long_rows; we.total = g->long_edges;
+      HIP_TRY(launch_wtri_edges(we, wp, g->cu_count, stream));
+    } else if (pl.corner_from < g->nv) {
+      we.v0 = pl.corner_from; we.total = g->ne;
+      HIP_TRY(launch_wtri_edges(we, wp, g->cu_count, stream));
+    }
+  }
+  if (g->w5_vert) HIP_TRY(launch_wtri_vertices(g->nv, g->d_w5tv2, g->d_w5deg, g->d_w5out, g->cu_count, stream));
+  return GM_OK;
+}
+
 int run_pattern(Pattern pat, const gm_graph *cg, const gm_launch *la, int k, uint64_t *h_out, int nout, gm_stats *st, int fin_mode,
                 unsigned long long fin_base, unsigned *sup_out) {
   PatternRun r;
@@ -996,7 +1032,8 @@ int run_pattern(Pattern pat, const gm_graph *cg, const gm_launch *la, int k, uin
   // (PAT_SUPPORT_PART: the share of a rank -- any world -- of the supports only, added into the caller's zeroed buffer: the ranks' arrays
   // are summed by a reduce-scatter and gm_diamond_support_finish takes sum C(t, 2) of a slice)
   pl.sup_part = pat == PAT_SUPPORT_PART;
-  pl.support = pat == PAT_SUPPORT || pl.sup_part;
+  pl.wtri = pat == PAT_WTRI;  // (the weighted pass of the 5-vertex closed forms: the same tables and task lists, gm_wtri.hip)
+  pl.support = pat == PAT_SUPPORT || pl.sup_part || pl.wtri;
   if (pl.sup_part && !sup_out) return GM_ERR_INVALID;
   pl.pat = pl.support ? PAT_TC : pat;
   if (fin_mode < 0) fin_mode = (pl.pat == PAT_MOTIF3) ? FIN_MOTIF3 : FIN_COPY;
@@ -1018,7 +1055,8 @@ int run_pattern(Pattern pat, const gm_graph *cg, const gm_launch *la, int k, uin
   if (pl.use_classes)
     if (int rc = launch_classes(r)) return rc;
   int rc = GM_OK;
-  if (pl.support) rc = launch_supports(r, sup_out);
+  if (pl.wtri) rc = launch_weighted(r);
+  else if (pl.support) rc = launch_supports(r, sup_out);
   else if (pl.use_tct) rc = launch_tc(r);
   else if (r.p.count > 0) HIP_TRY(launch_mine(pl.pat, r.p, r.grid, stream));
   if (rc) return rc;
@@ -1910,6 +1948,139 @@ extern "C" int gm_sgl4_finish(const char *pattern, const uint64_t raw[4], uint64
   return GM_OK;
 }
 
+// ---- the six 5-vertex patterns of src/sgl/omp_base.cc:29-45 as closed forms of eleven raw sums (DESIGN.md "SgL, 5-vertex closed forms") ----
+enum Sgl5Raw : int { R5_T = 0, R5_D, R5_W, R5_A, R5_B, R5_H, R5_S, R5_P, R5_K4, R5_R, R5_Q };
+static_assert(R5_Q + 1 == GM_SGL5_NRAW, "the order of the raw sums is ABI");
+// the raw sums a pattern needs as a bit mask (0: not one of the six); "all": every sum
+static unsigned sgl5_needs(const char *pattern) {
+  if (!pattern) return 0u;
+  auto b = [](int i) { return 1u << i; };
+  if (strcmp(pattern, "hourglass") == 0) return b(R5_H) | b(R5_D);
+  if (strcmp(pattern, "taileddiamond2") == 0) return b(R5_W);
+  if (strcmp(pattern, "taileddiamond") == 0) return b(R5_A) | b(R5_K4);
+  if (strcmp(pattern, "semihouse") == 0) return b(R5_B) | b(R5_K4);
+  if (strcmp(pattern, "closedhouse") == 0) return b(R5_Q);
+  if (strcmp(pattern, "5path") == 0) return b(R5_P) | b(R5_S) | b(R5_T) | b(R5_R);
+  return 0u;
+}
+
+extern "C" int gm_sgl5_finish(const char *pattern, const uint64_t raw[GM_SGL5_NRAW], uint64_t *total) {
+  if (!sgl5_needs(pattern) || !raw || !total) return GM_ERR_INVALID;
+  if (strcmp(pattern, "hourglass") == 0) *total = raw[R5_H] - 2ull * raw[R5_D];
+  else if (strcmp(pattern, "taileddiamond2") == 0) *total = raw[R5_W];
+  else if (strcmp(pattern, "taileddiamond") == 0) *total = raw[R5_A] - 12ull * raw[R5_K4];
+  else if (strcmp(pattern, "semihouse") == 0) *total = raw[R5_B] - 12ull * raw[R5_K4];
+  else if (strcmp(pattern, "closedhouse") == 0) *total = raw[R5_Q];
+  else *total = raw[R5_P] - 2ull * raw[R5_S] + 9ull * raw[R5_T] - 4ull * raw[R5_R];
+  return GM_OK;
+}
+
+// the per-handle arrays of the weighted pass on the DAG it runs on; the symmetric degrees are built once
+static int ensure_w5_buffers(gm_graph *g) {
+  std::lock_guard<std::mutex> lk(g->mu);
+  if (g->d_w5out) return GM_OK;
+  HIP_TRY(hipSetDevice(g->device));
+  const size_t ne = (size_t)std::max<long long>(g->ne, 1), nv = (size_t)std::max(g->nv, 1);
+  if (!g->d_w5sup) HIP_TRY(dev_malloc(&g->d_w5sup, sizeof(unsigned) * (size_t)diamond_support_entries(g->ne, 1)));
+  if (!g->d_w5ed) HIP_TRY(dev_malloc(&g->d_w5ed, sizeof(unsigned) * ne));
+  if (!g->d_w5tv2) HIP_TRY(dev_malloc(&g->d_w5tv2, sizeof(unsigned long long) * nv));
+  if (!g->d_w5deg) {
+    HIP_TRY(dev_malloc(&g->d_w5deg, sizeof(int) * nv));
+    HIP_TRY(launch_wtri_degrees(g->nv, g->ne, g->d_rp, g->d_col, g->d_w5deg, g->cu_count, 0));
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  HIP_TRY(dev_malloc(&g->d_w5out, 64));
+  return GM_OK;
+}
+
+// one kernel of the symmetric graph that leaves ONE sum in counters[0] (P, Q): a launch of its own on the handle
+template <class Launch>
+static int run_sym_sum(const gm_graph *sym, const gm_launch *la, uint64_t *out, double *ms, Launch launch) {
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, la, out, ctx)) return rc;
+  if (int rc = start_timer(ctx)) return rc;
+  if (int rc = launch(ctx)) return rc;
+  gm_stats s;
+  memset(&s, 0, sizeof s);
+  if (int rc = end_launch(ctx, FIN_COPY, 0, out, 1, &s)) return rc;
+  *ms += s.kernel_ms;
+  return GM_OK;
+}
+
+extern "C" int gm_sgl5_raw(const gm_graph *sym, const char *pattern, const gm_launch *la, uint64_t raw[GM_SGL5_NRAW], gm_stats *st) {
+  if (!sym || !pattern || !raw) return GM_ERR_INVALID;
+  const unsigned needs = strcmp(pattern, "all") == 0 ? (1u << GM_SGL5_NRAW) - 1u : sgl5_needs(pattern);
+  if (!needs) return GM_ERR_INVALID;
+  for (int i = 0; i < GM_SGL5_NRAW; ++i) raw[i] = 0;
+  if (int rc0 = reject_big(sym)) return rc0;
+  // the divisions and halvings need the sums of the whole graph, and the total is put together on the host: one rank, synchronous
+  if (la && (la->world > 1 || la->d_counts)) return GM_ERR_UNSUPPORTED;
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2;
+  memset(&l2, 0, sizeof l2);
+  if (la) l2 = *la;
+  auto need = [&](int i) { return (needs >> i & 1u) != 0; };
+  double ms = 0.0;
+  gm_stats s;
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  if (sym->ne == 0) return GM_OK;
+  if (need(R5_T) || need(R5_D) || need(R5_W) || need(R5_A) || need(R5_B) || need(R5_H) || need(R5_S)) {
+    // the supports of every entry of the oriented copy, filled like a one-rank gm_diamond_support_partial (rows beyond the stage through
+    // sup_long_kernel), into an array of the 5-vertex forms' own; then the sums over entries, triangles and vertices
+    gm_graph *run_on = nullptr;
+    if (int rc = diamond_run_on(sym, &l2, &run_on)) return rc;
+    if (int rc = ensure_w5_buffers(run_on)) return rc;
+    uint64_t dummy = 0, ab[4] = {0, 0, 0, 0};
+    memset(&s, 0, sizeof s);
+    if (int rc = run_pattern(PAT_SUPPORT_PART, run_on, &l2, 3, &dummy, 1, &s, -1, 0, run_on->d_w5sup)) return rc;
+    ms += s.kernel_ms;
+    run_on->w5_tri = need(R5_A) || need(R5_B);
+    run_on->w5_vert = need(R5_H) || need(R5_S);
+    memset(&s, 0, sizeof s);
+    if (int rc = run_pattern(PAT_WTRI, run_on, &l2, 3, ab, 4, &s, FIN_RAW4, 0)) return rc;
+    ms += s.kernel_ms;
+    unsigned long long o[5] = {0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpy(o, run_on->d_w5out, sizeof o, hipMemcpyDeviceToHost));  // (run_pattern has synchronised the stream)
+    const uint64_t v[7] = {o[0] / 3ull, o[1], o[2], ab[0], ab[1], o[3], o[4]};
+    const int at[7] = {R5_T, R5_D, R5_W, R5_A, R5_B, R5_H, R5_S};
+    for (int i = 0; i < 7; ++i)
+      if (need(at[i])) raw[at[i]] = v[i];
+  }
+  if (need(R5_K4)) {
+    if (const int rc_dag = ensure_dag_cache(g)) return rc_dag;
+    memset(&s, 0, sizeof s);
+    if (int rc = gm_clique(g->dag_cache, 4, &l2, &raw[R5_K4], &s)) return rc;
+    ms += s.kernel_ms;
+  }
+  if (need(R5_R)) {
+    memset(&s, 0, sizeof s);
+    if (int rc = gm_sgl(sym, "rectangle", &l2, &raw[R5_R], &s)) return rc;
+    ms += s.kernel_ms;
+  }
+  if (need(R5_P)) {
+    if (int rc = run_sym_sum(sym, &l2, &raw[R5_P], &ms, [&](LaunchCtx &c) {
+          HIP_TRY(launch_path5(g->nv, g->d_rp, g->d_col, g->d_counters, g->cu_count, c.stream));
+          return (int)GM_OK;
+        })) return rc;
+  }
+  if (need(R5_Q)) {
+    const int grid = chouse_grid(g->ne, g->cu_count);
+    if (int rc = ensure_scratch(g, sizeof(int) * (size_t)grid * 4 * (size_t)std::max(g->max_deg, 1))) return rc;
+    if (int rc = run_sym_sum(sym, &l2, &raw[R5_Q], &ms, [&](LaunchCtx &c) {
+          ChouseParams cp;
+          memset(&cp, 0, sizeof cp);
+          cp.nv = g->nv; cp.ne = g->ne; cp.rp = g->d_rp; cp.col = g->d_col;
+          cp.scratch = reinterpret_cast<int *>(g->d_scratch); cp.max_deg = std::max(g->max_deg, 1); cp.out = g->d_counters;
+          HIP_TRY(launch_chouse(cp, grid, c.stream));
+          return (int)GM_OK;
+        })) return rc;
+  }
+  g->ring_alias = nullptr;
+  g->ring_extra[0] = g->ring_extra[1] = nullptr;
+  if (st) st->kernel_ms = ms;
+  return GM_OK;
+}
+
 extern "C" int gm_sgl(const gm_graph *sym, const char *pattern, const gm_launch *la, uint64_t *total, gm_stats *st) {
   if (!pattern) return GM_ERR_INVALID;
   if (strcmp(pattern, "diamond") == 0) {
@@ -1979,7 +2150,17 @@ extern "C" int gm_sgl(const gm_graph *sym, const char *pattern, const gm_launch 
     const int rc = gm_sgl4_partial(sym, la, raw, st);
     return rc ? rc : gm_sgl4_finish(pattern, raw, total);
   }
-  if (total) *total = 0;  // "Not implemented", total_num = 0 (src/sgl/omp_base.cc:51-53)
+  // The six 5-vertex patterns beyond house / pentagon (5path, semihouse, closedhouse, hourglass, taileddiamond, taileddiamond2): closed
+  // forms of eleven raw sums over edge supports, triangles and degrees (gm_sgl5_raw / gm_sgl5_finish, gm_wtri.hip).  One rank, and the total
+  // is put together on the host: world > 1 or d_counts -> GM_ERR_UNSUPPORTED.
+  if (sgl5_needs(pattern)) {
+    if (total) *total = 0;
+    if (!total) return (la && la->d_counts) ? GM_ERR_UNSUPPORTED : GM_ERR_INVALID;
+    uint64_t raw[GM_SGL5_NRAW];
+    const int rc = gm_sgl5_raw(sym, pattern, la, raw, st);
+    return rc ? rc : gm_sgl5_finish(pattern, raw, total);
+  }
+  if (total) *total = 0;  // "Not implemented", total_num = 0 (src/sgl/omp_base.cc:51-53): 6path, dumbbell
   return GM_ERR_UNSUPPORTED;
 }
 

@@ -128,7 +128,8 @@ enum Pattern : int { PAT_TC = 0, PAT_DIAMOND = 1, PAT_MOTIF3 = 2, PAT_CLIQUE4 = 
                      PAT_DAGSTATS = 6 /* tooling: sum n, sum n^2, sum_{matches} d+(w) for the 4-clique algorithmic bytes */,
                      PAT_SUPPORT = 7 /* edge supports from the DAG's triangles + sum C(t, 2): the diamond count (gm_sup.hip) */,
                      PAT_SUPPORT_PART = 8 /* ... a rank's share of the supports only, into the caller's buffer (gm_diamond_support_partial) */,
-                     PAT_CLIQUEK_DEEP = 9 /* kernel side only: the instance of the mining kernel PAT_CLIQUEK launches for k = 9..12 (gm_chunk.h) */ };
+                     PAT_CLIQUEK_DEEP = 9 /* kernel side only: the instance of the mining kernel PAT_CLIQUEK launches for k = 9..12 (gm_chunk.h) */,
+                     PAT_WTRI = 10 /* the support-weighted second pass over the triangles + the per-entry / per-vertex sums (gm_wtri.hip) */ };
 
 // Symmetric-graph patterns stage up to 3072 entries: on skewed graphs thousands of rows have 1-3 K neighbours; with a
 // 1024-entry stage they are SPLIT rows whose keys are bisected in HBM, otherwise ordinary staged chunks behind
@@ -583,6 +584,49 @@ struct SupColsParams {
 };
 hipError_t launch_sup_cols(const SupColsParams &p, int cu_count, hipStream_t stream);
 hipError_t launch_sup_pairs(const unsigned *sup, long long first, long long count, unsigned long long *out, int cu_count, hipStream_t stream);
+// the raw sums of the 5-vertex closed forms (gm_wtri.hip): the support-weighted second pass over the triangles of the task lists, the
+// per-entry / per-vertex sums around it, and the two kernels on the symmetric graph
+struct WtriParams {
+  const unsigned *sup;  // per DAG entry: its support, complete
+  const unsigned *ed;   // per DAG entry u -> v: d(u) + d(v), symmetric degrees
+  const int *deg;       // per vertex: symmetric degree
+};
+struct WtriEdgeParams {
+  const int *rp, *col;
+  const int *rows;            // the rows beyond the stage (nullptr: the rows from v0 on)
+  const long long *prefix;    // prefix[r] = task edges of the rows before r
+  int nrows, nv, v0;
+  long long ne, total;        // total: the edges of `rows` (rows == nullptr: an upper bound, the kernel counts from rp[v0])
+  int topo;
+  unsigned long long *counters;  // [0] += A, [1] += B
+};
+struct WtriEntryParams {
+  int nv;
+  long long ne;
+  const int *rp, *col;
+  const unsigned *sup;
+  const int *deg;
+  unsigned *ed;
+  unsigned long long *tv2;  // per vertex: twice its triangles (zeroed by the caller)
+  unsigned long long *out;  // [0] += sum t, [1] += sum C(t,2), [2] += sum C(t,2) (d(u) + d(v) - 6)
+};
+struct ChouseParams {
+  int nv;
+  long long ne;
+  const int *rp, *col;
+  int *scratch;  // max_deg ints per wave of the launch
+  int max_deg;
+  unsigned long long *out;
+};
+hipError_t launch_wtri(const MineParams &p, const WtriParams &wp, int stage, int grid_blocks, hipStream_t stream);
+int wtri_per_cu(int stage);
+hipError_t launch_wtri_edges(const WtriEdgeParams &p, const WtriParams &wp, int cu_count, hipStream_t stream);
+hipError_t launch_wtri_degrees(int nv, long long ne, const int *rp, const int *col, int *deg, int cu_count, hipStream_t stream);
+hipError_t launch_wtri_entries(const WtriEntryParams &p, int cu_count, hipStream_t stream);
+hipError_t launch_wtri_vertices(int nv, const unsigned long long *tv2, const int *deg, unsigned long long *out, int cu_count, hipStream_t stream);  // out[3] += H, out[4] += S
+hipError_t launch_path5(int nv, const int *rp, const int *col, unsigned long long *out, int cu_count, hipStream_t stream);
+int chouse_grid(long long ne, int cu_count);
+hipError_t launch_chouse(const ChouseParams &p, int grid_blocks, hipStream_t stream);
 size_t mine_lds_bytes(Pattern pat);
 // the big-LDS classes (gm_mine_wide.hip): cls = 1 (mid rows) or 2 (big rows); DIAMOND, MOTIF3, MOTIF4E only
 hipError_t launch_mine_wide(Pattern pat, int cls, const MineParams &p, int grid_blocks, hipStream_t stream);

@@ -86,6 +86,12 @@ class Pattern {
   bool is_tailedtriangle() const { return name_ == "tailedtriangle"; }  // include/pattern.hh:64-66
   bool is_4path() const { return name_ == "4path"; }
   bool is_3star() const { return name_ == "3star"; }
+  bool is_5path() const { return name_ == "5path"; }  // include/pattern.hh:69-78
+  bool is_semihouse() const { return name_ == "semihouse"; }
+  bool is_closedhouse() const { return name_ == "closedhouse"; }
+  bool is_hourglass() const { return name_ == "hourglass"; }
+  bool is_taileddiamond() const { return name_ == "taileddiamond"; }
+  bool is_taileddiamond2() const { return name_ == "taileddiamond2"; }
   const std::string &get_name() const { return name_; }
 
  private:

@@ -132,6 +132,15 @@ bool sgl4(const Job &j) {
          (!std::strcmp(j.pattern, "tailedtriangle") || !std::strcmp(j.pattern, "4path") || !std::strcmp(j.pattern, "3star"));
 }
 
+// the six 5-vertex closed forms (gm_sgl5_raw / gm_sgl5_finish): one GPU only -- their halvings and products need the whole graph's sums
+bool sgl5(const Job &j) {
+  static const char *const names[] = {"hourglass", "taileddiamond", "taileddiamond2", "closedhouse", "semihouse", "5path"};
+  if (j.kind != Job::SGL || !j.pattern) return false;
+  for (const char *n : names)
+    if (!std::strcmp(j.pattern, n)) return true;
+  return false;
+}
+
 int call(const Job &j, gm_graph *g, const gm_launch *la, uint64_t *out, gm_stats *st) {
   switch (j.kind) {
     case Job::TC: return gm_tc(g, la, out, st);
@@ -338,7 +347,7 @@ bool run(const gm_csr &g, Job j, int n_gpu, int chunk, uint64_t *out) {
   }
   // gm_dev_option("GM_FORCE_RCCL_PATH", "1") drives the multi-GPU code (broadcast + all-reduce) even with one device,
   // so the RCCL path is exercised on a single-GPU test box.
-  if (n_gpu <= 1 && !opt_set("GM_FORCE_RCCL_PATH")) return run_single(g, j, chunk, out);
+  if ((n_gpu <= 1 && !opt_set("GM_FORCE_RCCL_PATH")) || sgl5(j)) return run_single(g, j, chunk, out);  // (sgl5: the one-GPU path at every n_gpu)
   if (n_gpu < 1) n_gpu = 1;
   j.name = "multigpu";
   return run_multi(g, j, n_gpu, chunk, out);

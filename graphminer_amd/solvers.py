@@ -115,6 +115,27 @@ def sgl4_finish(pattern: str, raw) -> int:
     return int(total.value)
 
 
+# ---- the six 5-vertex patterns as closed forms of eleven raw sums (include/graphminer_amd.h: gm_sgl5_*) ----------------------------------------
+SGL5_PATTERNS = ("hourglass", "taileddiamond", "taileddiamond2", "closedhouse", "semihouse", "5path")
+SGL5_RAW = ("T", "D", "W", "A", "B", "H", "S", "P", "K4", "R", "Q")
+
+
+def sgl5_raw(g: DeviceGraph, pattern: str = "all", *, chunk=0, return_stats=False, **kw):
+    """the raw sums `pattern` (one of SGL5_PATTERNS, or "all") needs, in the order of SGL5_RAW; the others are 0.  One GPU."""
+    la, st, raw = _launch(0, 1, chunk, **kw), gm_stats(), (C.c_uint64 * len(SGL5_RAW))()
+    _lib.check(_lib.load().gm_sgl5_raw(g.handle, pattern.encode(), C.byref(la), raw, C.byref(st)), "gm_sgl5_raw")
+    res = [int(x) for x in raw]
+    return (res, _stats(st)) if return_stats else res
+
+
+def sgl5_finish(pattern: str, raw) -> int:
+    """the eleven raw sums (mod 2**64) -> the count of `pattern`; host-only"""
+    total = C.c_uint64(0)
+    arr = (C.c_uint64 * len(SGL5_RAW))(*[int(x) & (2**64 - 1) for x in raw])
+    _lib.check(_lib.load().gm_sgl5_finish(pattern.encode(), arr, C.byref(total)), "gm_sgl5_finish")
+    return int(total.value)
+
+
 # ---- diamond on several ranks with the one-GPU algorithm (include/graphminer_amd.h: gm_diamond_support_*) ------------------------------
 def diamond_support_size(g: DeviceGraph, world: int = 1) -> int:
     """uint32 entries of a rank's support array: |E+| of the oriented copy, padded so that every rank's reduce-scatter slice is equal"""

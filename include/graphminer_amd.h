@@ -221,8 +221,10 @@ int gm_tc_core_info(const gm_graph *dag, int64_t info[4]);
  * (include/pattern.hh:62-78). Implemented: "diamond" (src/sgl/cpu_kernels/diamond.h:1-14,
  * src/sgl/gpu_kernels/diamond_count.cuh:3-21), "rectangle" (rectangle.h:1-11), "house" (house.h:1-16),
  * "pentagon" (pentagon.h:2-17), and -- one rank (several: gm_sgl4_partial), from the per-edge sums of the formula 4-motif, no enumeration of their own --
- * "tailedtriangle" (tailedtriangle.h:1-12), "4path" (4path.h:1-14), "3star" (3star.h:1-13).  Others (the 5- and 6-vertex patterns of
- * src/sgl/omp_base.cc:33-49 beyond house / pentagon) -> GM_ERR_UNSUPPORTED, *total = 0.
+ * "tailedtriangle" (tailedtriangle.h:1-12), "4path" (4path.h:1-14), "3star" (3star.h:1-13), and -- one rank, no d_counts: gm_sgl5_raw
+ * followed by gm_sgl5_finish, closed forms over edge supports, triangles and degrees -- "5path", "semihouse", "closedhouse", "hourglass",
+ * "taileddiamond", "taileddiamond2" (src/sgl/cpu_kernels/ of the same names).  Others ("6path", "dumbbell", src/sgl/omp_base.cc:46-49)
+ * -> GM_ERR_UNSUPPORTED, *total = 0.
  * With world > 1 a rank's house / pentagon value is a partial MODULO 2^64 (a centre's positive and negative terms may be tasks of different
  * ranks): add the ranks' values as uint64 (an all-reduce does), do not compare a single rank's value with anything.
  * rectangle / house keep the counter maps of their heavy centres in LDS (gm_mine.hip rect_lds_kernel / house_lds_kernel; tune[6] & GM_T6_GLOBAL_MAPS:
@@ -239,6 +241,22 @@ int gm_sgl(const gm_graph *sym, const char *pattern, const gm_launch *launch, ui
  * then gm_sgl4_finish(pattern, raw, &total) applies the pattern's closed form.  gm_sgl itself refuses world > 1 for these three. */
 int gm_sgl4_partial(const gm_graph *sym, const gm_launch *launch, uint64_t raw[4], gm_stats *stats);
 int gm_sgl4_finish(const char *pattern, const uint64_t raw[4], uint64_t *total);
+
+/* The six 5-vertex patterns (hourglass, taileddiamond, taileddiamond2, semihouse, closedhouse, 5path) as closed forms of eleven raw sums
+ * (DESIGN.md "SgL, 5-vertex closed forms"; t(e) = edge support, x = t - 1, d = degree, T_v = triangles at v, uint64 modulo 2^64):
+ *   raw[0] T = triangles          raw[1] D = sum_e C(t,2)               raw[2] W = sum_e C(t,2) (d(u) + d(v) - 6)
+ *   raw[3] A = sum_tri [x(bc)(d(a)-2) + x(ac)(d(b)-2) + x(ab)(d(c)-2)]   raw[4] B = sum_tri [x(ab)x(ac) + x(ab)x(bc) + x(ac)x(bc)]
+ *   raw[5] H = sum_v C(T_v,2)     raw[6] S = sum_v T_v d(v)             raw[7] P = sum_v (e1(v)^2 - p2(v)) / 2
+ *   raw[8] K4 = 4-cliques         raw[9] R = the rectangle count        raw[10] Q = sum_e (t - 2) sum_{c in S_e} |S_e ^ N(c)|
+ *   hourglass = H - 2 D, taileddiamond2 = W, taileddiamond = A - 12 K4, semihouse = B - 12 K4, closedhouse = Q, 5path = P - 2 S + 9 T - 4 R.
+ * gm_sgl5_raw fills the sums `pattern` needs (one of the six names, or "all") and sets the others to 0; T .. S come from the supports of the
+ * oriented copy and one more pass over its triangles (csrc/gm_wtri.hip), K4 and R from gm_clique / gm_sgl("rectangle"), P and Q from one
+ * kernel each on the symmetric graph.  stats->kernel_ms covers every kernel of the call, stats->tasks = the graph's directed entries.
+ * One GPU, synchronous: world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED (the closed forms are applied on the host), a handle of
+ * >= 2^31 entries -> GM_ERR_TOO_LARGE, any other name -> GM_ERR_INVALID.  gm_sgl5_finish is host-only (no device). */
+#define GM_SGL5_NRAW 11
+int gm_sgl5_raw(const gm_graph *sym, const char *pattern, const gm_launch *launch, uint64_t raw[GM_SGL5_NRAW], gm_stats *stats);
+int gm_sgl5_finish(const char *pattern, const uint64_t raw[GM_SGL5_NRAW], uint64_t *total);
 
 /* Diamond on SEVERAL ranks with the one-GPU algorithm (one shared pass over the triangles of the oriented copy; the reference has no
  * multi-GPU diamond: src/sgl/multigpu.cu:117 is commented out).  Per step, on every rank:
