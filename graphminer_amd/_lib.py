@@ -62,6 +62,7 @@ class gm_setup_times(C.Structure):
 
 GM_OK, GM_ERR_INVALID, GM_ERR_NO_DEVICE, GM_ERR_HIP, GM_ERR_TOO_LARGE, GM_ERR_UNSUPPORTED, GM_ERR_IO, GM_ERR_FORMAT = range(8)
 GM_PART_ROUND_ROBIN, GM_PART_RANGE, GM_PART_VERTEX = 0, 1, 2
+GM_TRUSS_REMOVED = 0xFFFFFFFF
 (GM_OP_INTERSECT_NUM, GM_OP_INTERSECT_NUM_UPPER, GM_OP_INTERSECT_SET, GM_OP_DIFFERENCE_NUM,
  GM_OP_DIFFERENCE_NUM_UPPER, GM_OP_DIFFERENCE_SET, GM_OP_INTERSECT_SET_UPPER, GM_OP_DIFFERENCE_SET_UPPER, GM_OP_COUNT_SMALLER) = range(9)
 
@@ -96,6 +97,9 @@ SYMBOLS = [
     ("gm_sgl4_finish", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("gm_sgl5_raw", C.c_int, [_P, C.c_char_p, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
     ("gm_sgl5_finish", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("gm_tc_local", C.c_int, [_P, C.POINTER(gm_launch), _P, _P, C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
+    ("gm_ktruss", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), _P, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(gm_stats)]),
+    ("gm_truss_decompose", C.c_int, [_P, C.POINTER(gm_launch), _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(gm_stats)]),
     ("gm_motif_formula", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.c_int, C.POINTER(gm_stats)]),
     ("gm_setop_batch", C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("gm_rmat_keys", C.c_int, [C.c_int, C.c_int64, C.c_uint64, _P, _P]),

@@ -1,11 +1,12 @@
 // gm_cli.cc -- one source for the whole command-line surface of the HIP solvers.
 //
-// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
+// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
 //   tc_gpu_base tc_multigpu tc_multigpu_base | sgl_gpu_base sgl_multigpu | clique_gpu_base clique_multigpu kcl_gpu_base |
-//   motif_gpu_base motif_multigpu
+//   motif_gpu_base motif_multigpu | truss_gpu_base
 // The observable behaviour -- positional argv, defaults, usage text, banner and FINAL result lines -- is that of the
 // reference mains (src/triangle/main.cc:7-27, src/sgl/main.cc:9-35, src/clique/main.cc:8-28, src/motif/main.cc:9-31,
-// Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.
+// Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.  truss_gpu_base <graph prefix> [k] has no
+// counterpart there: the same loader, argv checks and exit codes, last line `ktruss_edges = N` (with k) or `max_truss = K` (without).
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -18,8 +19,12 @@
 #define GM_SGL 2
 #define GM_CLIQUE 3
 #define GM_MOTIF 4
+#define GM_TRUSS 5
+#if defined(GM_APP) && GM_APP == GM_TRUSS
+#include <hip/hip_runtime_api.h>
+#endif
 #ifndef GM_APP
-#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF"
+#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS"
 #endif
 
 namespace {
@@ -32,6 +37,7 @@ struct Cli {
   int adj_sorted = 1;  // [adj_sorted(1)] (tc only)
 };
 
+#if GM_APP != GM_TRUSS
 // positional layout: TC has no <second>; the others do
 Cli parse(int argc, char **argv, bool has_second) {
   Cli c;
@@ -46,6 +52,7 @@ Cli parse(int argc, char **argv, bool has_second) {
 #endif
   return c;
 }
+#endif
 
 void usage_and_exit(const char *self) {
 #if GM_APP == GM_TC
@@ -54,6 +61,9 @@ void usage_and_exit(const char *self) {
 #elif GM_APP == GM_SGL
   std::fprintf(stderr, "usage: %s <graph prefix> <pattern> [num_gpu(1)] [chunk_size(1024)]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph rectangle\n", self);
+#elif GM_APP == GM_TRUSS
+  std::printf("Usage: %s <graph prefix> [k]\n", self);
+  std::printf("Example: %s /graph_inputs/mico/graph 4\n", self);
 #else
   std::printf("Usage: %s<graph> <k> [ngpu(0)] [chunk_size(1024)]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4\n", self);
@@ -86,9 +96,15 @@ static int strip_dev_options(int argc, char **argv) {
 
 int main(int argc, char **argv) {
   argc = strip_dev_options(argc, argv);
-  const bool has_second = (GM_APP != GM_TC);
+  const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS);
   if (argc < (has_second ? 3 : 2)) usage_and_exit(argv[0]);
+#if GM_APP == GM_TRUSS
+  Cli c;
+  c.graph = argv[1];
+  if (argc > 2) c.second = argv[2];  // [k]
+#else
   const Cli c = parse(argc, argv, has_second);
+#endif
 
 #if GM_APP == GM_TC
   std::printf("Triangle Counting: we assume the neighbor lists are sorted.\n");
@@ -126,6 +142,35 @@ int main(int argc, char **argv) {
 #else
   std::printf("num_%d-cliques = %llu\n", k, (unsigned long long)total);
 #endif
+
+#elif GM_APP == GM_TRUSS
+  std::printf("k-truss (undirected graph only)\n");
+  std::fflush(stdout);
+  Graph g(c.graph);
+  g.print_meta_data();
+  const gm_csr csr = g.csr();
+  gm_graph *h = nullptr;
+  int rc = gm_graph_upload(&csr, 0, &h);
+  uint64_t n_edges = 0;
+  int32_t k_max = 0, rounds = 0;
+  const bool with_k = !c.second.empty();
+  const int k = with_k ? std::atoi(c.second.c_str()) : 0;
+  uint32_t *d_tau = nullptr;
+  if (rc == GM_OK && with_k) rc = gm_ktruss(h, k, nullptr, nullptr, &n_edges, &rounds, nullptr);
+  if (rc == GM_OK && !with_k) {
+    // (the trussness array is the call's result and the caller's buffer)
+    if (hipMalloc(reinterpret_cast<void **>(&d_tau), sizeof(uint32_t) * (size_t)(csr.ne > 0 ? csr.ne : 1)) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK) rc = gm_truss_decompose(h, nullptr, d_tau, &k_max, &rounds, nullptr);
+    if (d_tau) (void)hipFree(d_tau);
+  }
+  gm_graph_free(h);
+  if (rc != GM_OK) {
+    std::fprintf(stderr, "%s: %s %s\n", argv[0], gm_strerror(rc), gm_last_error());
+    return 1;
+  }
+  std::printf("rounds = %d\n", (int)rounds);
+  if (with_k) std::printf("ktruss_edges = %llu\n", (unsigned long long)n_edges);
+  else std::printf("max_truss = %d\n", (int)k_max);
 
 #elif GM_APP == GM_MOTIF
   Graph g(c.graph);

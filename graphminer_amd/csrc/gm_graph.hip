@@ -197,7 +197,7 @@ extern "C" const char *gm_strerror(int s) {
   }
 }
 extern "C" const char *gm_last_error(void) { return g_last_error.c_str(); }
-extern "C" int gm_version(void) { return 100; }
+extern "C" int gm_version(void) { return 101; }
 
 extern "C" int gm_device_count(int *n) {
   if (!n) return GM_ERR_INVALID;
@@ -263,6 +263,9 @@ extern "C" void gm_graph_free(gm_graph *g) {
   if (g->d_sup) dev_free(g->d_sup);
   for (void *q : {(void *)g->d_w5sup, (void *)g->d_w5ed, (void *)g->d_w5deg, (void *)g->d_w5tv2, (void *)g->d_w5out})
     if (q) dev_free(q);
+  for (void *q : {(void *)g->d_newid, (void *)g->d_lsup, (void *)g->d_lent, (void *)g->d_lrev, (void *)g->d_lmark, (void *)g->d_lfront, (void *)g->d_ltruss,
+                  (void *)g->d_lcnt})
+    if (q) dev_free(q);
   free_clique_plans(g);
   if (g->d_wide_mat) dev_free(g->d_wide_mat);
   if (g->d_wide_sorted) dev_free(g->d_wide_sorted);
@@ -317,6 +320,7 @@ int finish_handle(gm_graph *g) {
     gm_touch_tch();
     gm_touch_sup();
     gm_touch_wtri();
+    gm_touch_local();
     gm_touch_cbuild();
     gm_touch_cmma();
     gm_touch_cgather();
@@ -1249,7 +1253,7 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
   DevBuf<int> dupflag;
   HIP_TRY(dupflag.alloc(1));
   HIP_TRY(hipMemsetAsync(dupflag.p, 0, sizeof(int), 0));
-  HIP_TRY(newid.alloc(nv1));
+  HIP_TRY(newid.alloc(nv1, mode == 2));  // (the topological copy keeps it: the local counts map the caller's ids through it)
   HIP_TRY(newdeg.alloc(nv1));
   HIP_TRY(vkeys.alloc(nv1));
   HIP_TRY(vsorted.alloc(nv1));
@@ -1357,6 +1361,7 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
       return GM_OK;
     }
   }
+  if (mode == 2) r->d_newid = newid.release();
   std::lock_guard<std::mutex> lk(g->mu);
   g->relabel_cache[mode] = r;
   g->setup.relabel_ms += timer.ms();

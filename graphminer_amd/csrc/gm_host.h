@@ -316,6 +316,19 @@ struct gm_graph {
   int *d_w5deg = nullptr;
   unsigned long long *d_w5tv2 = nullptr, *d_w5out = nullptr;
   bool w5_tri = false, w5_vert = false;  // what the PAT_WTRI launch in flight was asked for (gm_sgl5_raw)
+  // local counts and the k-truss (gm_local.hip, gm_tc_local / gm_ktruss / gm_truss_decompose).  A renumbered copy remembers its numbering;
+  // the DAG the triangle pass runs on has a support array of the local counts' own (d_sup and d_w5sup are not touched); the SYMMETRIC
+  // handle holds what lives in the caller's entry order: the supports / peeling state, the reverse-entry index (built once), the marks,
+  // the frontier list, the trussness, and the counters of a round
+  int *d_newid = nullptr;       // the topological copy made by get_relabeled (mode 2): id in the graph it was made from -> id here (nv)
+  unsigned *d_lsup = nullptr;   // per DAG entry (diamond_support_entries)
+  unsigned *d_lent = nullptr;   // per entry of the symmetric graph: the support of its edge; while peeling, exact at the canonical entries
+  int *d_lrev = nullptr;        // per entry (u, v): the entry (v, u)
+  bool lrev_ready = false;
+  unsigned char *d_lmark = nullptr;
+  int *d_lfront = nullptr;      // ne / 2 + 1 canonical entries
+  unsigned *d_ltruss = nullptr;
+  unsigned *d_lcnt = nullptr;   // 64 bytes: [0] frontier size, [1] 0xFFFFFFFF - smallest alive support
   // ... and the MATCH MASKS of the in-edge tasks with long tails (ensure_sup_masks, gm_tables.hip): per DAG entry / per task the offset of
   // the task's mask in the arena (64-bit words; kNoMask: the task keeps its atomics), the arena itself (written and read by every launch)
   unsigned *d_emoff = nullptr, *d_tmoff = nullptr;
@@ -535,6 +548,7 @@ void gm_touch_hrow();
 void gm_touch_tch();
 void gm_touch_sup();
 void gm_touch_wtri();
+void gm_touch_local();
 void gm_touch_cbuild();
 void gm_touch_cmma();
 void gm_touch_cgather();

@@ -627,6 +627,41 @@ hipError_t launch_wtri_vertices(int nv, const unsigned long long *tv2, const int
 hipError_t launch_path5(int nv, const int *rp, const int *col, unsigned long long *out, int cu_count, hipStream_t stream);
 int chouse_grid(long long ne, int cu_count);
 hipError_t launch_chouse(const ChouseParams &p, int grid_blocks, hipStream_t stream);
+// local counts and the k-truss (gm_local.hip): the supports of the oriented copy back at the caller's entries, the triangles per vertex, and
+// the peeling rounds on the symmetric graph
+struct LocalMapParams {
+  int nv;
+  long long ne;
+  const int *rp, *col;        // the caller's symmetric CSR
+  const int *newid;           // caller's id -> id of the DAG the supports were counted on (nullptr: the same ids)
+  const int *drp, *dcol;      // that DAG
+  const unsigned *dsup;       // its supports, one per entry
+  int topo;                   // every DAG edge goes to a larger id: the edge sits in the row of its smaller end
+  unsigned *out;              // per caller's entry: the support of its edge
+  unsigned long long *sum;    // [0] += the sum of out[] (6 T)
+};
+constexpr int kLocalShortRow = 32;  // local_vertex_kernel: a row of more entries is summed by the whole wave
+enum LocalMark : unsigned char { LM_ALIVE = 0, LM_FRONTIER = 1, LM_REMOVED = 2 };
+struct LocalPeelParams {
+  int nv;
+  long long ne;
+  const int *rp, *col;
+  const int *rev;             // per entry (u, v): the entry (v, u); its own index for a self loop
+  unsigned *sup;              // per undirected edge, at its CANONICAL entry min(e, rev[e]) (the row of the smaller end): alive triangles
+  unsigned char *mark;        // LocalMark of the edge, at the canonical entry
+  int *front;                 // the canonical entries of this round's frontier
+  unsigned *cnt;              // [0] frontier size, [1] 0xFFFFFFFF - smallest support of an alive edge outside the frontier (0: none)
+  unsigned *truss;            // nullptr, or per canonical entry: `level` is written when the edge enters the frontier
+  unsigned thr, level;        // an alive edge of support < thr enters the frontier
+};
+hipError_t launch_local_map(const LocalMapParams &p, int cu_count, hipStream_t stream);
+hipError_t launch_local_vertices(int nv, const int *rp, const unsigned *sup, unsigned long long *tv, int cu_count, hipStream_t stream);
+hipError_t launch_local_rev(int nv, long long ne, const int *rp, const int *col, int *rev, int cu_count, hipStream_t stream);
+hipError_t launch_local_peel_init(long long ne, const int *rev, unsigned char *mark, int cu_count, hipStream_t stream);
+hipError_t launch_local_mark(const LocalPeelParams &p, int cu_count, hipStream_t stream);
+hipError_t launch_local_peel(const LocalPeelParams &p, unsigned n_front, int cu_count, hipStream_t stream);
+// out[e] (may be nullptr): truss ? truss[canonical] : the edge's support or GM_TRUSS_REMOVED; sum[0] += alive edges
+hipError_t launch_local_truss_out(const LocalPeelParams &p, unsigned *out, unsigned long long *sum, int cu_count, hipStream_t stream);
 size_t mine_lds_bytes(Pattern pat);
 // the big-LDS classes (gm_mine_wide.hip): cls = 1 (mid rows) or 2 (big rows); DIAMOND, MOTIF3, MOTIF4E only
 hipError_t launch_mine_wide(Pattern pat, int cls, const MineParams &p, int grid_blocks, hipStream_t stream);

@@ -158,3 +158,55 @@ def diamond_support_finish(g: DeviceGraph, d_support: int, count: int, *, return
     _lib.check(_lib.load().gm_diamond_support_finish(g.handle, C.byref(la), d_support, count, None if la.d_counts else C.byref(total), C.byref(st)),
                "gm_diamond_support_finish")
     return (int(total.value), _stats(st)) if return_stats else int(total.value)
+
+
+# ---- local counts and the k-truss (include/graphminer_amd.h: gm_tc_local / gm_ktruss / gm_truss_decompose) -----------------------------
+TRUSS_REMOVED = _lib.GM_TRUSS_REMOVED
+
+
+def _dev_array(g: DeviceGraph, n: int, dtype):
+    """a device buffer of n elements on the graph's GPU: a torch tensor (uint32 / uint64 travel as int32 / int64 of the same bytes)"""
+    import torch
+
+    return torch.empty(max(int(n), 1), dtype=dtype, device=torch.device("cuda", g.device))
+
+
+def _to_numpy(t, n: int, dtype):
+    return t[:n].cpu().numpy().view(dtype)
+
+
+def tc_local(g: DeviceGraph, *, vertex=True, entries=True, chunk=0, return_stats=False, **kw):
+    """(total, T_v as np.uint64[nv] or None, edge supports as np.uint32[ne] or None) of a SYMMETRIC graph, in the caller's numbering and
+    entry order: T_v the triangles at v, the support of entry (u, v) = |N(u) ^ N(v)|.  One GPU."""
+    import torch
+
+    la, st, total = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0)
+    tv = _dev_array(g, g.nv, torch.int64) if vertex else None
+    sup = _dev_array(g, g.ne, torch.int32) if entries else None
+    _lib.check(_lib.load().gm_tc_local(g.handle, C.byref(la), tv.data_ptr() if vertex else None, sup.data_ptr() if entries else None,
+                                       C.byref(total), C.byref(st)), "gm_tc_local")
+    res = (int(total.value), _to_numpy(tv, g.nv, "uint64") if vertex else None, _to_numpy(sup, g.ne, "uint32") if entries else None)
+    return (*res, _stats(st)) if return_stats else res
+
+
+def ktruss(g: DeviceGraph, k: int, *, chunk=0, return_stats=False, **kw):
+    """(undirected edges of the k-truss, per entry its edge's support inside the truss or TRUSS_REMOVED as np.uint32[ne], peeling rounds)"""
+    import torch
+
+    la, st, n, rounds = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0), C.c_int32(0)
+    sup = _dev_array(g, g.ne, torch.int32)
+    _lib.check(_lib.load().gm_ktruss(g.handle, int(k), C.byref(la), sup.data_ptr(), C.byref(n), C.byref(rounds), C.byref(st)), "gm_ktruss")
+    res = (int(n.value), _to_numpy(sup, g.ne, "uint32"), int(rounds.value))
+    return (*res, _stats(st)) if return_stats else res
+
+
+def truss_decompose(g: DeviceGraph, *, chunk=0, return_stats=False, **kw):
+    """(trussness of every entry's edge as np.uint32[ne], the largest of them, peeling rounds)"""
+    import torch
+
+    la, st, kmax, rounds = _launch(0, 1, chunk, **kw), gm_stats(), C.c_int32(0), C.c_int32(0)
+    tau = _dev_array(g, g.ne, torch.int32)
+    _lib.check(_lib.load().gm_truss_decompose(g.handle, C.byref(la), tau.data_ptr(), C.byref(kmax), C.byref(rounds), C.byref(st)),
+               "gm_truss_decompose")
+    res = (_to_numpy(tau, g.ne, "uint32"), int(kmax.value), int(rounds.value))
+    return (*res, _stats(st)) if return_stats else res

@@ -284,6 +284,37 @@ int gm_diamond_support_partial(const gm_graph *sym, const gm_launch *launch, uin
 int gm_diamond_support_finish(const gm_graph *sym, const gm_launch *launch, const uint32_t *d_support, int64_t count, uint64_t *total,
                               gm_stats *stats);
 
+/* ---- local counts and the k-truss (csrc/gm_local.hip; DESIGN.md "Local counts and k-truss") ----------------------------------------
+ * What a caller asks of a triangle counter after the total: the triangles at every vertex and the support |N(u) ^ N(v)| of every edge, in
+ * the CALLER's numbering and entry order -- and their first consumer, the k-truss.  The supports come from the one pass over the triangles
+ * of the oriented copy that the one-GPU diamond takes (every path of it; launch->tune[6] is honoured), into an array of these calls' own:
+ * the calls work before or after any other solver on the handle and leave the diamond's and the 5-vertex forms' arrays alone.
+ * SYMMETRIC graph, one GPU, synchronous: a null handle -> GM_ERR_INVALID, a handle of >= 2^31 entries -> GM_ERR_TOO_LARGE, world > 1 or
+ * launch->d_counts -> GM_ERR_UNSUPPORTED, unsorted rows -> GM_ERR_INVALID as in every solver, ne == 0 -> GM_OK with zeros.
+ * ONE of these calls at a time per handle: the supports, the peeling state and the reverse-entry index live on the handle (as the other
+ * solvers' per-handle arrays do); different handles may be used from different threads.
+ * stats->kernel_ms covers every kernel of the call (a k-truss: also the host's one read-back per round), stats->tasks = the directed entries.
+ *
+ * gm_tc_local -- the CALLER's numbering and entry order:
+ *   d_vertex_tri: DEVICE uint64[nv] or NULL -- T_v, the triangles at v (half the sum of the supports of row v).
+ *   d_entry_sup:  DEVICE uint32[ne] or NULL -- for entry i = (u, v) of row u: |N(u) ^ N(v)|; the two directions of an edge are equal.
+ *   total (may be NULL): the triangle count, sum_v T_v / 3. */
+int gm_tc_local(const gm_graph *sym, const gm_launch *launch, uint64_t *d_vertex_tri, uint32_t *d_entry_sup, uint64_t *total, gm_stats *stats);
+
+#define GM_TRUSS_REMOVED 0xFFFFFFFFu
+/* k-truss, k >= 2 (k < 2 -> GM_ERR_INVALID): the largest edge set in which every edge lies in >= k - 2 triangles OF THAT SET.
+ *   d_entry_sup (DEVICE uint32[ne] or NULL): the support of the entry's edge inside the k-truss, GM_TRUSS_REMOVED for an edge outside it
+ *   (both directions of every edge are written).  n_edges: undirected edges of the k-truss.  rounds (may be NULL): peeling rounds run.
+ * A round marks the alive edges of support < k - 2 as the frontier, counts them (the one word the host reads per round), and one wave per
+ * frontier edge takes the edge's triangles from the supports of their surviving edges; the frontier is removed after the round.  The round
+ * that finds an empty frontier ends the call and counts: rounds >= 1 on a graph with edges. */
+int gm_ktruss(const gm_graph *sym, int k, const gm_launch *launch, uint32_t *d_entry_sup, uint64_t *n_edges, int32_t *rounds, gm_stats *stats);
+/* trussness of every edge: tau(e) = the largest k whose k-truss holds e (>= 2).  d_entry_truss: DEVICE uint32[ne] (NULL -> GM_ERR_INVALID).
+ * k_max = max tau (0 for a graph without edges).  rounds as above, over all levels: the same rounds with k rising from 3 -- an edge
+ * removed while the threshold is k - 2 gets tau = k - 1 -- and from a level whose frontier is empty k goes straight to the smallest alive
+ * support + 3, the first level that removes an edge. */
+int gm_truss_decompose(const gm_graph *sym, const gm_launch *launch, uint32_t *d_entry_truss, int32_t *k_max, int32_t *rounds, gm_stats *stats);
+
 #define GM_MAX_CLIQUE_K 12
 /* CliqueSolver on the DAG, 3 <= k <= GM_MAX_CLIQUE_K (src/clique/cpu_kernels/automine_omp.h:67-83,138-157;
  * src/clique/gpu_kernels/clique4_warp_edge.cuh:3-31 ... clique8; k = 9..12: the same levels once more, as the reference's generic
