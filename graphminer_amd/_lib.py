@@ -97,6 +97,10 @@ SYMBOLS = [
     ("gm_sgl4_finish", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("gm_sgl5_raw", C.c_int, [_P, C.c_char_p, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
     ("gm_sgl5_finish", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("gm_sgl6_need", C.c_int, [C.c_char_p, C.POINTER(C.c_uint32)]),
+    ("gm_sgl6_raw", C.c_int, [_P, C.c_uint32, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
+    ("gm_sgl6_finish", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("gm_sgl6", C.c_int, [_P, C.c_char_p, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
     ("gm_tc_local", C.c_int, [_P, C.POINTER(gm_launch), _P, _P, C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
     ("gm_ktruss", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), _P, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(gm_stats)]),
     ("gm_truss_decompose", C.c_int, [_P, C.POINTER(gm_launch), _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(gm_stats)]),

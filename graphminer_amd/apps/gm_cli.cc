@@ -1,12 +1,14 @@
 // gm_cli.cc -- one source for the whole command-line surface of the HIP solvers.
 //
-// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
+// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
 //   tc_gpu_base tc_multigpu tc_multigpu_base | sgl_gpu_base sgl_multigpu | clique_gpu_base clique_multigpu kcl_gpu_base |
-//   motif_gpu_base motif_multigpu | truss_gpu_base
+//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base
 // The observable behaviour -- positional argv, defaults, usage text, banner and FINAL result lines -- is that of the
 // reference mains (src/triangle/main.cc:7-27, src/sgl/main.cc:9-35, src/clique/main.cc:8-28, src/motif/main.cc:9-31,
 // Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.  truss_gpu_base <graph prefix> [k] has no
 // counterpart there: the same loader, argv checks and exit codes, last line `ktruss_edges = N` (with k) or `max_truss = K` (without).
+// sgl6_gpu_base <graph prefix> <6path|dumbbell> counts the two 6-vertex patterns sgl_gpu_base answers "Not implemented" for (gm_sgl6): the
+// banner and the last line `total_num = N` are sgl_gpu_base's.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -20,11 +22,12 @@
 #define GM_CLIQUE 3
 #define GM_MOTIF 4
 #define GM_TRUSS 5
+#define GM_SGL6 6
 #if defined(GM_APP) && GM_APP == GM_TRUSS
 #include <hip/hip_runtime_api.h>
 #endif
 #ifndef GM_APP
-#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS"
+#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6"
 #endif
 
 namespace {
@@ -61,6 +64,9 @@ void usage_and_exit(const char *self) {
 #elif GM_APP == GM_SGL
   std::fprintf(stderr, "usage: %s <graph prefix> <pattern> [num_gpu(1)] [chunk_size(1024)]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph rectangle\n", self);
+#elif GM_APP == GM_SGL6
+  std::fprintf(stderr, "usage: %s <graph prefix> <6path|dumbbell>\n", self);
+  std::printf("Example: %s /graph_inputs/mico/graph 6path\n", self);
 #elif GM_APP == GM_TRUSS
   std::printf("Usage: %s <graph prefix> [k]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4\n", self);
@@ -171,6 +177,24 @@ int main(int argc, char **argv) {
   std::printf("rounds = %d\n", (int)rounds);
   if (with_k) std::printf("ktruss_edges = %llu\n", (unsigned long long)n_edges);
   else std::printf("max_truss = %d\n", (int)k_max);
+
+#elif GM_APP == GM_SGL6
+  std::printf("Subgraph Listing/Counting (undirected graph only)\n");
+  std::printf("Pattern: %s\n", c.second.c_str());
+  std::fflush(stdout);
+  Graph g(c.graph);
+  g.print_meta_data();
+  const gm_csr csr = g.csr();
+  gm_graph *h = nullptr;
+  int rc = gm_graph_upload(&csr, 0, &h);
+  uint64_t total = 0;
+  if (rc == GM_OK) rc = gm_sgl6(h, c.second.c_str(), nullptr, &total, nullptr);
+  gm_graph_free(h);
+  if (rc != GM_OK) {
+    std::fprintf(stderr, "%s: %s %s\n", argv[0], gm_strerror(rc), gm_last_error());
+    return 1;
+  }
+  std::printf("total_num = %llu\n", (unsigned long long)total);
 
 #elif GM_APP == GM_MOTIF
   Graph g(c.graph);

@@ -263,6 +263,8 @@ extern "C" void gm_graph_free(gm_graph *g) {
   if (g->d_sup) dev_free(g->d_sup);
   for (void *q : {(void *)g->d_w5sup, (void *)g->d_w5ed, (void *)g->d_w5deg, (void *)g->d_w5tv2, (void *)g->d_w5out})
     if (q) dev_free(q);
+  for (void *q : {(void *)g->d_s6e1, (void *)g->d_wrect_mask, (void *)g->d_wrect_tasks})
+    if (q) dev_free(q);
   for (void *q : {(void *)g->d_newid, (void *)g->d_lsup, (void *)g->d_lent, (void *)g->d_lrev, (void *)g->d_lmark, (void *)g->d_lfront, (void *)g->d_ltruss,
                   (void *)g->d_lcnt})
     if (q) dev_free(q);
@@ -320,6 +322,7 @@ int finish_handle(gm_graph *g) {
     gm_touch_tch();
     gm_touch_sup();
     gm_touch_wtri();
+    gm_touch_wrect();
     gm_touch_local();
     gm_touch_cbuild();
     gm_touch_cmma();

@@ -316,6 +316,15 @@ struct gm_graph {
   int *d_w5deg = nullptr;
   unsigned long long *d_w5tv2 = nullptr, *d_w5out = nullptr;
   bool w5_tri = false, w5_vert = false;  // what the PAT_WTRI launch in flight was asked for (gm_sgl5_raw)
+  // the 6-vertex closed forms (gm_wrect.hip, gm_sgl6_raw).  On the DAG of the 5-vertex pass: e1 per vertex.  On the graph the weighted
+  // 4-cycle kernel walks (the copy numbered ascending in degree, or the handle itself): its plan, built once -- ids per range
+  // (GM_WRECT_RANGE), ranges per bit of the row masks, the masks, the task list
+  unsigned *d_s6e1 = nullptr;
+  unsigned long long *d_wrect_mask = nullptr;
+  int2 *d_wrect_tasks = nullptr;
+  unsigned long long n_wrect_tasks = 0;
+  int wrect_range = 0, wrect_grp = 1;
+  bool wrect_ready = false;
   // local counts and the k-truss (gm_local.hip, gm_tc_local / gm_ktruss / gm_truss_decompose).  A renumbered copy remembers its numbering;
   // the DAG the triangle pass runs on has a support array of the local counts' own (d_sup and d_w5sup are not touched); the SYMMETRIC
   // handle holds what lives in the caller's entry order: the supports / peeling state, the reverse-entry index (built once), the marks,
@@ -548,6 +557,7 @@ void gm_touch_hrow();
 void gm_touch_tch();
 void gm_touch_sup();
 void gm_touch_wtri();
+void gm_touch_wrect();
 void gm_touch_local();
 void gm_touch_cbuild();
 void gm_touch_cmma();

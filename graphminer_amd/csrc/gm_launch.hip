@@ -1,5 +1,5 @@
 // gm_launch.hip -- the solvers of the C ABI: launch prologue / epilogue, the dequeue words, run_pattern (TC, edge supports, diamond, 3-motif, k-clique,
-// the per-edge sums of 4-motif) as a driver over plan_pattern / fill_mine_params / prepare_scratch / launch_*, the SgL launches, gm_tc / gm_sgl / gm_clique / gm_motif*.
+// the per-edge sums of 4-motif) as a driver over plan_pattern / fill_mine_params / prepare_scratch / launch_*, the SgL launches, gm_tc / gm_sgl / gm_sgl5_* / gm_sgl6_* / gm_clique / gm_motif*.
 // Reference launch logic: src/triangle/gpu_base.cu:36-45, src/sgl/gpu_base.cu:37-75, src/clique/gpu_base.cu:28-50, src/motif/gpu_base.cu:42-75.
 #include "gm_host.h"
 
@@ -2007,10 +2007,9 @@ static int run_sym_sum(const gm_graph *sym, const gm_launch *la, uint64_t *out, 
   return GM_OK;
 }
 
-extern "C" int gm_sgl5_raw(const gm_graph *sym, const char *pattern, const gm_launch *la, uint64_t raw[GM_SGL5_NRAW], gm_stats *st) {
-  if (!sym || !pattern || !raw) return GM_ERR_INVALID;
-  const unsigned needs = strcmp(pattern, "all") == 0 ? (1u << GM_SGL5_NRAW) - 1u : sgl5_needs(pattern);
-  if (!needs) return GM_ERR_INVALID;
+// the raw sums of the bit mask `needs` (gm_sgl5_raw: those of a pattern; gm_sgl6_raw: D, B, K4, or T for the arrays of the pass alone)
+static int sgl5_raw_needs(const gm_graph *sym, unsigned needs, const gm_launch *la, uint64_t raw[GM_SGL5_NRAW], gm_stats *st) {
+  if (!sym || !raw || !needs) return GM_ERR_INVALID;
   for (int i = 0; i < GM_SGL5_NRAW; ++i) raw[i] = 0;
   if (int rc0 = reject_big(sym)) return rc0;
   // the divisions and halvings need the sums of the whole graph, and the total is put together on the host: one rank, synchronous
@@ -2079,6 +2078,11 @@ extern "C" int gm_sgl5_raw(const gm_graph *sym, const char *pattern, const gm_la
   g->ring_extra[0] = g->ring_extra[1] = nullptr;
   if (st) st->kernel_ms = ms;
   return GM_OK;
+}
+
+extern "C" int gm_sgl5_raw(const gm_graph *sym, const char *pattern, const gm_launch *la, uint64_t raw[GM_SGL5_NRAW], gm_stats *st) {
+  if (!sym || !pattern || !raw) return GM_ERR_INVALID;
+  return sgl5_raw_needs(sym, strcmp(pattern, "all") == 0 ? (1u << GM_SGL5_NRAW) - 1u : sgl5_needs(pattern), la, raw, st);
 }
 
 // ---- local counts and the k-truss (gm_local.hip; DESIGN.md "Local counts and k-truss") ----------------------------------------------------
@@ -2330,6 +2334,189 @@ extern "C" int gm_sgl(const gm_graph *sym, const char *pattern, const gm_launch 
   }
   if (total) *total = 0;  // "Not implemented", total_num = 0 (src/sgl/omp_base.cc:51-53): 6path, dumbbell
   return GM_ERR_UNSUPPORTED;
+}
+
+// ---- 6path and dumbbell (src/sgl/omp_base.cc:46-50) as closed forms of nine raw sums (DESIGN.md "SgL, 6-vertex closed forms") ---------------
+//   6path = X - Y - 2 Z + 12 R + 4 D - 5 C5,   dumbbell = M - B + 6 K4
+// behind entry points of their own: gm_sgl above keeps answering GM_ERR_UNSUPPORTED for the two names (tests/test_gpu_sgl5.py pins that);
+// routing it here is a later one-line change.
+enum Sgl6Raw : int { R6_X = 0, R6_Y, R6_Z, R6_R, R6_D, R6_C5, R6_M, R6_B, R6_K4 };
+static_assert(R6_K4 + 1 == GM_SGL6_NRAW, "the order of the raw sums is ABI");
+static unsigned sgl6_needs(const char *pattern) {
+  if (!pattern) return 0u;
+  auto b = [](int i) { return 1u << i; };
+  if (strcmp(pattern, "6path") == 0) return b(R6_X) | b(R6_Y) | b(R6_Z) | b(R6_R) | b(R6_D) | b(R6_C5);
+  if (strcmp(pattern, "dumbbell") == 0) return b(R6_M) | b(R6_B) | b(R6_K4);
+  return 0u;
+}
+
+extern "C" int gm_sgl6_need(const char *pattern, uint32_t *mask) {
+  if (!pattern || !mask) return GM_ERR_INVALID;
+  *mask = strcmp(pattern, "all") == 0 ? (1u << GM_SGL6_NRAW) - 1u : sgl6_needs(pattern);
+  return *mask ? GM_OK : GM_ERR_INVALID;
+}
+
+extern "C" int gm_sgl6_finish(const char *pattern, const uint64_t raw[GM_SGL6_NRAW], uint64_t *total) {
+  if (!sgl6_needs(pattern) || !raw || !total) return GM_ERR_INVALID;
+  if (strcmp(pattern, "6path") == 0) *total = raw[R6_X] - raw[R6_Y] - 2ull * raw[R6_Z] + 12ull * raw[R6_R] + 4ull * raw[R6_D] - 5ull * raw[R6_C5];
+  else *total = raw[R6_M] - raw[R6_B] + 6ull * raw[R6_K4];
+  return GM_OK;
+}
+
+// Z and R (out[0], out[1]) by wrect_kernel on the copy numbered ascending in degree (tune[6] & GM_T6_AS_NUMBERED: on the graph as given).  The plan
+// is built once per graph that runs it: GM_WRECT_RANGE (ids per LDS range, default and limit kWrectRange) is read then.
+static int run_wrect(const gm_graph *sym, const gm_launch *la_in, uint64_t out[2], gm_stats *st) {
+  gm_graph *self = const_cast<gm_graph *>(sym);
+  const gm_graph *run_on = sym;
+  if (!(la_in && (la_in->tune[6] & GM_T6_AS_NUMBERED))) {
+    gm_graph *r = nullptr;
+    if (int rc = get_relabeled(self, 0, &r)) return rc;
+    run_on = r;
+  }
+  uint64_t v[4] = {0, 0, 0, 0};
+  LaunchCtx ctx;
+  if (int rc = begin_launch(run_on, la_in, v, ctx)) return rc;
+  gm_graph *g = ctx.g;
+  const GraphView gv = graph_view(g);
+  if (int rc = ensure_idx0(g, gv)) return rc;
+  if (std::lock_guard<std::mutex> lk(g->mu); !g->wrect_ready) {  // (two first calls on one handle: one builds, the other waits)
+    OtherSetupScope scope(g);
+    const size_t nv = (size_t)g->nv;
+    int range = kWrectRange;
+    if (const char *e = gm_opt("GM_WRECT_RANGE")) range = std::max(16, std::min(kWrectRange, std::atoi(e)));
+    const long long nranges = std::max<long long>(1, ((long long)g->nv + range - 1) / range);
+    g->wrect_range = range;
+    g->wrect_grp = (int)((nranges + 63) / 64);
+    HIP_TRY(dev_malloc(&g->d_wrect_mask, sizeof(unsigned long long) * std::max<size_t>(nv, 1)));
+    HIP_TRY(launch_wrect_mask(g->nv, g->d_rp, g->d_col, range, g->wrect_grp, g->d_wrect_mask, g->cu_count, 0));
+    std::vector<int> idx0h(std::max<size_t>(nv, 1));
+    if (nv) HIP_TRY(hipMemcpy(idx0h.data(), g->d_idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
+    // the centres with more neighbours below them than the workgroup has threads first, a task per range (hubs are the last ids of the
+    // default numbering: from the last id down, every centre's top range first), then one task per remaining centre that can hold a 4-cycle
+    constexpr int per_wg = kWrectThreads;
+    std::vector<int2> tasks;
+    for (long long v0 = (long long)nv - 1; v0 >= 0; --v0)
+      if (idx0h[(size_t)v0] > per_wg)
+        for (int k = (int)((v0 - 1) / range); k >= 0; --k) tasks.push_back(make_int2((int)v0, k));
+    for (long long v0 = (long long)nv - 1; v0 >= 0; --v0)
+      if (idx0h[(size_t)v0] >= 2 && idx0h[(size_t)v0] <= per_wg) tasks.push_back(make_int2((int)v0, -1));
+    g->n_wrect_tasks = tasks.size();
+    HIP_TRY(dev_malloc(&g->d_wrect_tasks, sizeof(int2) * std::max<size_t>(tasks.size(), 1)));
+    if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_wrect_tasks, tasks.data(), sizeof(int2) * tasks.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    g->wrect_ready = true;
+  }
+  WrectParams p;
+  memset(&p, 0, sizeof p);
+  p.rp = g->d_rp; p.col = g->d_col; p.idx0 = g->d_idx0;
+  p.rmask = g->d_wrect_mask; p.range = g->wrect_range; p.grp = g->wrect_grp;
+  p.tasks = g->d_wrect_tasks; p.count = g->n_wrect_tasks;
+  p.queue = queue_word64(g, QW64_MAIN);
+  p.counters = g->d_counters;
+  if (int rc = start_timer(ctx)) return rc;
+  const int grid = grid_for((long long)p.count, g->cu_count, wrect_per_cu());
+  if (p.count > 0) HIP_TRY(launch_wrect(p, grid, ctx.stream));
+  fill_stats(st, (uint64_t)g->ne, (uint64_t)p.count, grid, kWrectThreads);
+  const int rc = end_launch(ctx, FIN_RAW4, 0, v, 4, st);
+  out[0] = v[0];
+  out[1] = v[1];
+  self->ring_alias = (run_on != sym) ? run_on : nullptr;
+  return rc;
+}
+
+extern "C" int gm_sgl6_raw(const gm_graph *sym, uint32_t need, const gm_launch *la, uint64_t raw[GM_SGL6_NRAW], gm_stats *st) {
+  if (!sym || !raw || !need || (need >> GM_SGL6_NRAW)) return GM_ERR_INVALID;
+  for (int i = 0; i < GM_SGL6_NRAW; ++i) raw[i] = 0;
+  if (int rc0 = reject_big(sym)) return rc0;
+  if (la && (la->world > 1 || la->d_counts)) return GM_ERR_UNSUPPORTED;  // (the closed forms are applied on the host: one rank, synchronous)
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2;
+  memset(&l2, 0, sizeof l2);
+  if (la) l2 = *la;
+  auto want = [&](int i) { return (need >> i & 1u) != 0; };
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  HIP_TRY(hipSetDevice(g->device));
+  {  // unsorted rows are refused as in every solver (begin_launch's check and text, before any of the sub-launches builds a table)
+    bool sorted = false;
+    if (int rc = graph_rows_sorted(g, &sorted)) return rc;
+    if (!sorted) {
+      g_last_error = "the neighbour lists of this graph are not strictly ascending: call gm_graph_sort_neighbors first (Graph::sort_neighbors, adj_sorted = 0)";
+      return GM_ERR_INVALID;
+    }
+  }
+  if (sym->ne == 0) return GM_OK;
+  double ms = 0.0;
+  gm_stats s;
+  const bool entry_sums = want(R6_X) || want(R6_Y) || want(R6_M);
+  if (entry_sums || want(R6_D) || want(R6_B) || want(R6_K4)) {
+    // D, B and K4 are sums of the 5-vertex forms; X, M and Y read the arrays their pass leaves on the DAG it ran on -- the supports of the
+    // entries, 2 T_v, the symmetric degrees -- so the pass runs for them too (T asks for nothing but the pass itself)
+    unsigned n5 = (want(R6_D) ? 1u << R5_D : 0u) | (want(R6_B) ? 1u << R5_B : 0u) | (want(R6_K4) ? 1u << R5_K4 : 0u);
+    if (entry_sums && !(n5 & ((1u << R5_D) | (1u << R5_B)))) n5 |= 1u << R5_T;
+    uint64_t raw5[GM_SGL5_NRAW];
+    memset(&s, 0, sizeof s);
+    if (int rc = sgl5_raw_needs(sym, n5, &l2, raw5, &s)) return rc;
+    ms += s.kernel_ms;
+    raw[R6_D] = want(R6_D) ? raw5[R5_D] : 0;
+    raw[R6_B] = want(R6_B) ? raw5[R5_B] : 0;
+    raw[R6_K4] = want(R6_K4) ? raw5[R5_K4] : 0;
+  }
+  if (entry_sums) {
+    gm_graph *run_on = nullptr;
+    if (int rc = diamond_run_on(sym, &l2, &run_on)) return rc;  // (the handle the pass above ran on)
+    if (!run_on->d_w5sup || !run_on->d_w5tv2 || !run_on->d_w5deg) return GM_ERR_INVALID;
+    {
+      std::lock_guard<std::mutex> lk(run_on->mu);
+      if (!run_on->d_s6e1) HIP_TRY(dev_malloc(&run_on->d_s6e1, sizeof(unsigned) * (size_t)std::max(run_on->nv, 1)));
+    }
+    uint64_t v[4] = {0, 0, 0, 0};
+    LaunchCtx ctx;
+    if (int rc = begin_launch(run_on, &l2, v, ctx)) return rc;
+    HIP_TRY(hipMemsetAsync(run_on->d_s6e1, 0, sizeof(unsigned) * (size_t)std::max(run_on->nv, 1), ctx.stream));
+    if (int rc = start_timer(ctx)) return rc;
+    Sgl6EntryParams ep;
+    memset(&ep, 0, sizeof ep);
+    ep.nv = run_on->nv; ep.ne = run_on->ne; ep.rp = run_on->d_rp; ep.col = run_on->d_col;
+    ep.sup = run_on->d_w5sup; ep.deg = run_on->d_w5deg; ep.tv2 = run_on->d_w5tv2; ep.e1 = run_on->d_s6e1; ep.out = run_on->d_counters;
+    HIP_TRY(launch_sgl6_sums(ep, run_on->cu_count, ctx.stream));
+    memset(&s, 0, sizeof s);
+    if (int rc = end_launch(ctx, FIN_RAW4, 0, v, 4, &s)) return rc;
+    ms += s.kernel_ms;
+    raw[R6_X] = want(R6_X) ? v[0] : 0;
+    raw[R6_M] = want(R6_M) ? v[1] : 0;
+    raw[R6_Y] = want(R6_Y) ? v[2] : 0;
+  }
+  if (want(R6_Z)) {  // (the kernel of Z counts R on the way: the rectangle path is only asked when Z is not)
+    uint64_t zr[2] = {0, 0};
+    memset(&s, 0, sizeof s);
+    if (int rc = run_wrect(sym, &l2, zr, &s)) return rc;
+    ms += s.kernel_ms;
+    raw[R6_Z] = zr[0];
+    raw[R6_R] = want(R6_R) ? zr[1] : 0;
+  } else if (want(R6_R)) {
+    memset(&s, 0, sizeof s);
+    if (int rc = gm_sgl(sym, "rectangle", &l2, &raw[R6_R], &s)) return rc;
+    ms += s.kernel_ms;
+  }
+  if (want(R6_C5)) {
+    memset(&s, 0, sizeof s);
+    if (int rc = gm_sgl(sym, "pentagon", &l2, &raw[R6_C5], &s)) return rc;
+    ms += s.kernel_ms;
+  }
+  g->ring_alias = nullptr;
+  g->ring_extra[0] = g->ring_extra[1] = nullptr;
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  if (st) st->kernel_ms = ms;
+  return GM_OK;
+}
+
+extern "C" int gm_sgl6(const gm_graph *sym, const char *pattern, const gm_launch *la, uint64_t *total, gm_stats *st) {
+  if (total) *total = 0;
+  const unsigned need = sgl6_needs(pattern);
+  if (!sym || !total || !need) return GM_ERR_INVALID;
+  uint64_t raw[GM_SGL6_NRAW];
+  const int rc = gm_sgl6_raw(sym, need, la, raw, st);
+  return rc ? rc : gm_sgl6_finish(pattern, raw, total);
 }
 
 extern "C" int gm_clique(const gm_graph *dag, int k, const gm_launch *la, uint64_t *total, gm_stats *st) {

@@ -9,7 +9,7 @@
 // else's main must not change what it runs on an ambient variable).  What tests need to reach a path on a small graph, and the documented
 // fallbacks, are named options set through the C ABI -- gm_dev_option(name, value), include/graphminer_amd.h -- and read with gm_opt():
 //   GM_DIAMOND_PER_EDGE, GM_SUP_STREAM / GM_SUP_NO_MASKS / GM_SUP_MASK_MIN (edge supports), GM_TC_CORE_H / GM_SUP_CORE_H (hub corner),
-//   GM_BIG_NE, GM_KST_MAX_KEYS, GM_TOPO_MIN_ROW, GM_WIDE_ARENA_MB, GM_TCT_SPLIT_ALWAYS, GM_RECT_LDS_MIN / GM_RECT_LDS_RANGES (limits lowered for tests), GM_ORIENT_TWO_GATHERS,
+//   GM_BIG_NE, GM_KST_MAX_KEYS, GM_TOPO_MIN_ROW, GM_WIDE_ARENA_MB, GM_TCT_SPLIT_ALWAYS, GM_RECT_LDS_MIN / GM_RECT_LDS_RANGES / GM_WRECT_RANGE (limits lowered for tests), GM_ORIENT_TWO_GATHERS,
 //   GM_RELABEL_GLOBAL_SORT (the previous setup paths, compared in tests), GM_NO_TEMP_POOL, and the n-GPU runner's GM_FORCE_RCCL_PATH /
 //   GM_DIAMOND_SUPPORTS_MAX_WORLD (host/multi.cc).  Only GM_SETUP_TRACE (setup steps on stderr: diagnostics, no algorithm) is an
 //   environment variable.  In -DGM_DEVEL builds (make DEVEL=1) an option that is not set falls back to the environment, and the
@@ -627,6 +627,35 @@ hipError_t launch_wtri_vertices(int nv, const unsigned long long *tv2, const int
 hipError_t launch_path5(int nv, const int *rp, const int *col, unsigned long long *out, int cu_count, hipStream_t stream);
 int chouse_grid(long long ne, int cu_count);
 hipError_t launch_chouse(const ChouseParams &p, int grid_blocks, hipStream_t stream);
+// the 6-vertex closed forms (gm_wrect.hip): the degree-weighted 4-cycle sum with its counters in LDS one range of ids at a time, and the
+// per-entry / per-vertex sums X, M, Y over the arrays of the 5-vertex pass
+constexpr int kWrectRange = 4096;  // ids of one LDS range: a 32-bit and a 64-bit counter each (48 KB of the workgroup's 52.3 KB)
+constexpr int kWrectWaves = 4;
+constexpr int kWrectThreads = kWrectWaves * 64;  // (waves of 64) a centre with at most this many neighbours below it is ONE task (a row per thread): the plan and the kernel share it
+struct WrectParams {
+  const int *rp, *col;
+  const int *idx0;                  // per vertex: its neighbours below it
+  const unsigned long long *rmask;  // per vertex: bit j = the row has a key in the ranges [j grp, (j + 1) grp)
+  int range, grp;                   // ids per range (<= kWrectRange); ranges per bit of rmask
+  const int2 *tasks;                // {centre, range} or {centre, -1} = every range of a centre of at most 256 neighbours below it
+  unsigned long long count;
+  unsigned long long *queue;
+  unsigned long long *counters;     // [0] += Z, [1] += R
+};
+struct Sgl6EntryParams {
+  int nv;
+  long long ne;
+  const int *rp, *col;              // the oriented copy
+  const unsigned *sup;              // per entry: its support
+  const int *deg;                   // per vertex: symmetric degree
+  const unsigned long long *tv2;    // per vertex: twice its triangles
+  unsigned *e1;                     // per vertex: sum of d(a) - 1 over its neighbours (zeroed by the caller)
+  unsigned long long *out;          // [0] += X, [1] += M, [2] += Y
+};
+int wrect_per_cu();
+hipError_t launch_wrect(const WrectParams &p, int grid_blocks, hipStream_t stream);
+hipError_t launch_wrect_mask(int nv, const int *rp, const int *col, int range, int grp, unsigned long long *rmask, int cu_count, hipStream_t stream);
+hipError_t launch_sgl6_sums(const Sgl6EntryParams &p, int cu_count, hipStream_t stream);
 // local counts and the k-truss (gm_local.hip): the supports of the oriented copy back at the caller's entries, the triangles per vertex, and
 // the peeling rounds on the symmetric graph
 struct LocalMapParams {

@@ -136,6 +136,46 @@ def sgl5_finish(pattern: str, raw) -> int:
     return int(total.value)
 
 
+# ---- 6path and dumbbell as closed forms of nine raw sums (include/graphminer_amd.h: gm_sgl6_*) ---------------------------------------------
+SGL6_PATTERNS = ("6path", "dumbbell")
+SGL6_RAW = ("X", "Y", "Z", "R", "D", "C5", "M", "B", "K4")
+
+
+def sgl6_need(pattern: str) -> int:
+    """the raw sums `pattern` (one of SGL6_PATTERNS, or "all") needs, as a bit mask over SGL6_RAW; host-only"""
+    mask = C.c_uint32(0)
+    _lib.check(_lib.load().gm_sgl6_need(pattern.encode(), C.byref(mask)), "gm_sgl6_need")
+    return int(mask.value)
+
+
+def sgl6_raw(g: DeviceGraph, need="all", *, chunk=0, return_stats=False, **kw):
+    """the raw sums of `need` -- a pattern name, "all", an iterable of names of SGL6_RAW, or a bit mask -- in the order of SGL6_RAW; the
+    others are 0.  One GPU."""
+    if isinstance(need, str):
+        need = sgl6_need(need)
+    elif not isinstance(need, int):
+        need = sum(1 << SGL6_RAW.index(k) for k in set(need))
+    la, st, raw = _launch(0, 1, chunk, **kw), gm_stats(), (C.c_uint64 * len(SGL6_RAW))()
+    _lib.check(_lib.load().gm_sgl6_raw(g.handle, need, C.byref(la), raw, C.byref(st)), "gm_sgl6_raw")
+    res = [int(x) for x in raw]
+    return (res, _stats(st)) if return_stats else res
+
+
+def sgl6_finish(pattern: str, raw) -> int:
+    """the nine raw sums (mod 2**64) -> the count of `pattern`; host-only"""
+    total = C.c_uint64(0)
+    arr = (C.c_uint64 * len(SGL6_RAW))(*[int(x) & (2**64 - 1) for x in raw])
+    _lib.check(_lib.load().gm_sgl6_finish(pattern.encode(), arr, C.byref(total)), "gm_sgl6_finish")
+    return int(total.value)
+
+
+def sgl6(g: DeviceGraph, pattern: str, *, chunk=0, return_stats=False, **kw):
+    """the count of "6path" or "dumbbell" on the SYMMETRIC graph (SglSolver keeps answering "Not implemented" for the two names).  One GPU."""
+    la, st, total = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0)
+    _lib.check(_lib.load().gm_sgl6(g.handle, pattern.encode(), C.byref(la), C.byref(total), C.byref(st)), "gm_sgl6")
+    return (int(total.value), _stats(st)) if return_stats else int(total.value)
+
+
 # ---- diamond on several ranks with the one-GPU algorithm (include/graphminer_amd.h: gm_diamond_support_*) ------------------------------
 def diamond_support_size(g: DeviceGraph, world: int = 1) -> int:
     """uint32 entries of a rank's support array: |E+| of the oriented copy, padded so that every rank's reduce-scatter slice is equal"""

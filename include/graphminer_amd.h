@@ -224,7 +224,8 @@ int gm_tc_core_info(const gm_graph *dag, int64_t info[4]);
  * "tailedtriangle" (tailedtriangle.h:1-12), "4path" (4path.h:1-14), "3star" (3star.h:1-13), and -- one rank, no d_counts: gm_sgl5_raw
  * followed by gm_sgl5_finish, closed forms over edge supports, triangles and degrees -- "5path", "semihouse", "closedhouse", "hourglass",
  * "taileddiamond", "taileddiamond2" (src/sgl/cpu_kernels/ of the same names).  Others ("6path", "dumbbell", src/sgl/omp_base.cc:46-49)
- * -> GM_ERR_UNSUPPORTED, *total = 0.
+ * -> GM_ERR_UNSUPPORTED, *total = 0: "6path" and "dumbbell" are counted by gm_sgl6 below, behind entry points of their own -- an existing
+ * test pins this call's answer for the two names, and routing them to gm_sgl6 is a later one-line change that goes with that test.
  * With world > 1 a rank's house / pentagon value is a partial MODULO 2^64 (a centre's positive and negative terms may be tasks of different
  * ranks): add the ranks' values as uint64 (an all-reduce does), do not compare a single rank's value with anything.
  * rectangle / house keep the counter maps of their heavy centres in LDS (gm_mine.hip rect_lds_kernel / house_lds_kernel; tune[6] & GM_T6_GLOBAL_MAPS:
@@ -257,6 +258,29 @@ int gm_sgl4_finish(const char *pattern, const uint64_t raw[4], uint64_t *total);
 #define GM_SGL5_NRAW 11
 int gm_sgl5_raw(const gm_graph *sym, const char *pattern, const gm_launch *launch, uint64_t raw[GM_SGL5_NRAW], gm_stats *stats);
 int gm_sgl5_finish(const char *pattern, const uint64_t raw[GM_SGL5_NRAW], uint64_t *total);
+
+/* The two 6-vertex patterns of the reference's dispatcher (src/sgl/omp_base.cc:46-50; cpu_kernels/6path.h, dumbbell.h) as closed forms of
+ * nine raw sums (DESIGN.md "SgL, 6-vertex closed forms"; e1(v) = sum_{a in N(v)} (d(a) - 1), R_v = 4-cycles through v, the rest as above):
+ *   raw[0] X = sum_{u,v} s(u,v) s(v,u) over the undirected edges, s(u,v) = e1(u) - (d(v) - 1) - t(e)     raw[1] Y = sum_v T_v (d(v) - 2)^2
+ *   raw[2] Z = sum_v d(v) R_v = sum over the 4-cycles of the degrees of their four vertices               raw[3] R = the rectangle count
+ *   raw[4] D = sum_e C(t,2)      raw[5] C5 = the pentagon count      raw[6] M = sum_{u,v} (T_u - t(e)) (T_v - t(e)) over the undirected edges
+ *   raw[7] B = sum_tri [x(ab)x(ac) + x(ab)x(bc) + x(ac)x(bc)]         raw[8] K4 = 4-cliques
+ *   6path = X - Y - 2 Z + 12 R + 4 D - 5 C5,   dumbbell = M - B + 6 K4.
+ * gm_sgl6_need (host-only): bit i of *mask = raw[i] is needed by `pattern` ("6path", "dumbbell", or "all").  gm_sgl6_raw fills the sums of the
+ * bit mask `need` and writes the others as 0: Z by a kernel of its own on the copy numbered ascending in degree (csrc/gm_wrect.hip: the
+ * rectangle's pruned walk with two counters per 2-path end, in LDS one range of ids at a time; tune[6] & GM_T6_AS_NUMBERED: on the graph as
+ * numbered; gm_dev_option("GM_WRECT_RANGE", ..), read when a handle's plan is built: ids per range, at most 4096); R from that kernel when Z
+ * is asked too, else from gm_sgl("rectangle"); D, B, K4 as gm_sgl5_raw takes them; X, M, Y from the supports, triangles and degrees the
+ * 5-vertex pass leaves on the oriented copy; C5 from gm_sgl("pentagon").  gm_sgl6_finish (host-only) applies a closed form modulo 2^64;
+ * gm_sgl6 = need -> raw -> finish.  The contract of gm_sgl5_raw: SYMMETRIC graph, one GPU, synchronous -- world > 1 or launch->d_counts ->
+ * GM_ERR_UNSUPPORTED, a handle of >= 2^31 entries -> GM_ERR_TOO_LARGE, an unknown name, need == 0 or bits beyond GM_SGL6_NRAW ->
+ * GM_ERR_INVALID, unsorted rows -> GM_ERR_INVALID as in every solver, ne == 0 -> GM_OK with zeros.  stats->kernel_ms covers every kernel of
+ * the call, stats->tasks = the graph's directed entries.  The arrays of the diamond, the 5-vertex forms and the local counts stay usable. */
+#define GM_SGL6_NRAW 9
+int gm_sgl6_need(const char *pattern, uint32_t *mask);
+int gm_sgl6_raw(const gm_graph *sym, uint32_t need, const gm_launch *launch, uint64_t raw[GM_SGL6_NRAW], gm_stats *stats);
+int gm_sgl6_finish(const char *pattern, const uint64_t raw[GM_SGL6_NRAW], uint64_t *total);
+int gm_sgl6(const gm_graph *sym, const char *pattern, const gm_launch *launch, uint64_t *total, gm_stats *stats);
 
 /* Diamond on SEVERAL ranks with the one-GPU algorithm (one shared pass over the triangles of the oriented copy; the reference has no
  * multi-GPU diamond: src/sgl/multigpu.cu:117 is commented out).  Per step, on every rank:
