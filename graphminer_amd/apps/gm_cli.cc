@@ -1,15 +1,18 @@
 // gm_cli.cc -- one source for the whole command-line surface of the HIP solvers.
 //
-// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
+// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
 //   tc_gpu_base tc_multigpu tc_multigpu_base | sgl_gpu_base sgl_multigpu | clique_gpu_base clique_multigpu kcl_gpu_base |
-//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base
+//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base
 // The observable behaviour -- positional argv, defaults, usage text, banner and FINAL result lines -- is that of the
 // reference mains (src/triangle/main.cc:7-27, src/sgl/main.cc:9-35, src/clique/main.cc:8-28, src/motif/main.cc:9-31,
 // Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.  truss_gpu_base <graph prefix> [k] has no
 // counterpart there: the same loader, argv checks and exit codes, last line `ktruss_edges = N` (with k) or `max_truss = K` (without).
 // sgl6_gpu_base <graph prefix> <6path|dumbbell> counts the two 6-vertex patterns sgl_gpu_base answers "Not implemented" for (gm_sgl6): the
 // banner and the last line `total_num = N` are sgl_gpu_base's.
+// tclist_gpu_base <graph prefix> [out.bin [first [cap]]] lists the triangles (gm_tc_list): `total_num_triangles = N` in tc_gpu_base's
+// spelling, then `triangles_written = M`; with out.bin the M triples of the window go there as raw little-endian int32, a < b < c.
 #include <cstdio>
+#include <algorithm>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -23,11 +26,12 @@
 #define GM_MOTIF 4
 #define GM_TRUSS 5
 #define GM_SGL6 6
-#if defined(GM_APP) && GM_APP == GM_TRUSS
+#define GM_TCLIST 7
+#if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST)
 #include <hip/hip_runtime_api.h>
 #endif
 #ifndef GM_APP
-#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6"
+#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST"
 #endif
 
 namespace {
@@ -40,7 +44,7 @@ struct Cli {
   int adj_sorted = 1;  // [adj_sorted(1)] (tc only)
 };
 
-#if GM_APP != GM_TRUSS
+#if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST
 // positional layout: TC has no <second>; the others do
 Cli parse(int argc, char **argv, bool has_second) {
   Cli c;
@@ -70,6 +74,9 @@ void usage_and_exit(const char *self) {
 #elif GM_APP == GM_TRUSS
   std::printf("Usage: %s <graph prefix> [k]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4\n", self);
+#elif GM_APP == GM_TCLIST
+  std::printf("Usage: %s <graph prefix> [out.bin [first [cap]]]\n", self);
+  std::printf("Example: %s /graph_inputs/mico/graph triangles.bin 0 1000000\n", self);
 #else
   std::printf("Usage: %s<graph> <k> [ngpu(0)] [chunk_size(1024)]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4\n", self);
@@ -102,12 +109,12 @@ static int strip_dev_options(int argc, char **argv) {
 
 int main(int argc, char **argv) {
   argc = strip_dev_options(argc, argv);
-  const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS);
+  const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS && GM_APP != GM_TCLIST);
   if (argc < (has_second ? 3 : 2)) usage_and_exit(argv[0]);
-#if GM_APP == GM_TRUSS
+#if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST
   Cli c;
   c.graph = argv[1];
-  if (argc > 2) c.second = argv[2];  // [k]
+  if (argc > 2) c.second = argv[2];  // [k] / [out.bin]
 #else
   const Cli c = parse(argc, argv, has_second);
 #endif
@@ -177,6 +184,43 @@ int main(int argc, char **argv) {
   std::printf("rounds = %d\n", (int)rounds);
   if (with_k) std::printf("ktruss_edges = %llu\n", (unsigned long long)n_edges);
   else std::printf("max_truss = %d\n", (int)k_max);
+
+#elif GM_APP == GM_TCLIST
+  std::printf("Triangle Listing (undirected graph only)\n");
+  std::fflush(stdout);
+  Graph g(c.graph);
+  g.print_meta_data();
+  const gm_csr csr = g.csr();
+  const uint64_t first = argc > 3 ? std::strtoull(argv[3], nullptr, 10) : 0;
+  gm_graph *h = nullptr;
+  int rc = gm_graph_upload(&csr, 0, &h);
+  uint64_t total = 0, written = 0;
+  if (rc == GM_OK) rc = gm_tc_list(h, nullptr, 0, 0, nullptr, &total, nullptr, nullptr);  // (count only: sizes the buffer)
+  if (rc == GM_OK && !c.second.empty()) {
+    uint64_t cap = first < total ? total - first : 0;
+    if (argc > 4) cap = std::min<uint64_t>(cap, std::strtoull(argv[4], nullptr, 10));
+    std::vector<int32_t> tri((size_t)(3 * cap));
+    int32_t *d_tri = nullptr;
+    if (cap > 0 && hipMalloc(reinterpret_cast<void **>(&d_tri), sizeof(int32_t) * tri.size()) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && cap > 0) rc = gm_tc_list(h, nullptr, first, cap, d_tri, &total, &written, nullptr);
+    if (rc == GM_OK && written > 0 && hipMemcpy(tri.data(), d_tri, sizeof(int32_t) * 3 * (size_t)written, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = GM_ERR_HIP;
+    if (d_tri) (void)hipFree(d_tri);
+    if (rc == GM_OK) {  // (the hosts this runs on are little-endian: the ints go out as they lie in memory)
+      FILE *f = std::fopen(c.second.c_str(), "wb");
+      const size_t n = 3 * (size_t)written;
+      const bool ok = f && std::fwrite(tri.data(), sizeof(int32_t), n, f) == n;
+      if (f && std::fclose(f) != 0) rc = GM_ERR_IO;
+      if (!ok) rc = GM_ERR_IO;
+    }
+  }
+  gm_graph_free(h);
+  if (rc != GM_OK) {
+    std::fprintf(stderr, "%s: %s %s\n", argv[0], gm_strerror(rc), gm_last_error());
+    return 1;
+  }
+  std::printf("total_num_triangles = %llu\n", (unsigned long long)total);
+  std::printf("triangles_written = %llu\n", (unsigned long long)written);
 
 #elif GM_APP == GM_SGL6
   std::printf("Subgraph Listing/Counting (undirected graph only)\n");

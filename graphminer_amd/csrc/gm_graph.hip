@@ -266,7 +266,7 @@ extern "C" void gm_graph_free(gm_graph *g) {
   for (void *q : {(void *)g->d_s6e1, (void *)g->d_wrect_mask, (void *)g->d_wrect_tasks})
     if (q) dev_free(q);
   for (void *q : {(void *)g->d_newid, (void *)g->d_lsup, (void *)g->d_lent, (void *)g->d_lrev, (void *)g->d_lmark, (void *)g->d_lfront, (void *)g->d_ltruss,
-                  (void *)g->d_lcnt})
+                  (void *)g->d_lcnt, (void *)g->d_list_off})
     if (q) dev_free(q);
   free_clique_plans(g);
   if (g->d_wide_mat) dev_free(g->d_wide_mat);
@@ -324,6 +324,7 @@ int finish_handle(gm_graph *g) {
     gm_touch_wtri();
     gm_touch_wrect();
     gm_touch_local();
+    gm_touch_list();
     gm_touch_cbuild();
     gm_touch_cmma();
     gm_touch_cgather();

@@ -338,6 +338,11 @@ struct gm_graph {
   int *d_lfront = nullptr;      // ne / 2 + 1 canonical entries
   unsigned *d_ltruss = nullptr;
   unsigned *d_lcnt = nullptr;   // 64 bytes: [0] frontier size, [1] 0xFFFFFFFF - smallest alive support
+  // triangle listing (gm_list.hip, gm_tc_list), on the SYMMETRIC handle: the first slot of every batch of 64 entries of the oriented copy
+  // (batches + 1 values, the last one T), counted and scanned by the first call and kept for the windows that follow
+  unsigned long long *d_list_off = nullptr;
+  unsigned long long list_total = 0;
+  bool list_ready = false;
   // ... and the MATCH MASKS of the in-edge tasks with long tails (ensure_sup_masks, gm_tables.hip): per DAG entry / per task the offset of
   // the task's mask in the arena (64-bit words; kNoMask: the task keeps its atomics), the arena itself (written and read by every launch)
   unsigned *d_emoff = nullptr, *d_tmoff = nullptr;
@@ -559,6 +564,7 @@ void gm_touch_sup();
 void gm_touch_wtri();
 void gm_touch_wrect();
 void gm_touch_local();
+void gm_touch_list();
 void gm_touch_cbuild();
 void gm_touch_cmma();
 void gm_touch_cgather();

@@ -2253,6 +2253,59 @@ extern "C" int gm_truss_decompose(const gm_graph *sym, const gm_launch *la, uint
   return run_truss(sym, true, 0, la, d_entry_truss, nullptr, k_max, rounds, st);
 }
 
+// ---- triangle listing (gm_list.hip; DESIGN.md "Triangle listing") -----------------------------------------------------------------------
+// On the oriented copy as numbered: it keeps the caller's ids, so a match is written as it is found.  The count stage runs once per handle
+// (the batches' first slots stay on the SYMMETRIC handle); a window is one fill launch that walks only the batches it meets.
+extern "C" int gm_tc_list(const gm_graph *sym, const gm_launch *la, uint64_t first, uint64_t cap, int32_t *d_tri, uint64_t *total,
+                          uint64_t *n_written, gm_stats *st) {
+  if (total) *total = 0;
+  if (n_written) *n_written = 0;
+  if (int rc = local_refusals(sym, la)) return rc;
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2;
+  memset(&l2, 0, sizeof l2);
+  if (la) l2 = *la;
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  uint64_t unused = 0;
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, &unused, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+  if (sym->ne == 0) return GM_OK;
+  if (const int rc_dag = ensure_dag_cache(g)) return rc_dag;  // (the oriented copy, cached on the handle)
+  const gm_graph *dag = g->dag_cache;
+  if (int rc = reject_big(dag)) return rc;
+  ListParams lp;
+  memset(&lp, 0, sizeof lp);
+  lp.nv = dag->nv; lp.ne = dag->ne; lp.rp = dag->d_rp; lp.col = dag->d_col;
+  if (int rc = start_timer(ctx)) return rc;
+  if (!g->list_ready) {  // (once per handle)
+    if (dag->ne > 0) {
+      const size_t nb = (size_t)((dag->ne + GM_WAVE - 1) / GM_WAVE);
+      {
+        std::lock_guard<std::mutex> lk(g->mu);
+        if (!g->d_list_off) HIP_TRY(dev_malloc(&g->d_list_off, sizeof(unsigned long long) * (nb + 1)));
+      }
+      lp.off = g->d_list_off;
+      HIP_TRY(list_count_scan(lp, g->cu_count, ctx.stream));
+      HIP_TRY(hipMemcpyAsync(&g->list_total, g->d_list_off + nb, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx.stream));
+      HIP_TRY(hipStreamSynchronize(ctx.stream));
+    }
+    g->list_ready = true;
+  }
+  const uint64_t T = g->list_total;
+  const uint64_t nw = (d_tri && first < T) ? std::min<uint64_t>(cap, T - first) : 0;
+  if (nw > 0) {
+    lp.off = g->d_list_off; lp.first = first; lp.nw = nw; lp.tri = d_tri;
+    HIP_TRY(launch_list_fill(lp, g->cu_count, ctx.stream));
+  }
+  gm_stats s;
+  memset(&s, 0, sizeof s);
+  if (int rc = end_launch(ctx, FIN_COPY, 0, &unused, 1, &s)) return rc;
+  if (total) *total = T;
+  if (n_written) *n_written = nw;
+  if (st) st->kernel_ms = s.kernel_ms;
+  return GM_OK;
+}
+
 extern "C" int gm_sgl(const gm_graph *sym, const char *pattern, const gm_launch *la, uint64_t *total, gm_stats *st) {
   if (!pattern) return GM_ERR_INVALID;
   if (strcmp(pattern, "diamond") == 0) {

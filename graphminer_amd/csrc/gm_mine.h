@@ -691,6 +691,18 @@ hipError_t launch_local_mark(const LocalPeelParams &p, int cu_count, hipStream_t
 hipError_t launch_local_peel(const LocalPeelParams &p, unsigned n_front, int cu_count, hipStream_t stream);
 // out[e] (may be nullptr): truss ? truss[canonical] : the edge's support or GM_TRUSS_REMOVED; sum[0] += alive edges
 hipError_t launch_local_truss_out(const LocalPeelParams &p, unsigned *out, unsigned long long *sum, int cu_count, hipStream_t stream);
+// triangle listing (gm_list.hip): the oriented copy is walked in batches of 64 consecutive entries, twice -- count, then fill
+constexpr int kListWholeWave = 64;  // a streamed list of this many keys or more is strided by the whole wave; shorter ones are flattened
+struct ListParams {
+  int nv;
+  long long ne;
+  const int *rp, *col;            // the oriented copy: it keeps the caller's ids
+  unsigned long long *off;        // per batch, + 1: the slot of its first match (the exclusive scan of the batches' counts; [batches] = T)
+  unsigned long long first, nw;   // fill: the window of slots [first, first + nw)
+  int *tri;                       // fill: 3 ints per slot of the window
+};
+hipError_t list_count_scan(const ListParams &p, int cu_count, hipStream_t stream);  // fills p.off; synchronises the stream
+hipError_t launch_list_fill(const ListParams &p, int cu_count, hipStream_t stream);
 size_t mine_lds_bytes(Pattern pat);
 // the big-LDS classes (gm_mine_wide.hip): cls = 1 (mid rows) or 2 (big rows); DIAMOND, MOTIF3, MOTIF4E only
 hipError_t launch_mine_wide(Pattern pat, int cls, const MineParams &p, int grid_blocks, hipStream_t stream);

@@ -174,4 +174,31 @@ __device__ __forceinline__ int wave_difference_set_upper(const int *A, int a, co
   return wave_difference_set(A, a, B, b, skip, out);
 }
 
+// ---- the row of a CSR entry (the local counts, the triangle listing: kernels that take 64 consecutive entries per wave) ----------------
+// largest u with rp[u] <= e: the row of entry e (rows may be empty)
+__device__ __forceinline__ int local_row_of(const int *__restrict__ rp, int nv, long long e) {
+  int lo = 0, hi = nv - 1;
+  while (lo < hi) {
+    const int mid = (int)(((long long)lo + hi + 1) >> 1);
+    if ((long long)rp[mid] <= e) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// the row of entry e when it is known to lie in [lo, hi]: largest u in [lo, hi] with rp[u] <= e
+__device__ __forceinline__ int local_row_in(const int *__restrict__ rp, int lo, int hi, long long e) {
+  while (lo < hi) {
+    const int mid = (int)(((long long)lo + hi + 1) >> 1);
+    if ((long long)rp[mid] <= e) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// The rows of the 64 consecutive entries base .. base + 63 of a wave: two wave-uniform bisections of the offsets bracket them (scalar loads,
+// once per wave), a lane then searches only the few rows between -- 64 entries span at most 64 non-empty rows, mostly one or two.
+__device__ __forceinline__ int local_wave_row(const int *__restrict__ rp, int nv, long long ne, long long base, long long e) {
+  const int lo = local_row_of(rp, nv, base), hi = local_row_of(rp, nv, min(base + GM_WAVE - 1, ne - 1));
+  return local_row_in(rp, lo, hi, min(e, ne - 1));
+}
+
 }  // namespace gm

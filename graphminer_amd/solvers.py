@@ -250,3 +250,27 @@ def truss_decompose(g: DeviceGraph, *, chunk=0, return_stats=False, **kw):
                "gm_truss_decompose")
     res = (_to_numpy(tau, g.ne, "uint32"), int(kmax.value), int(rounds.value))
     return (*res, _stats(st)) if return_stats else res
+
+
+# ---- triangle listing (include/graphminer_amd.h: gm_tc_list) ------------------------------------------------------------------------------
+def tc_list(g: DeviceGraph, *, first=0, cap=None, chunk=0, return_stats=False, **kw):
+    """(total, triangles as np.int32[n_written, 3]) of a SYMMETRIC graph: rows a < b < c in the caller's numbering, every triangle once, in
+    the handle's fixed listing order; the window is the `cap` triangles from index `first` (cap=None: all of them).  A count-only call sizes
+    the buffer, a second call fills it; the stats add the two up.  One GPU."""
+    import numpy as np
+    import torch
+
+    lib = _lib.load()
+    la, st, total, written = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0), C.c_uint64(0)
+    _lib.check(lib.gm_tc_list(g.handle, C.byref(la), 0, 0, None, C.byref(total), None, C.byref(st)), "gm_tc_list")
+    stats = _stats(st)
+    first = int(first)
+    n = max(int(total.value) - first, 0) if first >= 0 else 0
+    n = n if cap is None else min(n, int(cap))
+    tri = np.empty((0, 3), dtype=np.int32)
+    if n > 0:
+        buf = _dev_array(g, 3 * n, torch.int32)
+        _lib.check(lib.gm_tc_list(g.handle, C.byref(la), first, n, buf.data_ptr(), C.byref(total), C.byref(written), C.byref(st)), "gm_tc_list")
+        tri = _to_numpy(buf, 3 * int(written.value), "int32").reshape(-1, 3)
+        stats.kernel_ms += st.kernel_ms
+    return (int(total.value), tri, stats) if return_stats else (int(total.value), tri)

@@ -339,6 +339,25 @@ int gm_ktruss(const gm_graph *sym, int k, const gm_launch *launch, uint32_t *d_e
  * support + 3, the first level that removes an edge. */
 int gm_truss_decompose(const gm_graph *sym, const gm_launch *launch, uint32_t *d_entry_truss, int32_t *k_max, int32_t *rounds, gm_stats *stats);
 
+/* ---- triangle listing (csrc/gm_list.hip; DESIGN.md "Triangle listing") --------------------------------------------------------------
+ * Every triangle of a SYMMETRIC graph exactly once, as three ids of the CALLER's numbering, a < b < c, 12 bytes per triangle.
+ *   d_tri   DEVICE int32[3 * cap], or NULL (then cap is ignored: count only)
+ *   first   index of the first triangle wanted in the handle's listing order;  cap: at most this many are written
+ *   total   (may be NULL) T, the number of triangles of the graph -- always the whole count, whatever the window
+ *   n_written (may be NULL) min(cap, T - first), 0 when first >= T or d_tri == NULL
+ * The listing order is fixed for a handle: calls with windows [0,c), [c,2c), ... write, concatenated, exactly the sequence one call
+ * with first = 0, cap >= T writes.  Nothing is written beyond 3 * n_written ints.  The order: ascending entry (u, v) of the handle's
+ * oriented copy (gm_graph_orient's), then ascending position of the third vertex in the shorter of N+(u), N+(v) (N+(u) when equal).
+ * The first call on a handle counts the matches of every batch of 64 entries and scans them (kept on the handle); every call with a
+ * buffer then walks only the batches whose slots meet its window.  The call runs on the oriented copy as numbered -- it keeps the
+ * caller's ids -- so launch->tune[6] is ignored, GM_T6_AS_NUMBERED included: there is no renumbered copy to turn off.
+ * The contract of the local counts above: one GPU, synchronous; a null handle -> GM_ERR_INVALID, >= 2^31 entries -> GM_ERR_TOO_LARGE,
+ * world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED, unsorted rows -> GM_ERR_INVALID, ne == 0 -> GM_OK with zeros; launch->stream is
+ * honoured; stats->kernel_ms covers every kernel of the call, stats->tasks = the directed entries; before or after any other solver on
+ * the handle, whose arrays it leaves alone; ONE such call at a time per handle. */
+int gm_tc_list(const gm_graph *sym, const gm_launch *launch, uint64_t first, uint64_t cap, int32_t *d_tri, uint64_t *total,
+               uint64_t *n_written, gm_stats *stats);
+
 #define GM_MAX_CLIQUE_K 12
 /* CliqueSolver on the DAG, 3 <= k <= GM_MAX_CLIQUE_K (src/clique/cpu_kernels/automine_omp.h:67-83,138-157;
  * src/clique/gpu_kernels/clique4_warp_edge.cuh:3-31 ... clique8; k = 9..12: the same levels once more, as the reference's generic

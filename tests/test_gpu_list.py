@@ -1,0 +1,271 @@
+"""Triangle listing on the GPU (gm_tc_list, csrc/gm_list.hip): every triangle once, as a < b < c of the caller's numbering, against the plain
+numpy list of tests/list_ref.py; the windows of one handle tile its fixed order; the 64-lane tile, the flattened / whole-wave threshold,
+rows of more than 2048 entries, slots past 2^32, shuffled and offset numberings, the other solvers of the handle, the refusals.
+Every value is printed before it is asserted."""
+import ctypes as C
+import functools
+import itertools
+from math import comb
+
+import numpy as np
+import pytest
+
+import twin_graphs as T
+from common import GOLDEN, load_graph
+from graphminer_amd import Graph, SglSolver, TCSolver, _lib, ktruss, tc_list, tc_local
+from graphminer_amd.rmat import csr_from_pairs
+from list_ref import list_ref, sort_rows
+
+pytestmark = pytest.mark.gpu
+AS_NUMBERED = 0x200
+SMALL = ["citeseer", "cora", "rmat6_ef4_s1", "rmat8_ef8_s42", "rmat10_ef16_s42"]
+# csrc/gm_mine.h kListWholeWave: a streamed list of this many keys or more is strided by the whole wave, a shorter one is flattened.  The
+# longest streamed list of K_n is N+(1), n - 2 keys: K_65 is the last complete graph that is all flattened, K_66 the first with a whole-wave list
+WHOLE_WAVE = 64
+SENTINEL = -7
+
+
+def t6(x):
+    return [0, 0, 0, 0, 0, 0, x]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    import torch
+
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    return 0
+
+
+@functools.lru_cache(maxsize=None)
+def ref(name):
+    r = list_ref(load_graph(name))
+    r.setflags(write=False)
+    return r
+
+
+def check(label, got, want):
+    print(f"{label}: got {got} want {want}", flush=True)
+    assert got == want, label
+
+
+def check_rows(label, got, want):
+    got, want = np.asarray(got), np.asarray(want)
+    same = got.shape == want.shape and got.dtype == want.dtype
+    bad = np.flatnonzero((got != want).any(axis=1)) if same else np.zeros(0, np.int64)
+    print(f"{label}: got {got.shape} {got.dtype} want {want.shape} {want.dtype}, {bad.size} rows differ, first at {bad[:3].tolist()}: "
+          f"got {got[bad[:3]].tolist() if same else '-'} want {want[bad[:3]].tolist() if same else '-'}", flush=True)
+    assert same and bad.size == 0, label
+
+
+def ascending(tri):
+    return bool((tri[:, 0] < tri[:, 1]).all() and (tri[:, 1] < tri[:, 2]).all())
+
+
+def raw_call(sym, first, cap, buf, la=None):
+    """gm_tc_list itself: (status, total, n_written); buf a torch int32 tensor or None"""
+    total, written = C.c_uint64(99), C.c_uint64(99)
+    rc = _lib.load().gm_tc_list(sym.handle, C.byref(la) if la is not None else None, first, cap, buf.data_ptr() if buf is not None else None,
+                                C.byref(total), C.byref(written), None)
+    return rc, int(total.value), int(written.value)
+
+
+def windows(sym, size, upto):
+    """the windows [0, size), [size, 2 size), ... up to `upto` triangles: every call writes behind the one before it into one device
+    buffer (pre-filled, with slack), which comes back once"""
+    import torch
+
+    buf = torch.full((3 * upto + 64,), SENTINEL, dtype=torch.int32, device=f"cuda:{sym.device}")
+    lib, written = _lib.load(), C.c_uint64(0)
+    for f in range(0, upto, size):
+        want = min(size, upto - f)
+        rc = lib.gm_tc_list(sym.handle, None, f, want, buf.data_ptr() + 12 * f, None, C.byref(written), None)
+        assert (rc, int(written.value)) == (_lib.GM_OK, want), (f, rc, written.value)
+    host = buf.cpu().numpy()
+    assert bool((host[3 * upto:] == SENTINEL).all()), "nothing behind the last window"
+    return host[:3 * upto].reshape(-1, 3)
+
+
+@pytest.mark.parametrize("name", SMALL)
+def test_small_graphs(dev, name):
+    g = load_graph(name)
+    want = ref(name)
+    with g.to_device(dev) as sym:
+        total, tri, st = tc_list(sym, return_stats=True)
+        check_rows(f"{name} sorted list", sort_rows(tri), want)
+        check(f"{name} every row a < b < c", ascending(tri), True)
+        check(f"{name} total", total, GOLDEN[name]["motif3"][1])
+        check(f"{name} n_written", len(tri), total)
+        check(f"{name} stats.tasks", st.tasks, g.E())
+        print(f"{name} kernel_ms {st.kernel_ms}", flush=True)
+        assert st.kernel_ms > 0
+        with sym.orient() as dag:
+            check(f"{name} total against TCSolver", total, TCSolver(dag))
+        total2, tri2 = tc_list(sym)
+        check(f"{name} second call total", total2, total)
+        check_rows(f"{name} second call, the same sequence", tri2, tri)
+
+
+def test_count_only_and_guard_words(dev):
+    import torch
+
+    name = "rmat10_ef16_s42"
+    T_ = GOLDEN[name]["motif3"][1]
+    with load_graph(name).to_device(dev) as sym:
+        check("count only", raw_call(sym, 0, 12345, None), (_lib.GM_OK, T_, 0))
+        full = tc_list(sym)[1]
+        buf = torch.full((3 * T_ + 64,), SENTINEL, dtype=torch.int32, device=f"cuda:{dev}")
+        check("cap = T - 5", raw_call(sym, 0, T_ - 5, buf), (_lib.GM_OK, T_, T_ - 5))
+        host = buf.cpu().numpy()
+        check("ints changed", int((host != SENTINEL).sum()), 3 * (T_ - 5))
+        check("ints behind the window untouched", bool((host[3 * (T_ - 5):] == SENTINEL).all()), True)
+        check_rows("the first T - 5 rows", host[:3 * (T_ - 5)].reshape(-1, 3), full[:T_ - 5])
+        buf.fill_(SENTINEL)
+        for first in (T_, T_ + 1, 2**40):
+            check(f"first = {first}", raw_call(sym, first, 10, buf), (_lib.GM_OK, T_, 0))
+        check("nothing written", bool((buf.cpu().numpy() == SENTINEL).all()), True)
+
+
+@pytest.mark.parametrize("name", ["cora", "rmat10_ef16_s42"])
+def test_windows_tile_the_list(dev, name):
+    with load_graph(name).to_device(dev) as sym:
+        total, full = tc_list(sym)
+        check(f"{name} total", total, GOLDEN[name]["motif3"][1])
+        for size, upto in ((1, min(200, total)), (7, total), (64, total), (1000, total)):
+            check_rows(f"{name} windows of {size}", windows(sym, size, upto), full[:upto])
+        parts = [tc_list(sym, first=f, cap=1000)[1] for f in range(0, total, 1000)]
+        check_rows(f"{name} windows of 1000 through the mirror", np.concatenate(parts), full)
+
+
+@pytest.mark.parametrize("n", sorted({3, 4, 63, 64, 65, 66, 130, 200, WHOLE_WAVE + 1, WHOLE_WAVE + 2}))
+def test_complete_graphs_cross_the_tile_and_the_threshold(dev, n):
+    """K_n: DAG rows of every length 0 .. n - 1, streamed lists of every length 0 .. n - 2"""
+    want = np.array(list(itertools.combinations(range(n), 3)), dtype=np.int32).reshape(-1, 3)
+    with T.graph("complete", (n,)).to_device(dev) as sym:
+        total, tri = tc_list(sym)
+        check(f"K_{n} total", total, comb(n, 3))
+        check_rows(f"K_{n} rows", sort_rows(tri), want)
+        upto = min(total, 2000)
+        check_rows(f"K_{n} windows of 50", windows(sym, 50, upto), tri[:upto])
+
+
+def test_rows_beyond_2048_entries(dev):
+    """K_{2100,2101} + one triangle inside the 2100 side: the DAG rows of the 2101 side have 2100 entries, more than the 2048-entry LDS stage
+    of the other triangle kernels; the listing stages no row (the longer list is bisected in global memory), so no size is special to it"""
+    a, b = 2100, 2101
+    n, s, d = T.pairs("kab", (a, b))
+    inner = [(0, 1), (1, 2), (0, 2)]
+    g = csr_from_pairs(n, np.concatenate([s, [x for x, _ in inner]]).astype(np.uint64), np.concatenate([d, [y for _, y in inner]]).astype(np.uint64))
+    want = np.array([(0, 1, 2)] + [(x, y, w) for x, y in inner for w in range(a, n)], dtype=np.int32)
+    want = sort_rows(want)
+    check("expected triangles", len(want), 6304)
+    with g.to_device(dev) as sym:
+        total, tri = tc_list(sym)
+        check("total", total, 6304)
+        check_rows("rows", sort_rows(tri), want)
+
+
+def test_offsets_past_2_32(dev):
+    n = 3000
+    T_ = comb(n, 3)
+    check("T of K_3000", T_, 4495501000)
+    with T.graph("complete", (n,)).to_device(dev) as sym:
+        check("count only", raw_call(sym, 0, 0, None), (_lib.GM_OK, T_, 0))
+        total, both = tc_list(sym, first=2**32 - 100, cap=200)
+        check("window across 2^32", (total, both.shape), (T_, (200, 3)))
+        check("valid rows", bool(ascending(both) and both.min() >= 0 and both.max() < n), True)
+        check("distinct rows", len(np.unique(both, axis=0)), 200)
+        lo, hi = tc_list(sym, first=2**32 - 100, cap=100)[1], tc_list(sym, first=2**32, cap=100)[1]
+        check_rows("two windows of 100", np.concatenate([lo, hi]), both)
+        total, tail = tc_list(sym, first=T_ - 3, cap=10)
+        check("the last three", (total, tail.shape), (T_, (3, 3)))
+        check("valid last rows", bool(ascending(tail) and tail.max() < n and len(np.unique(tail, axis=0)) == 3), True)
+
+
+def permuted_rmat10():
+    g = load_graph("rmat10_ef16_s42")
+    perm = np.random.default_rng(5).permutation(g.V()).astype(np.uint64)
+    src = np.repeat(np.arange(g.V()), np.diff(g.row_ptr))
+    return csr_from_pairs(g.V(), perm[src], perm[g.col_idx])
+
+
+@pytest.mark.parametrize("which", ["rmat10 permuted", "multipartite (3, 40) at 517 of 1000"])
+def test_the_callers_numbering(dev, which):
+    g = permuted_rmat10() if which.startswith("rmat10") else T.graph("multipartite", (3, 40), nv=1000, offset=517)
+    want = list_ref(g)
+    assert len(want) == (GOLDEN["rmat10_ef16_s42"]["motif3"][1] if which.startswith("rmat10") else 40**3)
+    with g.to_device(dev) as sym:
+        for tune in (None, t6(AS_NUMBERED)):
+            total, tri = tc_list(sym, tune=tune)
+            check(f"{which} tune={tune} total", total, len(want))
+            check_rows(f"{which} tune={tune} rows", sort_rows(tri), want)
+
+
+def test_neighbours_on_the_handle(dev):
+    name = "rmat10_ef16_s42"
+    g = load_graph(name)
+    with g.to_device(dev) as fresh:
+        want_total, want_tri = tc_list(fresh)
+    with g.to_device(dev) as fresh:
+        want_local = tc_local(fresh)
+    with g.to_device(dev) as fresh:
+        want_truss = ktruss(fresh, 4)
+    check("fresh total", want_total, GOLDEN[name]["motif3"][1])
+
+    def same_list(label, sym):
+        total, tri = tc_list(sym)
+        check(label + " total", total, want_total)
+        check_rows(label + " sequence", tri, want_tri)
+
+    def same_local(label, sym):
+        total, tv, sup = tc_local(sym)
+        check(label, (total, bool(np.array_equal(tv, want_local[1])), bool(np.array_equal(sup, want_local[2]))), (want_local[0], True, True))
+
+    def same_truss(label, sym):
+        n, sup, _ = ktruss(sym, 4)
+        check(label, (n, bool(np.array_equal(sup, want_truss[1]))), (want_truss[0], True))
+
+    with g.to_device(dev) as sym:  # the list first, then each neighbour, the list after each
+        same_list("list first", sym)
+        same_local("tc_local after the list", sym)
+        same_list("list after tc_local", sym)
+        check("diamond after the list", SglSolver(sym, "diamond"), GOLDEN[name]["diamond"])
+        same_list("list after diamond", sym)
+        same_truss("ktruss after the list", sym)
+        same_list("list after ktruss", sym)
+    for label, other in (("tc_local", same_local), ("ktruss", same_truss)):
+        with g.to_device(dev) as sym:  # the neighbour first on a fresh handle
+            other(f"{label} first", sym)
+            same_list(f"list after a first {label}", sym)
+            other(f"{label} again", sym)
+    with g.to_device(dev) as sym:
+        check("diamond first", SglSolver(sym, "diamond"), GOLDEN[name]["diamond"])
+        same_list("list after a first diamond", sym)
+        check("diamond again", SglSolver(sym, "diamond"), GOLDEN[name]["diamond"])
+
+
+def test_refusals_and_the_empty_graph(dev):
+    import torch
+
+    g = load_graph("citeseer")
+    buf = torch.zeros(64, dtype=torch.int32, device=f"cuda:{dev}")
+    with g.to_device(dev) as sym:
+        la = _lib.gm_launch()
+        la.rank, la.world = 0, 2
+        check("world = 2", raw_call(sym, 0, 4, buf, la), (_lib.GM_ERR_UNSUPPORTED, 0, 0))
+        la = _lib.gm_launch()
+        counts = torch.zeros(8, dtype=torch.int64, device=f"cuda:{dev}")
+        la.d_counts = counts.data_ptr()
+        check("d_counts", raw_call(sym, 0, 4, buf, la), (_lib.GM_ERR_UNSUPPORTED, 0, 0))
+        check("the handle still lists", tc_list(sym)[0], 1166)
+    rev = g.col_idx.copy()
+    for v in range(g.V()):
+        a, b = int(g.row_ptr[v]), int(g.row_ptr[v + 1])
+        rev[a:b] = rev[a:b][::-1]
+    with Graph(row_ptr=g.row_ptr.copy(), col_idx=rev, name="citeseer_descending").to_device(dev) as sym:
+        check("unsorted rows", raw_call(sym, 0, 4, buf), (_lib.GM_ERR_INVALID, 0, 0))
+        assert b"ascending" in _lib.load().gm_last_error()
+    with Graph(row_ptr=[0, 0, 0, 0], col_idx=[]).to_device(dev) as sym:
+        check("no edges", raw_call(sym, 0, 4, buf), (_lib.GM_OK, 0, 0))
+        total, tri = tc_list(sym)
+        check("no edges, mirror", (total, tri.shape), (0, (0, 3)))
