@@ -117,6 +117,8 @@ SYMBOLS = [
     ("gm_diamond_support_size", C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     ("gm_diamond_support_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("gm_tc_core_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("gm_tc_pairs_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("gm_tc_pair_rule", C.c_int, [_P, C.c_int, C.c_int, C.c_uint64, _P]),
     ("gm_sup_core_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("gm_diamond_support_partial", C.c_int, [_P, C.POINTER(gm_launch), _P, C.c_int64, C.POINTER(gm_stats)]),
     ("gm_diamond_support_finish", C.c_int, [_P, C.POINTER(gm_launch), _P, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),

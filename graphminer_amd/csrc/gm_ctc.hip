@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kCtcWaves *GM_WAVE) void core_tc_kernel(const CoreT
 constexpr int kCtcBWaves = 8;        // wave (wi = w & 3, wj = w >> 2): I rows 64 wi .. + 63, J rows 128 wj .. + 127 of the block
 // (a column chunk: 512 columns = 16 words = 64 bytes of a row)
 constexpr int kCtcBStride = 20;      // LDS words per row (16 + 4: see the header)
-constexpr int kCtcBPiece = 16;       // chunks per task (triangle count)
+// (kCtcBPiece, gm_mine.h: chunks per task of the triangle count)
 constexpr int kCtcBPieceSup = 32;    // ... of the edge supports' product: every piece ends with an epilogue of atomics per edge
 constexpr int kCtcBStages = 2;  // two LDS stages (80 KB): ONE workgroup barrier per chunk (one stage, two barriers: 5 - 6 % slower, profiles/r05/ab_tc_core.txt)
 constexpr int kCtcBPanWords = 512 * kCtcBStride;
@@ -177,11 +177,20 @@ __global__ __launch_bounds__(kCtcBWaves *GM_WAVE) void core_tc_block_kernel(cons
     __syncthreads();
     const long long t64 = (long long)p.first + (long long)q * p.step;
     if (t64 >= (long long)p.ntasks) break;
-    const int pair = (int)(t64 / maxp), piece = (int)(t64 - (long long)pair * maxp);
-    int JB = (int)((sqrtf(8.f * (float)pair + 1.f) - 1.f) * 0.5f);
-    while ((JB + 1) * (JB + 2) / 2 <= pair) ++JB;
-    while (JB * (JB + 1) / 2 > pair) --JB;
-    const int IB = pair - JB * (JB + 1) / 2;
+    int IB, JB, piece;
+    if (!SUP && p.tasks != nullptr) {  // the chosen pairs' pieces, longest first (gm_tables.hip tc_pairs_setup)
+      const unsigned t = p.tasks[t64];
+      IB = (int)(t & 255u);
+      JB = (int)((t >> 8) & 255u);
+      piece = (int)(t >> 16);
+    } else {
+      const int pair = (int)(t64 / maxp);
+      piece = (int)(t64 - (long long)pair * maxp);
+      JB = (int)((sqrtf(8.f * (float)pair + 1.f) - 1.f) * 0.5f);
+      while ((JB + 1) * (JB + 2) / 2 <= pair) ++JB;
+      while (JB * (JB + 1) / 2 > pair) --JB;
+      IB = pair - JB * (JB + 1) / 2;
+    }
     // chunks below the J block hold no bit of its rows (strictly upper triangular); the chunk with the diagonal is taken whole
     const int cb = (SUP ? 0 : (JB >> 1)) + piece * kPiece, ce = min(cb + kPiece, nc);
     if (cb >= nc) continue;  // (workgroup-uniform: this pair has fewer pieces)
@@ -315,8 +324,9 @@ hipError_t launch_core_tc(CoreTcParams p, int cu_count, hipStream_t stream) {
   static_assert(kCtcBPieceSup * 512 < (1 << 24), "an accumulator of a supports' piece stays exact in f32");
   if (p.core == nullptr || p.h < 1 || p.h > kCtcMaxH || p.step < 1 || p.first < 0 || p.first >= p.step) return hipErrorInvalidValue;
   const bool fast = core_tc_fast_path(p);
+  if (p.tasks != nullptr && (!fast || p.n_list < 0)) return hipErrorInvalidValue;  // (a list of block pairs: the block kernel only)
   const int nJ = (p.h + 63) >> 6;
-  p.ntasks = fast ? ctc_block_tasks(p.h) : nJ * (nJ + 1) / 2;
+  p.ntasks = p.tasks != nullptr ? p.n_list : (fast ? ctc_block_tasks(p.h) : nJ * (nJ + 1) / 2);
   const long long mine = ((long long)p.ntasks - p.first + p.step - 1) / p.step;
   if (mine <= 0) return hipSuccess;
   if (fast) {

@@ -282,6 +282,8 @@ extern "C" void gm_graph_free(gm_graph *g) {
     if (q) dev_free(q);
   if (g->d_csym) dev_free(g->d_csym);
   if (g->d_cfirst) dev_free(g->d_cfirst);
+  if (g->d_tc_pair_bits) dev_free(g->d_tc_pair_bits);
+  if (g->d_tc_pair_tasks) dev_free(g->d_tc_pair_tasks);
   if (g->d_idx0) dev_free(g->d_idx0);
   if (g->d_wblock_prefix) dev_free(g->d_wblock_prefix);
   if (g->d_house_prefix) dev_free(g->d_house_prefix);

@@ -432,10 +432,22 @@ struct gm_graph {
   int n_cg_blocks = 0;
   int cg_tri_state = 0;                // 0 unknown, 1 built, 2 not applicable (no core bitmap, no room)
   // triangle count: the out-edges of the last tc_core_h vertices are counted on the matrix cores from the corner of d_core (gm_ctc.hip) and
-  // the key stream / the longer lists of this handle hold no task of a row >= kst_skip_from (ensure_keystream); 0 / nv: no such corner
+  // the key stream / the longer lists of this handle hold no task of a row >= kst_skip_from (ensure_keystream); 0 / nv: no such corner.
+  // With a choice of block pairs (tc_pair_region > 0, below) the three keep NAMING the base corner of the density rule (gm_tc_core_info)
+  // but the stream leaves out the chosen pairs' edges instead, rows >= kst_skip_from host tasks again: read kst_skip_from < nv only as
+  // "this stream lacks edges that the product takes", never as a row bound
   int tc_core_h = 0;
   int kst_skip_from = 0x7fffffff;
   long long tc_core_edges = 0;         // entries of the rows >= kst_skip_from
+  // ... chosen per PAIR of 256-row blocks (IB <= JB) of a region at the end of the core bitmap instead of as a full triangle of rows
+  // (tc_pairs_setup, gm_tables.hip): the stream then leaves out exactly the edges u -> v, u >= tc_pair_from, whose bit
+  // IB * nb + JB of d_tc_pair_bits is set, and the product walks d_tc_pair_tasks (CoreTcParams::tasks).  tc_core_h / kst_skip_from /
+  // tc_core_edges keep describing the base corner the density rule names (gm_tc_core_info).  tc_pair_region = 0: no selection
+  int tc_pair_region = 0, tc_pair_from = 0x7fffffff;
+  unsigned *d_tc_pair_bits = nullptr;
+  unsigned *d_tc_pair_tasks = nullptr;
+  int n_tc_pair_tasks = 0;
+  long long tc_pair_info[6] = {0, 0, 0, 0, 0, 0};  // gm_tc_pairs_info
   // the same for the TASK LISTS (ensure_tasklists: the edge supports, the triangle count without a key stream): no task of a row >= tl_skip_from;
   // the supports of the corner's edges come from the symmetric corner d_csym (tl_core_h / 32 words per row) with d_cfirst[row][word] = position
   // of the word's first entry inside its row (ensure_sup_corner, gm_tables.hip; core_tc_block_kernel<true>, gm_ctc.hip)

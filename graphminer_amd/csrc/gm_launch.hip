@@ -923,10 +923,17 @@ static int launch_tc(PatternRun &r) {
     memset(&cp, 0, sizeof cp);
     cp.core = g->d_core;
     cp.row_words = (g->core_h + 31) / 32;
-    cp.row0 = pl.corner_from - g->core_base;
+    // (a stream built with a choice of block pairs, tc_pairs_setup: the region they lie in and the list of their pieces)
+    const bool pairs = pl.use_kst && g->tc_pair_region > 0;
+    const int from = pairs ? g->tc_pair_from : pl.corner_from;
+    cp.row0 = from - g->core_base;
     cp.word0 = cp.row0 >> 5;
-    cp.h = g->nv - pl.corner_from;
+    cp.h = g->nv - from;
     cp.ntasks = 0;
+    if (pairs) {
+      cp.tasks = g->d_tc_pair_tasks;
+      cp.n_list = g->n_tc_pair_tasks;
+    }
     if (int rc = launch_corner(r, cp, false)) return rc;
     // (gm_stats.tasks: a table's task edges are its rows' entries -- the corner's rows are chunks of the table like any other)
   }
@@ -1254,6 +1261,19 @@ extern "C" int gm_tc_core_info(const gm_graph *dag, int64_t info[4]) {
   info[1] = on ? run_on->tc_core_edges : 0;       // DAG entries inside it
   info[2] = nJ * (nJ + 1) / 2;                    // 64 x 64 blocks of the masked product
   info[3] = on ? run_on->core_h : 0;              // vertices of the core bitmap the corner is a part of
+  return GM_OK;
+}
+
+// ... and the block pairs of it the product takes (tc_pairs_setup, gm_tables.hip): info[0] = rows of the region (0: no selection -- the full
+// triangle of gm_tc_core_info's corner, or none), [1] = pairs taken, [2] = pairs that hold keys, [3] = DAG entries in the product,
+// [4] = keys of the stream's model that left the stream, [5] = R of the rule
+extern "C" int gm_tc_pairs_info(const gm_graph *dag, int64_t info[6]) {
+  if (!dag || !info) return GM_ERR_INVALID;
+  gm_graph *run_on = nullptr;
+  const int rc = topo_view(dag->dag_cache ? dag->dag_cache : dag, nullptr, &run_on);
+  if (rc) return rc;
+  const bool on = run_on->kst_skip_from < run_on->nv && run_on->tc_pair_region > 0;
+  for (int i = 0; i < 6; ++i) info[i] = on ? run_on->tc_pair_info[i] : 0;
   return GM_OK;
 }
 

@@ -447,7 +447,13 @@ struct CoreTcParams {
   int base;
   const unsigned short *first_pos;
   unsigned *sup;
+  // the triangle count's chosen block pairs (gm_tables.hip tc_pairs_setup): n_list entries IB | JB << 8 | piece << 16, longest first;
+  // nullptr: every pair IB <= JB of the corner, every piece
+  const unsigned *tasks;
+  int n_list;
 };
+constexpr int kCtcBPiece = 16;         // 512-column chunks per task of the block kernel (triangle count)
+__host__ __device__ inline unsigned ctc_pack_task(int ib, int jb, int piece) { return (unsigned)ib | ((unsigned)jb << 8) | ((unsigned)piece << 16); }
 hipError_t launch_core_tc(CoreTcParams p, int cu_count, hipStream_t stream);
 hipError_t launch_core_sup(CoreTcParams p, int cu_count, hipStream_t stream);
 hipError_t launch_core_sym_fill(int nv, int base, int words, long long e0, long long e1, const int *rp, const int *col, unsigned *bits,

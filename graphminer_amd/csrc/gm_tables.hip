@@ -882,26 +882,32 @@ struct TaskWalk {
   const int *rp, *col;
   const int2 *edesc;
   int skip_from = 0x7fffffff;     // the out-edges of the rows >= skip_from are no tasks (the triangle count takes them from the core bitmap, gm_ctc.hip)
+  // ... or, chosen per pair of 256-row blocks (tc_pairs_setup): the edge u -> v of a row u >= region_from is no task when bit
+  // ((u - region_from) >> 8) * pair_nb + ((v - region_from) >> 8) of pair_bits is set.  Its row keeps its length: positions and tails stay
+  int region_from = 0x7fffffff, pair_nb = 0;
+  const unsigned *pair_bits = nullptr;
 };
-// calls f(u, i, e, ru, du, dv, tail, u_hosts) for every task edge of the rows this workgroup walks (all 64 lanes of a wave stay together:
-// f may use wave ballots; `act` = the lane holds a task)
+// calls f(u, i, e, ru, du, dv, tail, u_hosts) for every task edge of the rows u0 + 8 * (wave's trips of `stride` rows) below u_end (all 64
+// lanes of a wave stay together: f may use wave ballots; `act` = the lane holds a task)
 template <class F>
-__device__ __forceinline__ void task_walk(const TaskWalk &w, F f) {
-  const long long stride = ((long long)gridDim.x * blockDim.x) >> 3;
+__device__ __forceinline__ void task_walk_rows(const TaskWalk &w, const long long u0, const long long u_end, const long long stride, F f) {
   const int sub = threadIdx.x & 7;
-  const long long u0 = ((long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63)) >> 3;  // first row of this wave (8 rows per wave and trip)
-  for (long long ub = u0; ub < w.nv; ub += stride) {
+  for (long long ub = u0; ub < u_end; ub += stride) {
     const long long u = ub + ((threadIdx.x & 63) >> 3);
     int ru = 0, du = 0;
-    if (u < w.nv) {
+    if (u < u_end) {
       ru = w.rp[u];
       du = w.rp[u + 1] - ru;
       if (du > w.stage_max || u >= w.skip_from) du = 0;  // a row the stage cannot take hosts nothing, and its out-edges stay with the chunked kernel (run_pattern)
     }
     const int dmax = wave_max_nonneg(du);
     for (int i = sub; i - sub < dmax; i += 8) {  // wave-uniform trip count
-      const bool act = i < du;
+      bool act = i < du;
       const int e = ru + (act ? i : 0);
+      if (act && u >= w.region_from) {  // (topological: v > u, inside the region too)
+        const int b = ((int)(u - w.region_from) >> 8) * w.pair_nb + ((w.col[e] - w.region_from) >> 8);
+        act = ((w.pair_bits[b >> 5] >> (b & 31)) & 1u) == 0u;
+      }
       const int2 dv = act ? w.edesc[e] : make_int2(0, 0);  // {rp[v], d+(v)} of the entry's target v
       // the host = the endpoint whose list is NOT streamed: N+(v) whole, or N+(u) -- under a topological numbering only its part beyond
       // v -- whichever is shorter (ties: the source hosts); a list that does not fit the stage never hosts
@@ -910,6 +916,11 @@ __device__ __forceinline__ void task_walk(const TaskWalk &w, F f) {
       f(act, (int)u, i, e, ru, du, dv, tail, u_hosts);
     }
   }
+}
+// ... for every row of the graph, dealt to the waves of the grid (8 rows per wave and trip)
+template <class F>
+__device__ __forceinline__ void task_walk(const TaskWalk &w, F f) {
+  task_walk_rows(w, ((long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63)) >> 3, (long long)w.nv, ((long long)gridDim.x * blockDim.x) >> 3, f);
 }
 
 template <bool PLACE>
@@ -1122,6 +1133,164 @@ static int tc_core_size(gm_graph *g, const char *env = "GM_TC_CORE_H", bool bloc
   }
   return 0;
 }
+
+// ---- the hub corner chosen per PAIR of 256-row blocks ------------------------------------------------------------------------------------
+// The product takes the edges of a pair (IB <= JB) of 256-row blocks of a region at the end of the core bitmap for
+// 65536 * (columns from JB's 512-column chunk to the region's end) bit-products whatever the pair holds; the stream takes them for the
+// min(d+(v), tail_u(v)) keys of each.  Every triangle is counted by its (smallest, middle) edge, so ANY set of pairs is exact as long as the
+// stream leaves out exactly the edges of the chosen ones: a pair is taken iff its keys * R > its bit-products.
+// kTcPairR: the bit-products a streamed key is worth.  From profiles/r07/ab_tc_long_list.txt (R-MAT-22, full corner of 16 K): tch_kernel<1024>
+// 1.436 ms for the 1.716 G keys outside the corner = 0.837 ps per key, core_tc_block_kernel<false> 0.247 ms for 16384^3 / 6 = 7.33e11
+// bit-products = 0.337 fs each: 2480.  GM_TC_PAIR_R overrides (sweep: profiles/r09/ab_tc_corner_pairs.txt).
+constexpr unsigned long long kTcPairR = 2480;
+// the rule, on the host: keys[IB * nb + JB] = the stream's keys of the pair's edges; sets bit IB * nb + JB of bits[(nb * nb + 31) / 32] for
+// every pair taken and returns their number (< 0: invalid arguments)
+// (keys * R > cost  <=>  keys > floor(cost / R) for integers: no overflow whatever R)
+__host__ __device__ inline bool tc_pair_pays(const unsigned keys, const int jb, const int region, const unsigned long long R) {
+  const unsigned long long cost = 65536ull * (unsigned long long)(region - 512 * (jb >> 1));
+  return R != 0ull && (unsigned long long)keys > cost / R;
+}
+extern "C" int gm_tc_pair_rule(const uint32_t *keys, int nb, int region, uint64_t R, uint32_t *bits) {
+  if (!keys || !bits || nb < 1 || nb > 128 || region != nb * 256) return -1;
+  const int nwords = (nb * nb + 31) / 32;
+  for (int i = 0; i < nwords; ++i) bits[i] = 0u;
+  int taken = 0;
+  for (int ib = 0; ib < nb; ++ib)
+    for (int jb = ib; jb < nb; ++jb)
+      if (tc_pair_pays(keys[ib * nb + jb], jb, region, R)) {
+        const int b = ib * nb + jb;
+        bits[b >> 5] |= 1u << (b & 31);
+        ++taken;
+      }
+  return taken;
+}
+// the cells of the rule: a workgroup per block of 256 rows, its row of cells in LDS -- per (IB, JB) the keys the stream would move for the
+// pair's edges (the list a task streams, as kst_rows_kernel's task_list) and the edges themselves
+constexpr int kPairMaxNb = kCtcMaxH / 256;
+__global__ __launch_bounds__(1024) void tc_pair_cells_kernel(const TaskWalk w, const int region_from, const int nb, unsigned *__restrict__ keys,
+                                                              unsigned *__restrict__ edges) {
+  __shared__ unsigned ck[kPairMaxNb], ce[kPairMaxNb];
+  for (int j = threadIdx.x; j < kPairMaxNb; j += blockDim.x) ck[j] = ce[j] = 0u;
+  __syncthreads();
+  const int ib = blockIdx.x;
+  const long long r0 = (long long)region_from + 256ll * ib;
+  task_walk_rows(w, r0 + ((threadIdx.x & ~63) >> 3), r0 + 256, (long long)(blockDim.x >> 3),
+                 [&](const bool act, const int, const int, const int e, const int, const int, const int2 dv, const int tail, const bool u_hosts) {
+                   if (!act) return;
+                   const int jb = (w.col[e] - region_from) >> 8;  // (topological: ib <= jb < nb)
+                   atomicAdd(&ck[jb], (unsigned)(u_hosts ? dv.y : tail));
+                   atomicAdd(&ce[jb], 1u);
+                 });
+  __syncthreads();
+  for (int j = threadIdx.x; j < nb; j += blockDim.x) {
+    keys[ib * nb + j] = ck[j];
+    edges[ib * nb + j] = ce[j];
+  }
+}
+// the selection on the device (the host fetches 2 KB of bits and four sums instead of the cells: a copy of 128 KB into pageable memory
+// cost 5 ms of the first call): kind 0 = the rule (tc_pair_pays, what gm_tc_pair_rule evaluates), 1 all, 2 none, 3 checker, 4 diag,
+// 5 offdiag -- a pair without keys is never taken; sums = {taken, pairs with keys, edges taken, keys taken}; bits / sums zeroed before
+__global__ __launch_bounds__(256) void tc_pair_select_kernel(const int nb, const int region, const unsigned long long R, const int kind,
+                                                              const unsigned *__restrict__ keys, const unsigned *__restrict__ edges,
+                                                              unsigned *__restrict__ bits, unsigned long long *__restrict__ sums) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= nb * nb) return;
+  const int ib = b / nb, jb = b - ib * nb;
+  const unsigned k = keys[b];
+  if (ib > jb || k == 0u) return;
+  atomicAdd(&sums[1], 1ull);
+  const bool take = kind == 0 ? tc_pair_pays(k, jb, region, R)
+                              : (kind == 1 || (kind == 3 && ((ib + jb) & 1)) || (kind == 4 && ib == jb) || (kind == 5 && ib < jb));
+  if (!take) return;
+  atomicOr(&bits[b >> 5], 1u << (b & 31));
+  atomicAdd(&sums[0], 1ull);
+  atomicAdd(&sums[2], (unsigned long long)edges[b]);
+  atomicAdd(&sums[3], (unsigned long long)k);
+}
+// Decides the pairs of this handle (under g->mu, before the stream's count pass): tc_h = the base corner of the density rule (0: none).
+// Leaves g->tc_pair_region = 0 -- the full triangle of tc_h, as before -- when the corner is forced (GM_TC_CORE_H), switched off
+// (GM_TC_PAIRS=off), there is no base corner and no forced region, or the region cannot run on the block kernel.
+// GM_TC_PAIRS = rule | off | all | none | checker ((IB + JB) odd) | diag | offdiag (tests: the last five); GM_TC_PAIR_R = R of the rule;
+// GM_TC_PAIR_REGION = rows of the region whatever the density rule says (tests: small graphs)
+static int tc_pairs_setup(gm_graph *g, const TaskWalk &tw, const int tc_h) {
+  g->tc_pair_region = 0;
+  const char *mode = gm_opt("GM_TC_PAIRS");
+  if (!mode || !*mode) mode = "rule";
+  const char *forced_region = gm_opt("GM_TC_PAIR_REGION");
+  // (a misspelt option is an error on every graph, not only where a selection would have been made)
+  const int kind = !strcmp(mode, "rule") ? 0 : !strcmp(mode, "all") ? 1 : !strcmp(mode, "none") ? 2 : !strcmp(mode, "checker") ? 3 : !strcmp(mode, "diag") ? 4 : !strcmp(mode, "offdiag") ? 5 : !strcmp(mode, "off") ? 6 : -1;
+  if (kind < 0) return GM_ERR_INVALID;
+  long long region_want = 0;
+  if (forced_region) {
+    char *end = nullptr;
+    region_want = strtoll(forced_region, &end, 10);
+    if (end == forced_region || *end != '\0' || region_want <= 0) return GM_ERR_INVALID;
+  }
+  if (const char *e = gm_opt("GM_TC_PAIR_R")) {
+    char *end = nullptr;
+    if (strtoll(e, &end, 10) < 0 || end == e || *end != '\0') return GM_ERR_INVALID;
+  }
+  if (kind == 6 || gm_opt("GM_TC_CORE_H") || (tc_h <= 0 && !forced_region)) return GM_OK;
+  if (g->core_state != 1 || g->d_core == nullptr || !tw.topo) return GM_OK;
+  // the region: the largest multiple of 512 rows at the end of the core bitmap, at most a quarter of the vertices, starting where the block
+  // kernel's 16-byte loads can (core_tc_fast_path)
+  long long region = std::min<long long>(std::min<long long>(g->core_h, kCtcMaxH), (long long)g->nv / 4) / 512 * 512;
+  if (forced_region) region = region_want;
+  else while (region >= 512 && (g->core_h - region) % 128 != 0) region -= 512;
+  if (region < 512 || region % 512 != 0 || region > g->core_h || region > kCtcMaxH || region < tc_h) return GM_OK;
+  CoreTcParams cp;
+  memset(&cp, 0, sizeof cp);
+  cp.core = g->d_core;
+  cp.row_words = (g->core_h + 31) / 32;
+  cp.row0 = g->core_h - (int)region;
+  cp.word0 = cp.row0 >> 5;
+  cp.h = (int)region;
+  if (cp.row0 % 32 != 0 || !core_tc_fast_path(cp)) return GM_OK;
+  unsigned long long R = kTcPairR;
+  if (const char *e = gm_opt("GM_TC_PAIR_R")) R = (unsigned long long)std::max(0ll, atoll(e));
+  const int nb = (int)region / 256, nc = (int)region / 512, region_from = g->nv - (int)region, ncell = nb * nb, nwords = (ncell + 31) / 32;
+  DevBuf<unsigned> cells;
+  DevBuf<unsigned long long> sel;  // four sums, then the bits
+  HIP_TRY(cells.alloc((size_t)ncell * 2));
+  HIP_TRY(sel.alloc(4 + (size_t)(nwords + 1) / 2));
+  HIP_TRY(hipMemsetAsync(sel.p, 0, 8 * (4 + (size_t)(nwords + 1) / 2), 0));
+  hipLaunchKernelGGL(tc_pair_cells_kernel, dim3((unsigned)nb), dim3(1024), 0, 0, tw, region_from, nb, cells.p, cells.p + ncell);
+  hipLaunchKernelGGL(tc_pair_select_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, 0, nb, (int)region, R, kind, (const unsigned *)cells.p,
+                     (const unsigned *)(cells.p + ncell), reinterpret_cast<unsigned *>(sel.p + 4), sel.p);
+  HIP_TRY(hipGetLastError());
+  std::vector<unsigned long long> h_sel(4 + (size_t)(nwords + 1) / 2, 0ull);
+  HIP_TRY(hipMemcpy(h_sel.data(), sel.p, 8 * h_sel.size(), hipMemcpyDeviceToHost));
+  const unsigned *bits = reinterpret_cast<const unsigned *>(h_sel.data() + 4);
+  setup_trace("key stream: cells and choice of the block pairs");
+  // the product's tasks: the non-empty pieces (16 chunks from JB's on) of the chosen pairs, the longest first
+  std::vector<unsigned> tasks;
+  const long long taken = (long long)h_sel[0], possible = (long long)h_sel[1], p_edges = (long long)h_sel[2], p_keys = (long long)h_sel[3];
+  for (int ib = 0; ib < nb; ++ib)
+    for (int jb = ib; jb < nb; ++jb) {
+      const int b = ib * nb + jb;
+      if (!((bits[b >> 5] >> (b & 31)) & 1u)) continue;
+      for (int piece = 0, cb = jb >> 1; cb < nc; ++piece, cb += kCtcBPiece) tasks.push_back(ctc_pack_task(ib, jb, piece));
+    }
+  auto chunks_of = [&](const unsigned t) {
+    const int cb = (int)((t >> 8) & 255u) / 2 + (int)(t >> 16) * kCtcBPiece;
+    return std::min(cb + kCtcBPiece, nc) - cb;
+  };
+  std::stable_sort(tasks.begin(), tasks.end(), [&](const unsigned a, const unsigned b) { return chunks_of(a) > chunks_of(b); });
+  if (g->d_tc_pair_bits) { dev_free(g->d_tc_pair_bits); g->d_tc_pair_bits = nullptr; }
+  if (g->d_tc_pair_tasks) { dev_free(g->d_tc_pair_tasks); g->d_tc_pair_tasks = nullptr; }
+  HIP_TRY(dev_malloc(&g->d_tc_pair_bits, sizeof(unsigned) * (size_t)nwords));
+  HIP_TRY(dev_malloc(&g->d_tc_pair_tasks, sizeof(unsigned) * std::max<size_t>(tasks.size(), 1)));
+  HIP_TRY(hipMemcpy(g->d_tc_pair_bits, bits, sizeof(unsigned) * (size_t)nwords, hipMemcpyHostToDevice));
+  if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_tc_pair_tasks, tasks.data(), sizeof(unsigned) * tasks.size(), hipMemcpyHostToDevice));
+  g->n_tc_pair_tasks = (int)tasks.size();
+  g->tc_pair_from = region_from;
+  const long long info[6] = {region, taken, possible, p_edges, p_keys, (long long)R};
+  for (int i = 0; i < 6; ++i) g->tc_pair_info[i] = info[i];
+  g->tc_pair_region = (int)region;
+  setup_trace("key stream: tasks of the product, uploads");
+  return GM_OK;
+}
+
 int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
   auto have = [&]() { return g->d_kst_rp != nullptr && (!edges || g->d_kst_et != nullptr); };
   *built = have();
@@ -1176,8 +1345,17 @@ int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
   TaskWalk tw;
   tw.nv = g->nv; tw.stage_max = kTctStageMax; tw.topo = topo ? 1 : 0;
   tw.rp = g->d_rp; tw.col = g->d_col; tw.edesc = g->d_edesc;
-  const int skip_from = (!second && topo && tc_h > 0) ? g->nv - tc_h : 0x7fffffff;
-  tw.skip_from = skip_from;
+  int skip_from = (!second && topo && tc_h > 0) ? g->nv - tc_h : 0x7fffffff;
+  if (!second && allow_core && !edges) {  // the corner per pair of blocks: the stream leaves out the chosen pairs' edges instead of whole rows
+    if (const int rc = tc_pairs_setup(g, tw, skip_from < g->nv ? tc_h : 0)) return rc;
+    if (g->tc_pair_region > 0) {
+      tw.region_from = g->tc_pair_from;
+      tw.pair_nb = g->tc_pair_region / 256;
+      tw.pair_bits = g->d_tc_pair_bits;
+      if (skip_from >= g->nv) skip_from = g->tc_pair_from;  // (a forced region on a graph without a base corner: gm_tc_core_info names the region)
+    }
+  }
+  tw.skip_from = g->tc_pair_region > 0 ? 0x7fffffff : skip_from;
   long long core_edges = 0;
   if (skip_from < g->nv) {
     int e0 = 0;

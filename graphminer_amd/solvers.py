@@ -61,6 +61,30 @@ def tc_core_info(g: DeviceGraph) -> dict:
     return {"h": int(info[0]), "edges": int(info[1]), "blocks": int(info[2]), "core_h": int(info[3])}
 
 
+def tc_pairs_info(g: DeviceGraph) -> dict:
+    """the block pairs of the hub corner the product takes on this ORIENTED graph (gm_tc_pairs_info; after a first TCSolver call)"""
+    info = (C.c_int64 * 6)()
+    _lib.check(_lib.load().gm_tc_pairs_info(g.handle, info), "gm_tc_pairs_info")
+    return {"region": int(info[0]), "pairs": int(info[1]), "pairs_possible": int(info[2]), "edges": int(info[3]),
+            "keys_moved": int(info[4]), "R": int(info[5])}
+
+
+def tc_pair_rule(keys, nb: int, region: int, R: int):
+    """the rule that chooses the pairs (gm_tc_pair_rule; host only): keys = nb * nb uint32 cells, row IB, column JB -> nb x nb bool array"""
+    import numpy as np
+
+    keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+    if keys.size != nb * nb:
+        raise ValueError("tc_pair_rule: keys must hold nb * nb cells")
+    bits = np.zeros(max((nb * nb + 31) // 32, 1), dtype=np.uint32)
+    n = _lib.load().gm_tc_pair_rule(keys.ctypes.data, nb, region, R, bits.ctypes.data)
+    if n < 0:
+        raise ValueError("gm_tc_pair_rule: invalid arguments")
+    sel = ((bits[np.arange(nb * nb) >> 5] >> (np.arange(nb * nb, dtype=np.uint32) & 31)) & 1).astype(bool).reshape(nb, nb)
+    assert int(sel.sum()) == n
+    return sel
+
+
 def SglSolver(g: DeviceGraph, pattern: str, *, rank=0, world=1, chunk=0, return_stats=False, **kw):
     """Edge-induced subgraph listing on the SYMMETRIC graph; pattern by name (include/pattern.hh:62-78).
 

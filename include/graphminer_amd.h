@@ -216,6 +216,17 @@ int gm_tc(const gm_graph *dag, const gm_launch *launch, uint64_t *total, gm_stat
  * info[1] = DAG entries inside the corner, info[2] = 64 x 64 blocks of the product, info[3] = vertices of the core bitmap.
  * gm_dev_option("GM_TC_CORE_H", ..) (read when the handle's key stream is built): 0 = off, any other value = that H. */
 int gm_tc_core_info(const gm_graph *dag, int64_t info[4]);
+/* ... and, since the corner is chosen per PAIR of 256-row blocks (IB <= JB) of a region at the end of the core bitmap -- a pair goes to
+ * the product iff the keys the stream would move for its edges, times R, exceed the pair's 65536 * (region - 512 * (JB >> 1)) bit-products --
+ * what was chosen: info[0] = rows of the region (0: no selection on this handle), [1] = pairs taken, [2] = pairs that hold keys,
+ * [3] = DAG entries in the product, [4] = modelled keys moved out of the stream, [5] = R.  gm_tc_core_info keeps describing the base corner
+ * of the density rule.  gm_dev_option (read when the handle's key stream is built): "GM_TC_PAIRS" = rule (default) | off (the full triangle
+ * of the base corner) | all | none | checker | diag | offdiag, "GM_TC_PAIR_R" = R, "GM_TC_PAIR_REGION" = rows of the region whatever the
+ * density rule says (tests).  A forced GM_TC_CORE_H means the full triangle of that size, no selection. */
+int gm_tc_pairs_info(const gm_graph *dag, int64_t info[6]);
+/* the rule itself, on the host: keys[IB * nb + JB] (nb = region / 256 <= 128) -> bit IB * nb + JB of
+ * bits[(nb * nb + 31) / 32] for every pair taken; returns their number, < 0 for invalid arguments */
+int gm_tc_pair_rule(const uint32_t *keys, int nb, int region, uint64_t R, uint32_t *bits);
 
 /* SglSolver: edge-induced subgraph listing on the SYMMETRIC graph, pattern by NAME
  * (include/pattern.hh:62-78). Implemented: "diamond" (src/sgl/cpu_kernels/diamond.h:1-14,
