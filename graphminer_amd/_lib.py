@@ -126,6 +126,7 @@ SYMBOLS = [
     ("gm_selftest", C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     ("gm_dev_option", C.c_int, [C.c_char_p, C.c_char_p]),
     ("gm_dev_option_get", C.c_char_p, [C.c_char_p]),
+    ("gm_dev_live_blocks", C.c_int, [C.POINTER(C.c_int64)]),
 ]
 
 _lib = None
@@ -164,6 +165,13 @@ def dev_option(name, value=None):
     st = lib.gm_dev_option(None if name is None else str(name).encode(), None if value is None else str(value).encode())
     if st != GM_OK:
         raise GraphMinerError(st, "gm_dev_option", str(name))
+
+
+def dev_live_blocks() -> int:
+    """Device blocks the library has handed out and not yet got back (include/graphminer_amd.h gm_dev_live_blocks)."""
+    n = C.c_int64(0)
+    check(load().gm_dev_live_blocks(C.byref(n)), "gm_dev_live_blocks")
+    return n.value
 
 
 def check(status: int, where: str):

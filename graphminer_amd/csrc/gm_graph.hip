@@ -1,6 +1,7 @@
 // gm_graph.hip -- the device graph handle behind include/graphminer_amd.h: upload / adopt (GraphGPU::init, include/graph_gpu.h:69-122),
 // Graph::orientation and Graph::sort_neighbors on the GPU (src/common/graph.cc:233-279,138-146), degree renumbering, download.
 #include "gm_host.h"
+#include <atomic>
 #include <unordered_map>
 #include "gm_scan.h"
 #include "gm_setops.h"
@@ -62,6 +63,7 @@ bool big_cache_on() { return gm_opt("GM_NO_TEMP_POOL") == nullptr; }  // (read a
 // 9 / 16 / 41 / 69).  The cache is emptied when the LAST handle of the device is freed, and whenever an allocation meets an out-of-memory error.
 std::unordered_map<void *, size_t> g_dev_sizes;  // (under g_big_mu)
 int g_live_handles[64] = {0};                    // (under g_big_mu) handles alive per device
+std::atomic<long long> g_live_blocks{0};         // blocks handed out and not yet back (gm_dev_live_blocks); a block parked in the cache is back
 bool cache_take(int dev, size_t bytes, size_t max_bytes, void **p, size_t *got) {  // (caller holds g_big_mu) the smallest cached block in [bytes, max_bytes]
   size_t best = g_big_blocks.size();
   for (size_t i = 0; i < g_big_blocks.size(); ++i) {
@@ -93,6 +95,7 @@ hipError_t dev_malloc_bytes(void **p, size_t bytes) {
     size_t got = 0;
     if (cache_take(dev, bytes, bytes + bytes / 4, p, &got)) {  // (a persistent array: a block at most a quarter larger than asked for)
       g_dev_sizes[*p] = got;
+      g_live_blocks.fetch_add(1, std::memory_order_relaxed);
       return hipSuccess;  // (big_cache_put synchronised the device before the block went in)
     }
   }
@@ -106,6 +109,7 @@ hipError_t dev_malloc_bytes(void **p, size_t bytes) {
     std::lock_guard<std::mutex> lk(g_big_mu);
     g_dev_sizes[*p] = bytes;
   }
+  if (e == hipSuccess) g_live_blocks.fetch_add(1, std::memory_order_relaxed);
   return e;
 }
 void dev_free(void *p) {
@@ -119,8 +123,14 @@ void dev_free(void *p) {
       g_dev_sizes.erase(it);
     }
   }
-  if (bytes) big_cache_put(p, bytes);  // (synchronises the device; beyond the cache's budget: hipFree)
-  else (void)hipFree(p);
+  if (bytes) return big_cache_put(p, bytes);  // (synchronises the device; beyond the cache's budget: hipFree)
+  g_live_blocks.fetch_sub(1, std::memory_order_relaxed);
+  (void)hipFree(p);
+}
+extern "C" int gm_dev_live_blocks(int64_t *n) {
+  if (!n) return GM_ERR_INVALID;
+  *n = g_live_blocks.load(std::memory_order_relaxed);
+  return GM_OK;
 }
 hipError_t big_cache_get(void **p, size_t bytes, size_t *block_bytes) {
   *block_bytes = 0;
@@ -130,7 +140,10 @@ hipError_t big_cache_get(void **p, size_t bytes, size_t *block_bytes) {
     (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> lk(g_big_mu);
     // (a temporary: the smallest block that holds the request without wasting more than 3 / 4 of itself)
-    if (cache_take(dev, bytes, bytes * 4, p, block_bytes)) return hipSuccess;  // (big_cache_put synchronised the device before the block went in)
+    if (cache_take(dev, bytes, bytes * 4, p, block_bytes)) {  // (big_cache_put synchronised the device before the block went in)
+      g_live_blocks.fetch_add(1, std::memory_order_relaxed);
+      return hipSuccess;
+    }
   }
   hipError_t e = hipMalloc(p, bytes);
   if (e == hipErrorOutOfMemory) {
@@ -139,10 +152,12 @@ hipError_t big_cache_get(void **p, size_t bytes, size_t *block_bytes) {
     e = hipMalloc(p, bytes);
   }
   if (e == hipSuccess && on) *block_bytes = bytes;  // (0: a plain allocation, freed by hipFree)
+  if (e == hipSuccess) g_live_blocks.fetch_add(1, std::memory_order_relaxed);
   return e;
 }
 void big_cache_put(void *p, size_t block_bytes) {
   if (!p) return;
+  g_live_blocks.fetch_sub(1, std::memory_order_relaxed);
   (void)hipDeviceSynchronize();  // what hipFree did implicitly: nothing may still be using the block when it is handed out again
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -235,77 +250,13 @@ extern "C" void gm_graph_free(gm_graph *g) {
     r = nullptr;
   }
   (void)hipSetDevice(g->device);
-  free_tables(g);
-  for (auto &b : g->bitmap_sets) {
-    if (b.d_bitmaps) dev_free(b.d_bitmaps);
-    if (b.d_row_slot) dev_free(b.d_row_slot);
-  }
-  if (g->d_rp) dev_free(g->d_rp);
-  if (g->d_rp64) dev_free(g->d_rp64);
-  if (g->own_col && g->d_col) dev_free(g->d_col);
-  if (g->d_edesc) dev_free(g->d_edesc);
-  if (g->d_symdeg) dev_free(g->d_symdeg);
-  if (g->d_trp) dev_free(g->d_trp);
-  if (g->d_tdesc) dev_free(g->d_tdesc);
-  if (g->d_tedge) dev_free(g->d_tedge);
-  for (void *q : {(void *)g->d_emoff, (void *)g->d_tmoff, (void *)g->d_smask, (void *)g->d_sup_far_rows})
-    if (q) dev_free(q);
-  if (g->d_long_rows) dev_free(g->d_long_rows);
-  if (g->d_long_prefix) dev_free(g->d_long_prefix);
-  if (g->d_colk) dev_free(g->d_colk);
-  if (g->d_tdesck) dev_free(g->d_tdesck);
-  if (g->d_kst) dev_free(g->d_kst);
-  for (void *q : {(void *)g->d_kst_et, (void *)g->d_tedgel, (void *)g->d_kst2, (void *)g->d_tdescl2})
-    if (q) dev_free(q);
-  if (g->d_kst_rp) dev_free(g->d_kst_rp);
-  if (g->d_trpl) dev_free(g->d_trpl);
-  if (g->d_tdescl) dev_free(g->d_tdescl);
-  if (g->d_sup) dev_free(g->d_sup);
-  for (void *q : {(void *)g->d_w5sup, (void *)g->d_w5ed, (void *)g->d_w5deg, (void *)g->d_w5tv2, (void *)g->d_w5out})
-    if (q) dev_free(q);
-  for (void *q : {(void *)g->d_s6e1, (void *)g->d_wrect_mask, (void *)g->d_wrect_tasks})
-    if (q) dev_free(q);
-  for (void *q : {(void *)g->d_newid, (void *)g->d_lsup, (void *)g->d_lent, (void *)g->d_lrev, (void *)g->d_lmark, (void *)g->d_lfront, (void *)g->d_ltruss,
-                  (void *)g->d_lcnt, (void *)g->d_list_off})
-    if (q) dev_free(q);
-  free_clique_plans(g);
-  if (g->d_wide_mat) dev_free(g->d_wide_mat);
-  if (g->d_wide_sorted) dev_free(g->d_wide_sorted);
-  if (g->d_wide_queue) dev_free(g->d_wide_queue);
   for (auto &st_ : g->aux_stream) if (st_) (void)hipStreamDestroy(st_);
   for (auto &ev_ : g->aux_done) if (ev_) (void)hipEventDestroy(ev_);
-  if (g->pool.base) dev_free(g->pool.base);
-  if (g->d_counters) dev_free(g->d_counters);
-  if (g->d_scratch) dev_free(g->d_scratch);
-  if (g->d_core) dev_free(g->d_core);
-  for (void *q : {(void *)g->d_cg_tri, (void *)g->d_cg_rowbase, (void *)g->d_cg_bid, (void *)g->d_cg_blk})
-    if (q) dev_free(q);
-  if (g->d_csym) dev_free(g->d_csym);
-  if (g->d_cfirst) dev_free(g->d_cfirst);
-  if (g->d_tc_pair_bits) dev_free(g->d_tc_pair_bits);
-  if (g->d_tc_pair_tasks) dev_free(g->d_tc_pair_tasks);
-  if (g->d_idx0) dev_free(g->d_idx0);
-  if (g->d_wblock_prefix) dev_free(g->d_wblock_prefix);
-  if (g->d_house_prefix) dev_free(g->d_house_prefix);
-  if (g->d_pent_touched) dev_free(g->d_pent_touched);
-  if (g->d_house_t) dev_free(g->d_house_t);
-  if (g->d_house_tlt) dev_free(g->d_house_tlt);
-  if (g->d_house_tasks) dev_free(g->d_house_tasks);
-  if (g->d_house_acc) dev_free(g->d_house_acc);
-  if (g->d_house_touched) dev_free(g->d_house_touched);
-  if (g->d_house_bnd) dev_free(g->d_house_bnd);
-  if (g->d_house_lds_tasks) dev_free(g->d_house_lds_tasks);
-  if (g->d_house_cut_tasks) dev_free(g->d_house_cut_tasks);
-  if (g->d_rect_tasks) dev_free(g->d_rect_tasks);
-  if (g->d_rect_bnd) dev_free(g->d_rect_bnd);
-  if (g->d_rect_lds_tasks) dev_free(g->d_rect_lds_tasks);
-  if (g->d_rect_cut_tasks) dev_free(g->d_rect_cut_tasks);
-  if (g->d_rect_acc) dev_free(g->d_rect_acc);
   for (auto &pr : g->ev)
     for (auto &e : pr)
       if (e) (void)hipEventDestroy(e);
   const bool last = g->counted && dev_handle_died(g->device);
-  delete g;
+  delete g;  // (its device arrays, tables, plans and pool go back through their DevOwn members)
   // the blocks kept for reuse -- large temporaries, and the persistent arrays of freed handles (dev_free) -- go back to the driver with the
   // device's LAST handle (not inside a timed call); while another handle lives they serve the next one
   if (last) big_cache_trim();
@@ -338,7 +289,7 @@ int finish_handle(gm_graph *g) {
     (void)hipDeviceSynchronize();
     (void)hipGetLastError();
   });
-  HIP_TRY(dev_malloc(&g->d_counters, 64));
+  HIP_TRY(g->d_counters.alloc(64));
   HIP_TRY(hipMemset(g->d_counters, 0, 64));
   for (auto &pr : g->ev)
     for (auto &e : pr) HIP_TRY(hipEventCreate(&e));
@@ -416,7 +367,7 @@ static int adopt_offsets(gm_graph *g, const int64_t *d_rp64) {
   long long big_from = 0x7fffffffLL;
   if (const char *e = gm_opt("GM_BIG_NE")) big_from = std::max(0ll, atoll(e));  // (tests: the 64-bit paths on small graphs)
   if (g->ne >= big_from) {  // a big handle: its own copy of the 64-bit offsets
-    HIP_TRY(dev_malloc(&g->d_rp64, sizeof(long long) * ((size_t)g->nv + 1)));
+    HIP_TRY(g->d_rp64.alloc(sizeof(long long) * ((size_t)g->nv + 1)));
     HIP_TRY(hipMemcpy(g->d_rp64, d_rp64, sizeof(long long) * ((size_t)g->nv + 1), hipMemcpyDeviceToDevice));
     hipLaunchKernelGGL(check_offsets64_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, (const long long *)g->d_rp64, g->nv, g->ne, info.p);
     HIP_TRY(hipGetLastError());
@@ -427,7 +378,7 @@ static int adopt_offsets(gm_graph *g, const int64_t *d_rp64) {
     g->max_deg = h[1];
     return GM_OK;
   }
-  HIP_TRY(dev_malloc(&g->d_rp, sizeof(int) * ((size_t)g->nv + 1)));
+  HIP_TRY(g->d_rp.alloc(sizeof(int) * ((size_t)g->nv + 1)));
   hipLaunchKernelGGL(convert_offsets_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, (const long long *)d_rp64, g->nv, g->ne, g->d_rp, info.p);
   HIP_TRY(hipGetLastError());  // (a failed launch would leave info == 0 and an uninitialised d_rp behind a passing validation)
   int h[2] = {0, 0};
@@ -479,7 +430,8 @@ extern "C" int gm_graph_upload(const gm_csr *h, int device, gm_graph **out) {
     if (rc) return fail(rc);
   }
   hipError_t e;
-  if ((e = dev_malloc(&g->d_col, sizeof(int) * (size_t)std::max<long long>(g->ne, 1))) != hipSuccess) return fail(hip_fail(e, "hipMalloc(col)", __FILE__, __LINE__));
+  if ((e = g->d_col_mem.alloc(sizeof(int) * (size_t)std::max<long long>(g->ne, 1))) != hipSuccess) return fail(hip_fail(e, "hipMalloc(col)", __FILE__, __LINE__));
+  g->d_col = g->d_col_mem;
   if (g->ne > 0 && (e = hipMemcpy(g->d_col, h->col_idx, sizeof(int) * (size_t)g->ne, hipMemcpyHostToDevice)) != hipSuccess) return fail(hip_fail(e, "hipMemcpy(col)", __FILE__, __LINE__));
   rc = finish_handle(g);
   if (rc) return fail(rc);
@@ -498,8 +450,7 @@ extern "C" int gm_graph_from_device(int32_t nv, int64_t ne, const int64_t *d_row
   g->device = device;
   g->nv = nv;
   g->ne = ne;
-  g->own_col = false;
-  g->d_col = const_cast<int *>(d_col_idx);
+  g->d_col = const_cast<int *>(d_col_idx);  // borrowed: d_col_mem stays empty
   auto fail = [&](int code) { gm_graph_free(g); return code; };
   rc = adopt_offsets(g, d_row_ptr);
   if (rc) return fail(rc);
@@ -530,9 +481,9 @@ extern "C" int gm_graph_sort_neighbors(gm_graph *g) {
   size_t bytes = 0;
   int bits = 1;
   while (bits < 31 && (1ll << bits) < (long long)g->nv) ++bits;
-  HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, bytes, g->d_col, sorted.p, (int)g->ne, g->nv, g->d_rp, g->d_rp + 1, 0, bits));
+  HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, bytes, g->d_col, sorted.p, (int)g->ne, g->nv, g->d_rp.get(), g->d_rp + 1, 0, bits));
   HIP_TRY(tmp.reserve(bytes));
-  HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.buf.p, bytes, g->d_col, sorted.p, (int)g->ne, g->nv, g->d_rp, g->d_rp + 1, 0, bits));
+  HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.buf.p, bytes, g->d_col, sorted.p, (int)g->ne, g->nv, g->d_rp.get(), g->d_rp + 1, 0, bits));
   HIP_TRY(hipMemcpy(g->d_col, sorted.p, sizeof(int) * (size_t)g->ne, hipMemcpyDeviceToDevice));
   HIP_TRY(hipDeviceSynchronize());
   g->sorted_state = 0;  // (checked again by the first solver: duplicates are still not "strictly ascending")
@@ -778,9 +729,8 @@ static int orient_impl(const gm_graph *sym, const OffT *rp_in, gm_graph **out) {
   ScanTemp tmp;
   // the symmetric degrees first: the passes compare (degree, id) of both endpoints of every entry; the oriented handle keeps them (what
   // the topological renumbering of this DAG sorts by -- get_relabeled mode 2)
-  int *sdeg = nullptr;
-  HIP_TRY(dev_malloc(&sdeg, sizeof(int) * (size_t)std::max(nv, 1)));
-  struct SdegGuard { int *&p; ~SdegGuard() { if (p) dev_free(p); } } sdeg_guard{sdeg};
+  DevOwn<int> sdeg;
+  HIP_TRY(sdeg.alloc(sizeof(int) * (size_t)std::max(nv, 1)));
   if (nv > 0) hipLaunchKernelGGL((symdeg_kernel<OffT>), dim3(vb), dim3(256), 0, 0, nv, rp_in, sdeg);
   // segment table of the long rows (device): counts -> exclusive scan -> fill
   DevBuf<int> nseg_of, seg_first, deg, segcnt;
@@ -815,7 +765,7 @@ static int orient_impl(const gm_graph *sym, const OffT *rp_in, gm_graph **out) {
   g->nv = nv;
   auto fail = [&](int code) { gm_graph_free(g); return code; };
   hipError_t e;
-  if ((e = dev_malloc(&g->d_rp, sizeof(int) * ((size_t)nv + 1))) != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__));
+  if ((e = g->d_rp.alloc(sizeof(int) * ((size_t)nv + 1))) != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__));
   if constexpr (sizeof(OffT) == 8) {
     // the oriented graph of a symmetric graph of >= 2^31 entries: half of them -- checked in 64 bits before the offsets are narrowed
     DevBuf<long long> rp64;
@@ -829,7 +779,7 @@ static int orient_impl(const gm_graph *sym, const OffT *rp_in, gm_graph **out) {
     }
     hipLaunchKernelGGL(narrow_offsets_kernel, dim3(vb), dim3(256), 0, 0, nv, rp64.p, g->d_rp);
   } else {
-    if ((e = dev_exclusive_sum(tmp, deg.p, g->d_rp, (size_t)nv + 1)) != hipSuccess) return fail(hip_fail(e, "ExclusiveSum", __FILE__, __LINE__));
+    if ((e = dev_exclusive_sum(tmp, deg.p, g->d_rp.get(), (size_t)nv + 1)) != hipSuccess) return fail(hip_fail(e, "ExclusiveSum", __FILE__, __LINE__));
   }
   DevBuf<int> md;
   if ((e = md.alloc(1)) != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__));
@@ -840,7 +790,8 @@ static int orient_impl(const gm_graph *sym, const OffT *rp_in, gm_graph **out) {
   if ((e = hipMemcpy(&max_deg, md.p, sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) return fail(hip_fail(e, "hipMemcpy", __FILE__, __LINE__));
   g->ne = ne_new;
   g->max_deg = max_deg;
-  if ((e = dev_malloc(&g->d_col, sizeof(int) * (size_t)std::max(ne_new, 1))) != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__));
+  if ((e = g->d_col_mem.alloc(sizeof(int) * (size_t)std::max(ne_new, 1))) != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__));
+  g->d_col = g->d_col_mem;
   setup_trace("orient: scan, max degree, allocations");
   // pass 1: compact
   if (nseg) hipLaunchKernelGGL((orient_segout_kernel<OffT>), dim3(vb), dim3(256), 0, 0, nv, rp_in, seg_first.p, segcnt.p, g->d_rp, segs.p);
@@ -856,8 +807,7 @@ static int orient_impl(const gm_graph *sym, const OffT *rp_in, gm_graph **out) {
   setup_trace("orient: compact");
   int rc = finish_handle(g);
   if (rc) { gm_graph_free(g); return rc; }
-  g->d_symdeg = sdeg;
-  sdeg = nullptr;
+  g->d_symdeg = std::move(sdeg);
   setup_trace("orient: finish_handle + degrees");
   g->setup.orient_ms = timer.ms();
   *out = g;
@@ -1286,9 +1236,10 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
   r->ne = ne;
   auto fail = [&](hipError_t e, const char *what) { gm_graph_free(r); return hip_fail(e, what, __FILE__, __LINE__); };
   hipError_t e;
-  if ((e = dev_malloc(&r->d_rp, sizeof(int) * nv1)) != hipSuccess) return fail(e, "hipMalloc(rp)");
-  if ((e = dev_malloc(&r->d_col, sizeof(int) * n1)) != hipSuccess) return fail(e, "hipMalloc(col)");
-  if ((e = dev_exclusive_sum(tmp, newdeg.p, r->d_rp, nv1)) != hipSuccess) return fail(e, "ExclusiveSum");
+  if ((e = r->d_rp.alloc(sizeof(int) * nv1)) != hipSuccess) return fail(e, "hipMalloc(rp)");
+  if ((e = r->d_col_mem.alloc(sizeof(int) * n1)) != hipSuccess) return fail(e, "hipMalloc(col)");
+  r->d_col = r->d_col_mem;
+  if ((e = dev_exclusive_sum(tmp, newdeg.p, r->d_rp.get(), nv1)) != hipSuccess) return fail(e, "ExclusiveSum");
   // rows of at most kRelabelLdsMax entries are sorted inside the kernels that write them (rank / bitonic network in LDS): no key per
   // entry, no device-wide sort; the few rows beyond that -- the hubs of a symmetric graph -- through one segmented radix sort of their
   // segments (GM_RELABEL_GLOBAL_SORT=1: round 3's 64-bit keys + radix sort of every entry)
@@ -1367,7 +1318,7 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
       return GM_OK;
     }
   }
-  if (mode == 2) r->d_newid = newid.release();
+  if (mode == 2) r->d_newid.take(newid);
   std::lock_guard<std::mutex> lk(g->mu);
   g->relabel_cache[mode] = r;
   g->setup.relabel_ms += timer.ms();

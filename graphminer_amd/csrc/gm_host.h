@@ -12,6 +12,7 @@
 // instead of per-GPU COO copies, and the multi-GPU split is index arithmetic on chunk ids.
 #pragma once
 #include "../../include/graphminer_amd.h"
+#include "gm_devown.h"
 #include "gm_mine.h"
 #include "gm_setops.h"
 
@@ -44,7 +45,7 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
 // synchronises the device: round 2 measured ~10 ms of allocation overhead per table. What does not fit the pool
 // falls through to hipMalloc (and tells the pool how much to ask for next time).
 struct TempPool {
-  char *base = nullptr;
+  DevOwn<char> base;
   size_t cap = 0, off = 0, want = 0;  // want: bytes the open scopes would have liked (pool + fall-through allocations)
   // A handle family (a graph + its cached orientation and renumbered copies) shares the root's pool, and two threads may work on two
   // members at once under their own handle locks.  The pool belongs to ONE thread at a time: the first PoolScope claims it,
@@ -69,12 +70,10 @@ constexpr size_t kBigCacheMinBytes = (size_t)4 << 20;
 // EVERY device allocation of the library goes through here: hipMalloc, and when the device is out of memory the cached
 // temporaries of this device go back to the driver and the request is made once more -- the cache may park up to its budget of memory
 // that nothing else can reach, and a setup path must not fail (or quietly drop an optimisation) while it does.
-hipError_t dev_malloc_bytes(void **p, size_t bytes);
-void dev_free(void *p);           // the counterpart: a block of >= kBigCacheMinBytes goes to the device's cache, anything else to hipFree
+// dev_malloc_bytes, and dev_free, the counterpart: a block of >= kBigCacheMinBytes goes to the device's cache, anything else to hipFree
+// (declared in gm_devown.h, with DevOwn<T>, the owner of every persistent array)
 void dev_handle_born(int device);  // (gm_graph.hip: the cache lives as long as the device has a handle)
 bool dev_handle_died(int device);
-template <class T>
-inline hipError_t dev_malloc(T **p, size_t bytes) { return dev_malloc_bytes(reinterpret_cast<void **>(p), bytes); }
 
 template <class T>
 struct DevBuf {  // RAII device array; pooled when a PoolScope is open and the pool has room
@@ -95,7 +94,7 @@ struct DevBuf {  // RAII device array; pooled when a PoolScope is open and the p
     pooled = false;
     block_bytes = 0;
   }
-  // keep = true: the array outlives the scope (release() hands it to a long-lived owner): never from the pool
+  // keep = true: the array outlives the scope (DevOwn::take hands it to a long-lived owner): never from the pool
   hipError_t alloc(size_t count, bool keep = false) {
     drop();
     n = count;
@@ -111,7 +110,7 @@ struct DevBuf {  // RAII device array; pooled when a PoolScope is open and the p
       }
     }
     if (!keep && bytes >= kBigCacheMinBytes) return big_cache_get(reinterpret_cast<void **>(&p), bytes, &block_bytes);
-    return dev_malloc(&p, bytes);
+    return dev_malloc_bytes(reinterpret_cast<void **>(&p), bytes);
   }
   // (a pooled array cannot be handed on: alloc(..., true); a cached block can -- it is an allocation of its own, only larger than asked for)
   T *release() { T *q = pooled ? nullptr : p; p = nullptr; n = 0; pooled = false; block_bytes = 0; return q; }
@@ -170,7 +169,7 @@ struct RowFilter {
 // the in-process rank-share tests of rounds 2 - 4 shared one handle and could not see it).
 struct ShareOrder {
   int world = 1, rank = 0, policy = 0, which = -1;  // which: the dequeue order it was cut from (-1: plain record order)
-  int *d = nullptr;
+  DevOwn<int> d;
   long long n = 0;
   unsigned long long edges = 0;  // task edges of the share
 };
@@ -184,16 +183,18 @@ struct ChunkTable {
   RowFilter rf;                     // the rows the table covers
   int bitmap_min_deg = 0;           // rows longer than this got dense bitmaps (allow_split tables)
   std::vector<unsigned long long> cost;  // estimated work per chunk (after cutting)
-  ChunkRec *d = nullptr;
+  DevOwn<ChunkRec> d;
   size_t n = 0;
-  int *d_slot = nullptr;                 // per chunk: hub bitmap slot or -1
-  int *d_row_slot = nullptr;             // per vertex: bitmap slot or -1
+  DevOwn<int> d_slot;                    // per chunk: hub bitmap slot or -1
   // dequeue orders of the round-robin policy: [0] chunks well above the mean cost first (heaviest first), the rest in vertex
   // order (single rank); [1] all chunks by estimated cost, descending (rank r of n owns every n-th entry)
-  int *d_order[2] = {nullptr, nullptr};
+  DevOwn<int> d_order[2];
   std::vector<int> order[2];
-  bool own_bitmaps = true;               // false: d_bitmaps / d_row_slot belong to a BitmapSet of the graph (shared by its tables)
+  // the views every reader uses; the arrays are a BitmapSet's of the graph (shared by its tables) or, built by the table itself, its own
   unsigned *d_bitmaps = nullptr;         // n_bitmaps x bitmap_words
+  int *d_row_slot = nullptr;             // per vertex: bitmap slot or -1
+  DevOwn<unsigned> d_bitmaps_mem;        // (empty when borrowed)
+  DevOwn<int> d_row_slot_mem;
   size_t n_bitmaps = 0;
   unsigned long long bitmap_words = 0;
   unsigned long long max_bit_words = 0;  // largest nel*stride over chunks that exceed bit_words
@@ -206,8 +207,8 @@ struct ChunkTable {
   bool host_ready = false;
   unsigned long long total_edges = 0, total_cost = 0;
   size_t n_with_cost = 0;  // chunks of non-zero cost (device-built tables): they are the first n_with_cost entries of d_order[1]
-  int *d_edges = nullptr, *d_firstv = nullptr;  // device twins of the host views (device-built tables)
-  unsigned long long *d_cost = nullptr;
+  DevOwn<int> d_edges, d_firstv;  // device twins of the host views (device-built tables)
+  DevOwn<unsigned long long> d_cost;
   std::list<ShareOrder> shares;  // the shares handed out so far (get_share_order)
 };
 int table_host_views(gm_graph *g, ChunkTable *t);  // gm_tables.hip
@@ -224,16 +225,16 @@ struct CliqueRound {
   size_t w0 = 0, w1 = 0;                    // wide slots [w0, w1) of the plan's vertex list
   size_t mcls_begin[4] = {0, 0, 0, 0};      // ... per class of the matrix-core count kernel (gm_cmma.hip), in d_mcls_slots
   unsigned long long words = 0;             // arena words of the round
-  unsigned long long *d_base = nullptr;     // per vertex: word offset of its matrix (nv + 1; non-owners are empty)
-  gm::CBuildTask *d_tasks = nullptr;
+  DevOwn<unsigned long long> d_base;        // per vertex: word offset of its matrix (nv + 1; non-owners are empty)
+  DevOwn<gm::CBuildTask> d_tasks;
   size_t n_tasks = 0;
-  int *d_trp = nullptr;                     // task-list offsets per host vertex (nv + 1)
+  DevOwn<int> d_trp;                        // task-list offsets per host vertex (nv + 1)
   ChunkTable host_tab;                      // chunks of host vertices (rows that fit the stage), costs from the task lists
   // the blocked gather of the wide rows (gm_cgather.hip cgatherb_kernel): the (vertex, block of core rows) units of this round's wide
   // slots sorted by block, cut into work items of about equal probe counts
-  uint4 *d_gunits = nullptr;
-  unsigned *d_gtab = nullptr;              // the column tables of the round's slots (16-bit positions, two tiles per dword)
-  int2 *d_gitems = nullptr;
+  DevOwn<uint4> d_gunits;
+  DevOwn<unsigned> d_gtab;                 // the column tables of the round's slots (16-bit positions, two tiles per dword)
+  DevOwn<int2> d_gitems;
   size_t n_gunits = 0, n_gitems = 0;
   unsigned long long gather_table_bytes = 0;  // records + row positions + table dwords the units read by construction (tooling: gm_clique4_gather_info)
 };
@@ -245,10 +246,10 @@ struct CliquePlan {
   long long n_first = 0, n_step = 1, n_count = 0;  // this rank's share of it: positions first + i * step of the dequeue order
   const int *d_order = nullptr;
   std::vector<int> verts;            // this rank's wide vertices; slot = index here (longest rows first)
-  int *d_verts = nullptr;
-  unsigned long long *d_slot_base = nullptr;  // slot -> word offset of its matrix inside its round's arena
-  int *d_mcls_slots = nullptr;
-  int4 *d_mcls_rec = nullptr;        // per entry of d_mcls_slots: {d+, word offset of the matrix (low, high), 0} (gm_cmma.hip)
+  DevOwn<int> d_verts;
+  DevOwn<unsigned long long> d_slot_base;  // slot -> word offset of its matrix inside its round's arena
+  DevOwn<int> d_mcls_slots;
+  DevOwn<int4> d_mcls_rec;           // per entry of d_mcls_slots: {d+, word offset of the matrix (low, high), 0} (gm_cmma.hip)
   int core_base = -1;                // >= 0: the rows of the wide vertices' matrices whose first endpoint is >= core_base are gathered from the
                                      // core bitmap of the graph (gm_cgather.hip); the task lists of the streamed build leave them out
   std::vector<CliqueRound> rounds;
@@ -261,8 +262,8 @@ struct CliquePlan {
 struct BitmapSet {
   int min_deg = 0;
   RowFilter rf;
-  unsigned *d_bitmaps = nullptr;
-  int *d_row_slot = nullptr;
+  DevOwn<unsigned> d_bitmaps;
+  DevOwn<int> d_row_slot;
   size_t n = 0;
   unsigned long long words = 0;
 };
@@ -272,56 +273,57 @@ struct gm_graph {
   int nv = 0;
   long long ne = 0;
   int max_deg = 0;
-  int *d_rp = nullptr;   // int32 offsets, owned
-  long long *d_rp64 = nullptr;  // a BIG handle (ne >= 2^31): 64-bit offsets instead -- orientation, formula 3-motif and download only
-  int *d_col = nullptr;  // col_idx
-  bool own_col = true;
-  int *d_symdeg = nullptr;  // a DAG made by gm_graph_orient: the degrees of the symmetric graph it came from (its topological numbering sorts by them)
-  int2 *d_edesc = nullptr;  // per CSR entry: {rp[col[e]], degree(col[e])}, built on first use (ensure_edesc)
-  int *d_trp = nullptr;     // task lists of the shorter-list-streams triangle count (ensure_tasklists): row offsets (nv + 1)
-  int2 *d_tdesc = nullptr;  // ... and per task {rp[partner], d(partner)}
-  int *d_tedge = nullptr;   // ... and (edge supports only: ensure_tasklists(g, true)) the task's own DAG entry
+  DevOwn<int> d_rp;   // int32 offsets, owned
+  DevOwn<long long> d_rp64;  // a BIG handle (ne >= 2^31): 64-bit offsets instead -- orientation, formula 3-motif and download only
+  int *d_col = nullptr;  // col_idx: the view every reader uses -- d_col_mem's array, or the caller's (gm_graph_from_device: borrowed)
+  DevOwn<int> d_col_mem;
+  DevOwn<int> d_symdeg;  // a DAG made by gm_graph_orient: the degrees of the symmetric graph it came from (its topological numbering sorts by them)
+  DevOwn<int2> d_edesc;  // per CSR entry: {rp[col[e]], degree(col[e])}, built on first use (ensure_edesc)
+  DevOwn<int> d_trp;     // task lists of the shorter-list-streams triangle count (ensure_tasklists): row offsets (nv + 1)
+  int2 *d_tdesc = nullptr;  // ... and per task {rp[partner], d(partner)}: the view of d_tdesc_mem that ensure_tasklists publishes, read without the lock
+  DevOwn<int2> d_tdesc_mem;
+  DevOwn<int> d_tedge;   // ... and (edge supports only: ensure_tasklists(g, true)) the task's own DAG entry
   // ... and TASK-MAJOR COPIES of the short lists (ensure_tasklists): d_colk = col followed by the keys of every list of <= GM_TC_INLINE_MAX
   // entries in task order, d_tdesck = the descriptors pointing at the copies.  Consecutive tasks of a host then stream consecutive
   // lines instead of one random 64-byte line (or two) each: what bounds the triangle count on LiveJournal-shaped graphs (mean list 9)
-  int *d_colk = nullptr;
-  int2 *d_tdesck = nullptr;
+  DevOwn<int> d_colk;
+  DevOwn<int2> d_tdesck;
   unsigned long long n_inline_keys = 0;
   // nv <= 2^24: instead of descriptors that point at the copies, the copies ARE the task list of the short lists -- a key stream in host
   // order, every key tagged with its host's low 8 bits (GraphView::kst), offsets per host vertex, and the longer lists as their own
   // task lists (d_trpl / d_tdescl).  No descriptor, no row search, no flattening for the short lists: one coalesced load per 64 keys.
-  unsigned *d_kst = nullptr;  // the stream itself (ensure_keystream, gm_tables.hip)
+  DevOwn<unsigned> d_kst;  // the stream itself (ensure_keystream, gm_tables.hip)
   int kst_state = 0;          // 2: this handle cannot have one (ids beyond 24 bits, GM_TC_NO_KEY_STREAM)
   int n_long_tasks = 0;
-  int *d_kst_rp = nullptr;
-  int *d_trpl = nullptr;
-  int2 *d_tdescl = nullptr;
+  DevOwn<int> d_kst_rp;
+  DevOwn<int> d_trpl;
+  DevOwn<int2> d_tdescl;
   // the same for the edge supports (ensure_keystream(g, true)): per key the DAG entry it was copied from and the entry of its task's own
   // edge, per longer list the entry of its task's own edge.  They belong to d_kst / d_tdescl when the stream was built with them, else to
   // a second set d_kst2 / d_tdescl2 (same offsets, its own order of arrival).
-  int2 *d_kst_et = nullptr;  // per key: {entry it was copied from, entry of its task's own edge}
-  int *d_tedgel = nullptr;
-  unsigned *d_kst2 = nullptr;
-  int2 *d_tdescl2 = nullptr;
+  DevOwn<int2> d_kst_et;  // per key: {entry it was copied from, entry of its task's own edge}
+  DevOwn<int> d_tedgel;
+  DevOwn<unsigned> d_kst2;
+  DevOwn<int2> d_tdescl2;
   int kst_lmax = 0;  // the limit of a "short" list the stream was built with
   // the rows beyond the stage of the task-list kernels (> 2048 entries; ensure_long_rows): ids and the prefix of their lengths
-  int *d_long_rows = nullptr;
-  long long *d_long_prefix = nullptr;
+  DevOwn<int> d_long_rows;
+  DevOwn<long long> d_long_prefix;
   int n_long_rows = -1;               // -1: not looked for yet
   long long long_edges = 0;
-  unsigned *d_sup = nullptr;  // edge supports: one counter per DAG entry (gm_sup.hip)
+  DevOwn<unsigned> d_sup;  // edge supports: one counter per DAG entry (gm_sup.hip)
   // the 5-vertex closed forms (gm_wtri.hip, gm_sgl5_raw): a support array of their own (the diamond's d_sup is not touched), d(u) + d(v) per
   // entry, the symmetric degrees (built once), 2 T_v per vertex, and the eight sums of one call
-  unsigned *d_w5sup = nullptr, *d_w5ed = nullptr;
-  int *d_w5deg = nullptr;
-  unsigned long long *d_w5tv2 = nullptr, *d_w5out = nullptr;
+  DevOwn<unsigned> d_w5sup, d_w5ed;
+  DevOwn<int> d_w5deg;
+  DevOwn<unsigned long long> d_w5tv2, d_w5out;
   bool w5_tri = false, w5_vert = false;  // what the PAT_WTRI launch in flight was asked for (gm_sgl5_raw)
   // the 6-vertex closed forms (gm_wrect.hip, gm_sgl6_raw).  On the DAG of the 5-vertex pass: e1 per vertex.  On the graph the weighted
   // 4-cycle kernel walks (the copy numbered ascending in degree, or the handle itself): its plan, built once -- ids per range
   // (GM_WRECT_RANGE), ranges per bit of the row masks, the masks, the task list
-  unsigned *d_s6e1 = nullptr;
-  unsigned long long *d_wrect_mask = nullptr;
-  int2 *d_wrect_tasks = nullptr;
+  DevOwn<unsigned> d_s6e1;
+  DevOwn<unsigned long long> d_wrect_mask;
+  DevOwn<int2> d_wrect_tasks;
   unsigned long long n_wrect_tasks = 0;
   int wrect_range = 0, wrect_grp = 1;
   bool wrect_ready = false;
@@ -329,33 +331,33 @@ struct gm_graph {
   // the DAG the triangle pass runs on has a support array of the local counts' own (d_sup and d_w5sup are not touched); the SYMMETRIC
   // handle holds what lives in the caller's entry order: the supports / peeling state, the reverse-entry index (built once), the marks,
   // the frontier list, the trussness, and the counters of a round
-  int *d_newid = nullptr;       // the topological copy made by get_relabeled (mode 2): id in the graph it was made from -> id here (nv)
-  unsigned *d_lsup = nullptr;   // per DAG entry (diamond_support_entries)
-  unsigned *d_lent = nullptr;   // per entry of the symmetric graph: the support of its edge; while peeling, exact at the canonical entries
-  int *d_lrev = nullptr;        // per entry (u, v): the entry (v, u)
+  DevOwn<int> d_newid;       // the topological copy made by get_relabeled (mode 2): id in the graph it was made from -> id here (nv)
+  DevOwn<unsigned> d_lsup;   // per DAG entry (diamond_support_entries)
+  DevOwn<unsigned> d_lent;   // per entry of the symmetric graph: the support of its edge; while peeling, exact at the canonical entries
+  DevOwn<int> d_lrev;        // per entry (u, v): the entry (v, u)
   bool lrev_ready = false;
-  unsigned char *d_lmark = nullptr;
-  int *d_lfront = nullptr;      // ne / 2 + 1 canonical entries
-  unsigned *d_ltruss = nullptr;
-  unsigned *d_lcnt = nullptr;   // 64 bytes: [0] frontier size, [1] 0xFFFFFFFF - smallest alive support
+  DevOwn<unsigned char> d_lmark;
+  DevOwn<int> d_lfront;      // ne / 2 + 1 canonical entries
+  DevOwn<unsigned> d_ltruss;
+  DevOwn<unsigned> d_lcnt;   // 64 bytes: [0] frontier size, [1] 0xFFFFFFFF - smallest alive support
   // triangle listing (gm_list.hip, gm_tc_list), on the SYMMETRIC handle: the first slot of every batch of 64 entries of the oriented copy
   // (batches + 1 values, the last one T), counted and scanned by the first call and kept for the windows that follow
-  unsigned long long *d_list_off = nullptr;
+  DevOwn<unsigned long long> d_list_off;
   unsigned long long list_total = 0;
   bool list_ready = false;
   // ... and the MATCH MASKS of the in-edge tasks with long tails (ensure_sup_masks, gm_tables.hip): per DAG entry / per task the offset of
   // the task's mask in the arena (64-bit words; kNoMask: the task keeps its atomics), the arena itself (written and read by every launch)
-  unsigned *d_emoff = nullptr, *d_tmoff = nullptr;
-  unsigned long long *d_smask = nullptr;
+  DevOwn<unsigned> d_emoff, d_tmoff;
+  DevOwn<unsigned long long> d_smask;
   unsigned long long smask_words = 0;
-  int *d_sup_far_rows = nullptr;  // the rows with tails of more than 64 keys (masks of several words), widest ids first
+  DevOwn<int> d_sup_far_rows;  // the rows with tails of more than 64 keys (masks of several words), widest ids first
   int n_sup_far_rows = 0;
   int smask_min_tail = 0;  // (0: kSupMaskMinTail)
   int smask_state = 0;  // 0 unknown, 1 built, 2 not applicable (DAG not topological, arena beyond 2^32 words, GM_SUP_NO_MASKS)
   std::vector<int> h_rp;  // host copy of the offsets, fetched on first use (host_rp): download, k-clique tables, SgL renumbering
   std::list<ChunkTable> tables;  // list: handed-out pointers stay valid
-  unsigned long long *d_counters = nullptr;  // [4] + queue word, 64 B
-  unsigned *d_scratch = nullptr;
+  DevOwn<unsigned long long> d_counters;  // [4] + queue word, 64 B
+  DevOwn<unsigned> d_scratch;
   size_t scratch_bytes = 0;
   static constexpr int kEvRing = 64;  // HIP-event pairs of the most recent launches
   hipEvent_t ev[kEvRing][4] = {};      // [0], [1]: around the launch; [2], [3]: around its hub-corner kernel (gm_ctc.hip) when it has one
@@ -372,63 +374,63 @@ struct gm_graph {
   bool topo_relabel_failed = false;  // the (degree, id) numbering is not topological for this DAG: it runs as given
   const gm_graph *ring_alias = nullptr;
   const gm_graph *ring_extra[2] = {nullptr, nullptr};  // 4-motif: the handles that ran the other sub-launches of the most recent calls (gm_kernel_times adds them)
-  int *d_idx0 = nullptr;                  // rectangle: #neighbours below v, and the wedge-block prefix
-  unsigned long long *d_wblock_prefix = nullptr;
+  DevOwn<int> d_idx0;                  // rectangle: #neighbours below v, and the wedge-block prefix
+  DevOwn<unsigned long long> d_wblock_prefix;
   unsigned long long n_wblocks = 0;
-  int4 *d_rect_tasks = nullptr;          // rectangle by wedge accumulation: task list, counter maps
+  DevOwn<int4> d_rect_tasks;          // rectangle by wedge accumulation: task list, counter maps
   unsigned long long n_rect_tasks = 0;
   // rectangle with the heavy centres' counter maps in LDS (round 6, gm_mine.hip rect_lds_kernel): row bounds per range boundary, the
   // (centre, range) tasks, and rect_acc_kernel's list with the centres that keep only their ends below `rect_cut` first
-  int *d_rect_bnd = nullptr;
-  int2 *d_rect_lds_tasks = nullptr;
-  int4 *d_rect_cut_tasks = nullptr;
+  DevOwn<int> d_rect_bnd;
+  DevOwn<int2> d_rect_lds_tasks;
+  DevOwn<int4> d_rect_cut_tasks;
   unsigned long long n_rect_lds_tasks = 0, n_rect_cut_tasks = 0, n_rect_cut = 0;
   int rect_cut = 0;
   gm::RectLdsRanges rect_ranges;
   bool rect_lds_ready = false;
-  unsigned *d_rect_acc = nullptr;
+  DevOwn<unsigned> d_rect_acc;
   size_t rect_acc_bytes = 0;
-  unsigned *d_house_t = nullptr;         // house by wedge accumulation: per-entry tables, task list, 64-bit maps
-  unsigned *d_house_tlt = nullptr;
-  int4 *d_house_tasks = nullptr;
+  DevOwn<unsigned> d_house_t;         // house by wedge accumulation: per-entry tables, task list, 64-bit maps
+  DevOwn<unsigned> d_house_tlt;
+  DevOwn<int4> d_house_tasks;
   unsigned long long n_house_tasks = 0;
-  unsigned long long *d_house_acc = nullptr;
+  DevOwn<unsigned long long> d_house_acc;
   size_t house_acc_bytes = 0;
-  int *d_house_touched = nullptr;
+  DevOwn<int> d_house_touched;
   // house with the heavy centres' maps in LDS (round 6, gm_mine.hip house_lds_kernel): as for the rectangle
-  int *d_house_bnd = nullptr;
-  int2 *d_house_lds_tasks = nullptr;
-  int4 *d_house_cut_tasks = nullptr;
+  DevOwn<int> d_house_bnd;
+  DevOwn<int2> d_house_lds_tasks;
+  DevOwn<int4> d_house_cut_tasks;
   unsigned long long n_house_lds_tasks = 0, n_house_cut_tasks = 0, n_house_cut = 0;
   gm::HouseLdsRanges house_ranges;
   bool house_lds_ready = false;
-  int *d_pent_touched = nullptr;         // pentagon by wedge accumulation: touched-vertex lists (same shape as d_rect_acc)
+  DevOwn<int> d_pent_touched;         // pentagon by wedge accumulation: touched-vertex lists (same shape as d_rect_acc)
   size_t pent_touched_bytes = 0;
-  unsigned long long *d_house_prefix = nullptr;  // house: per-entry task-block prefix
+  DevOwn<unsigned long long> d_house_prefix;  // house: per-entry task-block prefix
   unsigned long long n_house_blocks = 0;   // handle whose event ring holds this handle's most recent launch
   unsigned long long sum_c2 = 0;          // sum_v C(d(v),2)
   bool sum_c2_valid = false;
   // k-clique: the wide DAG vertices (clique_is_wide), longest rows first, and the per-(rank, world, policy) plans of their two
   // phases (row-group chunks of phase 1, count classes of phase 2, matrix offsets, arena rounds)
   std::list<BitmapSet> bitmap_sets;
-  int *d_wide_sorted = nullptr;
+  DevOwn<int> d_wide_sorted;
   size_t n_wide = 0;
   bool wide_valid = false;
   std::list<CliquePlan> clique_plans;
-  unsigned *d_wide_mat = nullptr;      // matrix arena (largest round so far)
+  DevOwn<unsigned> d_wide_mat;      // matrix arena (largest round so far)
   size_t wide_mat_bytes = 0;
-  unsigned *d_wide_queue = nullptr;    // dequeue words of the wide launches of one call (zeroed per call)
+  DevOwn<unsigned> d_wide_queue;    // dequeue words of the wide launches of one call (zeroed per call)
   // k-clique on a topologically numbered DAG: dense adjacency bitmap of its LAST core_h vertices (the hubs, when the numbering is by
   // degree) -- row v - core_base holds bit w - core_base for every edge v -> w; the rows of the wide vertices' matrices whose first
   // endpoint lies in this core are GATHERED from it (gm_cgather.hip) instead of being built by streamed intersections
-  unsigned *d_core = nullptr;
+  DevOwn<unsigned> d_core;
   int core_h = 0, core_base = 0;       // core_h = 0: not built / not applicable (ensure_core_bitmap)
   int core_state = 0;                  // 0 unknown, 1 built, 2 not applicable
   // ... and the same bits cut into BLOCKS of consecutive rows for the blocked gather (gm_cgather.hip cgatherb_kernel; ensure_core_tri)
-  unsigned *d_cg_tri = nullptr;        // block images: of every core row the words from its diagonal word on
-  int *d_cg_rowbase = nullptr;         // per core row: offset inside its block's image - first stored word
-  int *d_cg_bid = nullptr;             // per core row: its block
-  int4 *d_cg_blk = nullptr;            // per block: {first row, rows, image offset, image words}
+  DevOwn<unsigned> d_cg_tri;        // block images: of every core row the words from its diagonal word on
+  DevOwn<int> d_cg_rowbase;         // per core row: offset inside its block's image - first stored word
+  DevOwn<int> d_cg_bid;             // per core row: its block
+  DevOwn<int4> d_cg_blk;            // per block: {first row, rows, image offset, image words}
   int n_cg_blocks = 0;
   int cg_tri_state = 0;                // 0 unknown, 1 built, 2 not applicable (no core bitmap, no room)
   // triangle count: the out-edges of the last tc_core_h vertices are counted on the matrix cores from the corner of d_core (gm_ctc.hip) and
@@ -444,8 +446,8 @@ struct gm_graph {
   // IB * nb + JB of d_tc_pair_bits is set, and the product walks d_tc_pair_tasks (CoreTcParams::tasks).  tc_core_h / kst_skip_from /
   // tc_core_edges keep describing the base corner the density rule names (gm_tc_core_info).  tc_pair_region = 0: no selection
   int tc_pair_region = 0, tc_pair_from = 0x7fffffff;
-  unsigned *d_tc_pair_bits = nullptr;
-  unsigned *d_tc_pair_tasks = nullptr;
+  DevOwn<unsigned> d_tc_pair_bits;
+  DevOwn<unsigned> d_tc_pair_tasks;
   int n_tc_pair_tasks = 0;
   long long tc_pair_info[6] = {0, 0, 0, 0, 0, 0};  // gm_tc_pairs_info
   // the same for the TASK LISTS (ensure_tasklists: the edge supports, the triangle count without a key stream): no task of a row >= tl_skip_from;
@@ -453,8 +455,8 @@ struct gm_graph {
   // of the word's first entry inside its row (ensure_sup_corner, gm_tables.hip; core_tc_block_kernel<true>, gm_ctc.hip)
   int tl_core_h = 0;
   int tl_skip_from = 0x7fffffff;
-  unsigned *d_csym = nullptr;
-  unsigned short *d_cfirst = nullptr;
+  DevOwn<unsigned> d_csym;
+  DevOwn<unsigned short> d_cfirst;
   hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr};  // class kernels that cannot fill the chip run beside the others (run_pattern)
   hipEvent_t aux_done[3] = {nullptr, nullptr, nullptr};
   TempPool pool;  // temporaries of the setup paths (PoolScope)
@@ -493,7 +495,7 @@ struct PoolScope {
     }
     if (!pl.base && !gm_opt("GM_NO_TEMP_POOL")) {
       const size_t need = std::min<size_t>((size_t)256 << 20, (size_t)24 * ((size_t)g->nv + 1) + ((size_t)16 << 20));
-      if (dev_malloc(&pl.base, need) == hipSuccess) pl.cap = need;
+      if (pl.base.alloc(need) == hipSuccess) pl.cap = need;
       else (void)hipGetLastError();  // (no pool: everything falls through to hipMalloc)
     }
     mark = pl.off;
@@ -596,7 +598,6 @@ int graph_rows_sorted(gm_graph *g, bool *out);
 int ensure_long_rows(gm_graph *g);  // (gm_tables.hip) d_long_rows / d_long_prefix: the rows of more than kTctStageMax entries
 int ensure_core_tri(gm_graph *g);     // (gm_tables.hip) d_cg_* of a handle with a core bitmap; GM_OK also when not applicable
 int ensure_core_bitmap(gm_graph *g);  // (gm_tables.hip) d_core / core_h / core_base of a topologically numbered DAG; GM_OK also when not applicable
-void free_tables(gm_graph *g);                                   // gm_tables.hip
 int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned long long part_cap, int stage_cap, ChunkTable **out,
               const RowFilter &rf = RowFilter(), int bitmap_min_deg = kBitmapMinDeg);
 int ensure_edesc(gm_graph *g);
@@ -610,6 +611,5 @@ int ensure_tri_per_edge(gm_graph *g);  // (gm_launch.hip) |N+(u) ^ N+(v)| averag
 unsigned long long task_part_cap(gm_graph *g, int world);
 int clique_wide_min_words();
 int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, unsigned long long part_cap, CliquePlan **out);
-void free_clique_plans(gm_graph *g);
 int run_pattern(gm::Pattern pat, const gm_graph *cg, const gm_launch *la, int k, uint64_t *h_out, int nout, gm_stats *st, int fin_mode = -1,
                 unsigned long long fin_base = 0, unsigned *sup_out = nullptr);  // gm_launch.hip (sup_out: PAT_SUPPORT_PART's buffer)

@@ -56,13 +56,13 @@ __global__ __launch_bounds__(256) void giant_edges_kernel(int nv, const int *__r
 static int giant_task_edges(gm_graph *g, unsigned long long *out) {
   if (g->giant_edges == ~0ull) {
     HIP_TRY(hipSetDevice(g->device));
-    unsigned long long *d_s = nullptr, s = 0;
-    HIP_TRY(dev_malloc(&d_s, 8));
+    DevOwn<unsigned long long> d_s;
+    unsigned long long s = 0;
+    HIP_TRY(d_s.alloc(8));
     hipError_t e = hipMemset(d_s, 0, 8);
     if (e == hipSuccess && g->nv > 0)
       hipLaunchKernelGGL(giant_edges_kernel, dim3((unsigned)std::min<long long>(((long long)g->nv + 255) / 256, 2048)), dim3(256), 0, 0, g->nv, g->d_rp, d_s);
     if (e == hipSuccess) e = hipMemcpy(&s, d_s, 8, hipMemcpyDeviceToHost);
-    dev_free(d_s);
     if (e != hipSuccess) return hip_fail(e, "giant_edges_kernel", __FILE__, __LINE__);
     g->giant_edges = s;
   }
@@ -170,16 +170,14 @@ static inline int grid_for(long long count, int cu_count, long long per_cu) { re
 
 // a device buffer of a handle, grown to `need` bytes (never shrunk; the old contents are not kept)
 template <class T>
-static int grow_dev(T **buf, size_t *bytes, size_t need) {
+static int grow_dev(DevOwn<T> &buf, size_t *bytes, size_t need) {
   if (need <= *bytes) return GM_OK;
-  if (*buf) dev_free(*buf);
-  *buf = nullptr;
   *bytes = 0;
-  HIP_TRY(dev_malloc(buf, need));
+  HIP_TRY(buf.alloc(need));
   *bytes = need;
   return GM_OK;
 }
-static int ensure_scratch(gm_graph *g, size_t need) { return grow_dev(&g->d_scratch, &g->scratch_bytes, need); }
+static int ensure_scratch(gm_graph *g, size_t need) { return grow_dev(g->d_scratch, &g->scratch_bytes, need); }
 
 // this rank's share of n units (gm_partition) as the first / step / count of a kernel's parameters; returns the count
 template <class P>
@@ -228,6 +226,9 @@ struct PatternRun {
   unsigned long long my_edges = 0;  // task edges of this rank's shares (gm_stats.tasks)
   uint64_t chunks_total = 0;        // chunks of this rank's shares (gm_stats.chunks)
   bool joined[3] = {false, false, false};  // class kernels on a side stream that the launch stream has yet to wait for
+#ifdef GM_DEBUG_CHUNKS
+  DevOwn<unsigned long long> debug_ticks;  // what p.chunk_ticks points at
+#endif
 };
 
 // which path the launch takes and the chunk tables it needs (pl.pat / support / sup_part are set by the caller)
@@ -312,7 +313,7 @@ static int plan_pattern(const LaunchCtx &c, PatternPlan &pl) {
       if (const int rc_t = ensure_tasklists(g, pl.support)) return rc_t;
     }
   }
-  if (pl.support && !pl.sup_part && !pl.wtri && !g->d_sup) HIP_TRY(dev_malloc(&g->d_sup, sizeof(unsigned) * (size_t)std::max<long long>(g->ne, 1)));
+  if (pl.support && !pl.sup_part && !pl.wtri && !g->d_sup) HIP_TRY(g->d_sup.alloc(sizeof(unsigned) * (size_t)std::max<long long>(g->ne, 1)));
   // match masks instead of one atomic per streamed edge (gm_sup.hip): one GPU, the task lists, a topologically numbered DAG
   // (tune[6] & GM_T6_SUP_ATOMICS: A/B switch, every streamed edge by an atomic)
   if (pl.support && !pl.sup_part && !pl.wtri && world == 1 && pl.use_tct && !pl.use_kst && !(la->tune[6] & GM_T6_SUP_ATOMICS)) {
@@ -598,10 +599,9 @@ static int prepare_scratch(PatternRun &r, int k) {
 // diagnostics: wall_clock64 ticks per dequeue position of the main table, dumped after the launch
 static int debug_chunks_begin(PatternRun &r) {
   ChunkTable *tab = r.pl.tab;
-  unsigned long long *d_ticks = nullptr;
-  HIP_TRY(dev_malloc(&d_ticks, sizeof(unsigned long long) * std::max<size_t>(tab->n, 1)));
-  HIP_TRY(hipMemset(d_ticks, 0, sizeof(unsigned long long) * std::max<size_t>(tab->n, 1)));
-  r.p.chunk_ticks = d_ticks;
+  HIP_TRY(r.debug_ticks.alloc(sizeof(unsigned long long) * std::max<size_t>(tab->n, 1)));
+  HIP_TRY(hipMemset(r.debug_ticks, 0, sizeof(unsigned long long) * std::max<size_t>(tab->n, 1)));
+  r.p.chunk_ticks = r.debug_ticks;
   return GM_OK;
 }
 static int debug_chunks_dump(PatternRun &run) {
@@ -614,7 +614,7 @@ static int debug_chunks_dump(PatternRun &run) {
   HIP_TRY(hipStreamSynchronize(stream));
   std::vector<unsigned long long> ticks(tab->n);
   HIP_TRY(hipMemcpy(ticks.data(), d_ticks, sizeof(unsigned long long) * tab->n, hipMemcpyDeviceToHost));
-  dev_free(d_ticks);
+  run.debug_ticks.reset();
   std::vector<ChunkRec> recs(tab->n);
   HIP_TRY(hipMemcpy(recs.data(), tab->d, sizeof(ChunkRec) * tab->n, hipMemcpyDeviceToHost));
   if (int rcv = table_host_views(g, tab)) return rcv;
@@ -1146,13 +1146,13 @@ __global__ __launch_bounds__(256) void sum_sq_deg_kernel(int nv, const int *__re
 int ensure_mean_sq_deg(gm_graph *self) {
   if (self->mean_sq_deg < 0) {
     HIP_TRY(hipSetDevice(self->device));
-    unsigned long long *d_s = nullptr, s2 = 0;
-    HIP_TRY(dev_malloc(&d_s, 8));
+    DevOwn<unsigned long long> d_s;
+    unsigned long long s2 = 0;
+    HIP_TRY(d_s.alloc(8));
     hipError_t e = hipMemset(d_s, 0, 8);
     if (e == hipSuccess && self->nv > 0)
       hipLaunchKernelGGL(sum_sq_deg_kernel, dim3((unsigned)std::min<long long>(((long long)self->nv + 255) / 256, 2048)), dim3(256), 0, 0, self->nv, self->d_rp, d_s);
     if (e == hipSuccess) e = hipMemcpy(&s2, d_s, 8, hipMemcpyDeviceToHost);
-    dev_free(d_s);
     if (e != hipSuccess) return hip_fail(e, "sum_sq_deg_kernel", __FILE__, __LINE__);
     self->mean_sq_deg = self->ne > 0 ? (double)s2 / (double)self->ne : 0.0;
   }
@@ -1192,14 +1192,14 @@ int ensure_tri_per_edge(gm_graph *self) {
     HIP_TRY(hipSetDevice(self->device));
     const int nsamples = (int)std::min<long long>(1 << 16, std::max<long long>(self->ne, 1));
     const long long stride = std::max<long long>(1, self->ne / nsamples);
-    unsigned long long *d_s = nullptr, s = 0;
-    HIP_TRY(dev_malloc(&d_s, 8));
+    DevOwn<unsigned long long> d_s;
+    unsigned long long s = 0;
+    HIP_TRY(d_s.alloc(8));
     hipError_t e = hipMemset(d_s, 0, 8);
     if (e == hipSuccess && self->ne > 0)
       hipLaunchKernelGGL(tri_sample_kernel, dim3((unsigned)((nsamples + 255) / 256)), dim3(256), 0, 0, self->nv, (long long)self->ne, self->d_rp, self->d_col, stride,
                          nsamples, d_s);
     if (e == hipSuccess) e = hipMemcpy(&s, d_s, 8, hipMemcpyDeviceToHost);
-    dev_free(d_s);
     if (e != hipSuccess) return hip_fail(e, "tri_sample_kernel", __FILE__, __LINE__);
     self->tri_per_edge = (double)s / (double)nsamples;
   }
@@ -1294,13 +1294,13 @@ static void emit_centre_tasks(const std::vector<int> &vs, const std::vector<unsi
 // ... every centre with work, by its 2-path estimate (work_launch: the kernel that writes it per centre), as one task list on the device
 // (the form with every end in the global maps)
 template <class WorkLaunch>
-static int build_centre_tasks(size_t nv, WorkLaunch work_launch, const char *what, int4 **d_tasks, unsigned long long *n_tasks) {
-  unsigned long long *d_work = nullptr;
-  HIP_TRY(dev_malloc(&d_work, sizeof(unsigned long long) * std::max<size_t>(nv, 1)));
+static int build_centre_tasks(size_t nv, WorkLaunch work_launch, const char *what, DevOwn<int4> &d_tasks, unsigned long long *n_tasks) {
+  DevOwn<unsigned long long> d_work;
+  HIP_TRY(d_work.alloc(sizeof(unsigned long long) * std::max<size_t>(nv, 1)));
   std::vector<unsigned long long> work(std::max<size_t>(nv, 1));
   hipError_t e = nv ? work_launch(d_work) : hipSuccess;
   if (e == hipSuccess) e = hipMemcpy(work.data(), d_work, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost);
-  dev_free(d_work);
+  d_work.reset();
   if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
   std::vector<int> vs;
   vs.reserve(nv);
@@ -1309,9 +1309,11 @@ static int build_centre_tasks(size_t nv, WorkLaunch work_launch, const char *wha
   std::stable_sort(vs.begin(), vs.end(), [&](int a, int b) { return work[(size_t)a] > work[(size_t)b]; });
   std::vector<int4> tasks;
   emit_centre_tasks(vs, work, tasks);
+  DevOwn<int4> d;
+  HIP_TRY(d.alloc(sizeof(int4) * std::max<size_t>(tasks.size(), 1)));
+  if (!tasks.empty()) HIP_TRY(hipMemcpy(d, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice));
   *n_tasks = tasks.size();
-  HIP_TRY(dev_malloc(d_tasks, sizeof(int4) * std::max<size_t>(tasks.size(), 1)));
-  if (!tasks.empty()) HIP_TRY(hipMemcpy(*d_tasks, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice));
+  d_tasks = std::move(d);  // (the list is what says "built": handed over whole)
   return GM_OK;
 }
 
@@ -1319,8 +1321,10 @@ static int build_centre_tasks(size_t nv, WorkLaunch work_launch, const char *wha
 static int ensure_idx0(gm_graph *g, const GraphView &gv) {
   if (g->d_idx0) return GM_OK;
   OtherSetupScope scope(g);
-  HIP_TRY(dev_malloc(&g->d_idx0, sizeof(int) * (size_t)std::max(g->nv, 1)));
-  HIP_TRY(launch_idx0(gv, g->d_idx0, 0));
+  DevOwn<int> idx0;
+  HIP_TRY(idx0.alloc(sizeof(int) * (size_t)std::max(g->nv, 1)));
+  HIP_TRY(launch_idx0(gv, idx0, 0));
+  g->d_idx0 = std::move(idx0);
   return GM_OK;
 }
 
@@ -1346,8 +1350,10 @@ static int run_rect_flat(const gm_graph *cg, const gm_launch *la_in, uint64_t *h
     }
     pre[g->nv] = acc;
     g->n_wblocks = acc;
-    HIP_TRY(dev_malloc(&g->d_wblock_prefix, sizeof(unsigned long long) * ((size_t)g->nv + 1)));
-    HIP_TRY(hipMemcpy(g->d_wblock_prefix, pre.data(), sizeof(unsigned long long) * ((size_t)g->nv + 1), hipMemcpyHostToDevice));
+    DevOwn<unsigned long long> d_pre;
+    HIP_TRY(d_pre.alloc(sizeof(unsigned long long) * ((size_t)g->nv + 1)));
+    HIP_TRY(hipMemcpy(d_pre, pre.data(), sizeof(unsigned long long) * ((size_t)g->nv + 1), hipMemcpyHostToDevice));
+    g->d_wblock_prefix = std::move(d_pre);
   }
   RectParams p;
   memset(&p, 0, sizeof p);
@@ -1382,7 +1388,7 @@ static int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_
   const bool lds_maps = !pentagon && !(la->tune[6] & GM_T6_GLOBAL_MAPS);
   if (!g->d_rect_tasks && !lds_maps) {  // once per graph: 2-path estimate per centre (device), task list (host): heavy first, then light by 4
     OtherSetupScope scope(g);
-    const int rc_t = build_centre_tasks((size_t)g->nv, [&](unsigned long long *d_work) { return launch_rect_work(gv, g->d_idx0, d_work, 0); }, "rect_work_kernel", &g->d_rect_tasks, &g->n_rect_tasks);
+    const int rc_t = build_centre_tasks((size_t)g->nv, [&](unsigned long long *d_work) { return launch_rect_work(gv, g->d_idx0, d_work, 0); }, "rect_work_kernel", g->d_rect_tasks, &g->n_rect_tasks);
     if (rc_t) return rc_t;
   }
   // rectangle: the 2-path ends in the last kRectLdsRanges * kRectLdsRange ids of the centres with >= GM_RECT_LDS_MIN 2-paths are counted in
@@ -1403,12 +1409,11 @@ static int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_
       const int nblk = (int)((nv + kRectLdsWords - 1) / kRectLdsWords);
       std::vector<int> bmax((size_t)std::max(nblk, 1), 0);
       if (nv) {
-        int *d_bmax = nullptr;
-        HIP_TRY(dev_malloc(&d_bmax, sizeof(int) * (size_t)nblk));
+        DevOwn<int> d_bmax;
+        HIP_TRY(d_bmax.alloc(sizeof(int) * (size_t)nblk));
         hipError_t e0 = hipMemset(d_bmax, 0, sizeof(int) * (size_t)nblk);
         if (e0 == hipSuccess) e0 = launch_rect_blockmax(gv, d_bmax, 0);
         if (e0 == hipSuccess) e0 = hipMemcpy(bmax.data(), d_bmax, sizeof(int) * (size_t)nblk, hipMemcpyDeviceToHost);
-        dev_free(d_bmax);
         if (e0 != hipSuccess) return hip_fail(e0, "rect_blockmax_kernel", __FILE__, __LINE__);
       }
       auto max_deg_of_blocks = [&](int b0, int nb) {  // blocks b0 .. b0 + nb - 1 (counted from the top), those that exist
@@ -1436,9 +1441,9 @@ static int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_
     }
     setup_trace("rect: ranges");
     g->rect_cut = rr.rb[0];
-    HIP_TRY(dev_malloc(&g->d_rect_bnd, sizeof(int) * (size_t)(rr.n + 1) * std::max<size_t>(nv, 1)));
-    unsigned long long *d_work = nullptr;
-    HIP_TRY(dev_malloc(&d_work, sizeof(unsigned long long) * 2 * std::max<size_t>(nv, 1)));
+    HIP_TRY(g->d_rect_bnd.alloc(sizeof(int) * (size_t)(rr.n + 1) * std::max<size_t>(nv, 1)));
+    DevOwn<unsigned long long> d_work;
+    HIP_TRY(d_work.alloc(sizeof(unsigned long long) * 2 * std::max<size_t>(nv, 1)));
     std::vector<unsigned long long> work(std::max<size_t>(nv, 1)), wcut(std::max<size_t>(nv, 1));
     hipError_t e = hipSuccess;
     if (nv) {
@@ -1447,7 +1452,7 @@ static int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_
       if (e == hipSuccess) e = hipMemcpy(work.data(), d_work, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost);
       if (e == hipSuccess) e = hipMemcpy(wcut.data(), d_work + nv, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost);
     }
-    dev_free(d_work);
+    d_work.reset();
     if (e != hipSuccess) return hip_fail(e, "rect_bounds_kernel", __FILE__, __LINE__);
     setup_trace("rect: bounds + work estimates");
     std::vector<int> lds, rest;
@@ -1488,9 +1493,9 @@ static int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_
     emit_centre_tasks(rest, work, tasks);
     g->n_rect_cut_tasks = tasks.size();
     g->n_rect_lds_tasks = lt.size();
-    HIP_TRY(dev_malloc(&g->d_rect_cut_tasks, sizeof(int4) * std::max<size_t>(tasks.size(), 1)));
+    HIP_TRY(g->d_rect_cut_tasks.alloc(sizeof(int4) * std::max<size_t>(tasks.size(), 1)));
     if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_rect_cut_tasks, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice));
-    HIP_TRY(dev_malloc(&g->d_rect_lds_tasks, sizeof(int2) * std::max<size_t>(lt.size(), 1)));
+    HIP_TRY(g->d_rect_lds_tasks.alloc(sizeof(int2) * std::max<size_t>(lt.size(), 1)));
     if (!lt.empty()) HIP_TRY(hipMemcpy(g->d_rect_lds_tasks, lt.data(), sizeof(int2) * lt.size(), hipMemcpyHostToDevice));
     g->rect_lds_ready = true;
     setup_trace("rect: task lists");
@@ -1523,12 +1528,12 @@ static int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_
   grid = clamp_grid(count, grid);
   const size_t need = (size_t)per_wg * (size_t)grid;
   if (need > g->rect_acc_bytes) {
-    if (int rc_a = grow_dev(&g->d_rect_acc, &g->rect_acc_bytes, need)) return rc_a;
+    if (int rc_a = grow_dev(g->d_rect_acc, &g->rect_acc_bytes, need)) return rc_a;
     HIP_TRY(hipMemset(g->d_rect_acc, 0, need));  // every launch leaves the maps zeroed again
   }
   p.acc = g->d_rect_acc;
   // touched-vertex lists: same shape as the maps (one int list of up to nv entries per wave)
-  if (int rc_t = grow_dev(&g->d_pent_touched, &g->pent_touched_bytes, need)) return rc_t;
+  if (int rc_t = grow_dev(g->d_pent_touched, &g->pent_touched_bytes, need)) return rc_t;
   p.touched = g->d_pent_touched;
   setup_trace("rect: global maps");
   if (pentagon) {
@@ -1593,8 +1598,8 @@ static int ensure_edge_tables(gm_graph *g, const GraphView &gv) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemset(g->d_counters, 0, kCounterBlockBytes));  // (the table kernel used the dequeue head)
   }
-  g->d_house_t = t.release();  // (published only after the build kernel has succeeded; the buffers free themselves on the error paths)
-  g->d_house_tlt = tlt.release();
+  g->d_house_t.take(t);  // (published only after the build kernel has succeeded; the buffers free themselves on the error paths)
+  g->d_house_tlt.take(tlt);
   return GM_OK;
 }
 
@@ -1625,9 +1630,9 @@ static int run_house_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h
     rr.n = (int)std::min<long long>(std::min<long long>(max_ranges, by_memory), ((long long)g->nv + kHouseLdsIds - 1) / kHouseLdsIds);
     rr.nv = g->nv;
     rr.cut = (int)std::max<long long>(0, (long long)g->nv - (long long)rr.n * kHouseLdsIds);
-    HIP_TRY(dev_malloc(&g->d_house_bnd, sizeof(int) * (size_t)(rr.n + 1) * std::max<size_t>(nv, 1)));
-    unsigned long long *d_work = nullptr;
-    HIP_TRY(dev_malloc(&d_work, sizeof(unsigned long long) * 2 * std::max<size_t>(nv, 1)));
+    HIP_TRY(g->d_house_bnd.alloc(sizeof(int) * (size_t)(rr.n + 1) * std::max<size_t>(nv, 1)));
+    DevOwn<unsigned long long> d_work;
+    HIP_TRY(d_work.alloc(sizeof(unsigned long long) * 2 * std::max<size_t>(nv, 1)));
     std::vector<unsigned long long> work(std::max<size_t>(nv, 1)), wcut(std::max<size_t>(nv, 1));
     std::vector<int> rph(nv + 1, 0);
     hipError_t e = hipSuccess;
@@ -1638,7 +1643,7 @@ static int run_house_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h
       if (e == hipSuccess) e = hipMemcpy(wcut.data(), d_work + nv, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost);
       if (e == hipSuccess) e = hipMemcpy(rph.data(), g->d_rp, sizeof(int) * (nv + 1), hipMemcpyDeviceToHost);
     }
-    dev_free(d_work);
+    d_work.reset();
     if (e != hipSuccess) return hip_fail(e, "house_bounds_kernel", __FILE__, __LINE__);
     // A centre with at most one neighbour per thread is ONE task that walks every range -- two per walk -- at ~2.5 us of a CU per walk
     // whatever it finds there, against ~12 ns per 2-path in the global maps (both measured on R-MAT-20): it pays from ~200 2-paths per
@@ -1681,15 +1686,15 @@ static int run_house_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h
     emit_centre_tasks(rest, work, tasks);
     g->n_house_cut_tasks = tasks.size();
     g->n_house_lds_tasks = lt.size();
-    HIP_TRY(dev_malloc(&g->d_house_cut_tasks, sizeof(int4) * std::max<size_t>(tasks.size(), 1)));
+    HIP_TRY(g->d_house_cut_tasks.alloc(sizeof(int4) * std::max<size_t>(tasks.size(), 1)));
     if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_house_cut_tasks, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice));
-    HIP_TRY(dev_malloc(&g->d_house_lds_tasks, sizeof(int2) * std::max<size_t>(lt.size(), 1)));
+    HIP_TRY(g->d_house_lds_tasks.alloc(sizeof(int2) * std::max<size_t>(lt.size(), 1)));
     if (!lt.empty()) HIP_TRY(hipMemcpy(g->d_house_lds_tasks, lt.data(), sizeof(int2) * lt.size(), hipMemcpyHostToDevice));
     g->house_lds_ready = true;
   }
   if (!g->d_house_tasks && !lds_maps) {  // once per graph
     OtherSetupScope scope(g);
-    const int rc_t = build_centre_tasks((size_t)g->nv, [&](unsigned long long *d_work) { return launch_house_work(gv, d_work, 0); }, "house_work_kernel", &g->d_house_tasks, &g->n_house_tasks);
+    const int rc_t = build_centre_tasks((size_t)g->nv, [&](unsigned long long *d_work) { return launch_house_work(gv, d_work, 0); }, "house_work_kernel", g->d_house_tasks, &g->n_house_tasks);
     if (rc_t) return rc_t;
   }
   HouseAccParams p;
@@ -1716,14 +1721,10 @@ static int run_house_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h
   grid = clamp_grid(count, grid);
   const size_t need = (size_t)per_wg * (size_t)grid;
   if (need > g->house_acc_bytes) {
-    if (g->d_house_acc) dev_free(g->d_house_acc);
-    g->d_house_acc = nullptr;
     g->house_acc_bytes = 0;
-    HIP_TRY(dev_malloc(&g->d_house_acc, need));
+    HIP_TRY(g->d_house_acc.alloc(need));
     HIP_TRY(hipMemset(g->d_house_acc, 0, need));  // every launch leaves the maps zeroed again
-    if (g->d_house_touched) dev_free(g->d_house_touched);
-    g->d_house_touched = nullptr;
-    HIP_TRY(dev_malloc(&g->d_house_touched, need / 2));  // one int list per map
+    HIP_TRY(g->d_house_touched.alloc(need / 2));  // one int list per map
     g->house_acc_bytes = need;
   }
   p.acc = g->d_house_acc;
@@ -1759,20 +1760,22 @@ static int run_house_flat(const gm_graph *cg, const gm_launch *la_in, uint64_t *
   if (!g->d_house_prefix) {  // once per graph: blocks per entry on the device, prefix on the host
     OtherSetupScope scope(g);
     const size_t ne = (size_t)g->ne;
-    unsigned *d_nblk = nullptr;
-    HIP_TRY(dev_malloc(&d_nblk, sizeof(unsigned) * std::max<size_t>(ne, 1)));
+    DevOwn<unsigned> d_nblk;
+    HIP_TRY(d_nblk.alloc(sizeof(unsigned) * std::max<size_t>(ne, 1)));
     std::vector<unsigned> nblk(std::max<size_t>(ne, 1));
     hipError_t e = ne ? launch_house_blocks(gv, d_nblk, 0) : hipSuccess;
     if (e == hipSuccess) e = hipMemcpy(nblk.data(), d_nblk, sizeof(unsigned) * ne, hipMemcpyDeviceToHost);
-    dev_free(d_nblk);
+    d_nblk.reset();
     if (e != hipSuccess) return hip_fail(e, "house block table", __FILE__, __LINE__);
     std::vector<unsigned long long> pre(ne + 1);
     unsigned long long acc = 0;
     for (size_t i = 0; i < ne; ++i) { pre[i] = acc; acc += nblk[i]; }
     pre[ne] = acc;
     g->n_house_blocks = acc;
-    HIP_TRY(dev_malloc(&g->d_house_prefix, sizeof(unsigned long long) * (ne + 1)));
-    HIP_TRY(hipMemcpy(g->d_house_prefix, pre.data(), sizeof(unsigned long long) * (ne + 1), hipMemcpyHostToDevice));
+    DevOwn<unsigned long long> d_pre;
+    HIP_TRY(d_pre.alloc(sizeof(unsigned long long) * (ne + 1)));
+    HIP_TRY(hipMemcpy(d_pre, pre.data(), sizeof(unsigned long long) * (ne + 1), hipMemcpyHostToDevice));
+    g->d_house_prefix = std::move(d_pre);
   }
   HouseParams p;
   memset(&p, 0, sizeof p);
@@ -1813,7 +1816,7 @@ static int run_sgl_nested(int pat, const gm_graph *cg, const gm_launch *la_in, u
     const size_t need = (size_t)grid * 4 * (size_t)p.max_deg * sizeof(int);
     rc = ensure_scratch(g, need);
     if (rc) return rc;
-    p.scratch = reinterpret_cast<int *>(g->d_scratch);
+    p.scratch = reinterpret_cast<int *>(g->d_scratch.get());
   }
   if (int rc_t = start_timer(ctx)) return rc_t;
   if (count > 0) HIP_TRY(launch_sgl_nested(pat, p, grid, ctx.stream));
@@ -2001,15 +2004,15 @@ static int ensure_w5_buffers(gm_graph *g) {
   if (g->d_w5out) return GM_OK;
   HIP_TRY(hipSetDevice(g->device));
   const size_t ne = (size_t)std::max<long long>(g->ne, 1), nv = (size_t)std::max(g->nv, 1);
-  if (!g->d_w5sup) HIP_TRY(dev_malloc(&g->d_w5sup, sizeof(unsigned) * (size_t)diamond_support_entries(g->ne, 1)));
-  if (!g->d_w5ed) HIP_TRY(dev_malloc(&g->d_w5ed, sizeof(unsigned) * ne));
-  if (!g->d_w5tv2) HIP_TRY(dev_malloc(&g->d_w5tv2, sizeof(unsigned long long) * nv));
+  if (!g->d_w5sup) HIP_TRY(g->d_w5sup.alloc(sizeof(unsigned) * (size_t)diamond_support_entries(g->ne, 1)));
+  if (!g->d_w5ed) HIP_TRY(g->d_w5ed.alloc(sizeof(unsigned) * ne));
+  if (!g->d_w5tv2) HIP_TRY(g->d_w5tv2.alloc(sizeof(unsigned long long) * nv));
   if (!g->d_w5deg) {
-    HIP_TRY(dev_malloc(&g->d_w5deg, sizeof(int) * nv));
+    HIP_TRY(g->d_w5deg.alloc(sizeof(int) * nv));
     HIP_TRY(launch_wtri_degrees(g->nv, g->ne, g->d_rp, g->d_col, g->d_w5deg, g->cu_count, 0));
     HIP_TRY(hipDeviceSynchronize());
   }
-  HIP_TRY(dev_malloc(&g->d_w5out, 64));
+  HIP_TRY(g->d_w5out.alloc(64));
   return GM_OK;
 }
 
@@ -2089,7 +2092,7 @@ static int sgl5_raw_needs(const gm_graph *sym, unsigned needs, const gm_launch *
           ChouseParams cp;
           memset(&cp, 0, sizeof cp);
           cp.nv = g->nv; cp.ne = g->ne; cp.rp = g->d_rp; cp.col = g->d_col;
-          cp.scratch = reinterpret_cast<int *>(g->d_scratch); cp.max_deg = std::max(g->max_deg, 1); cp.out = g->d_counters;
+          cp.scratch = reinterpret_cast<int *>(g->d_scratch.get()); cp.max_deg = std::max(g->max_deg, 1); cp.out = g->d_counters;
           HIP_TRY(launch_chouse(cp, grid, c.stream));
           return (int)GM_OK;
         })) return rc;
@@ -2111,14 +2114,14 @@ static int ensure_local_buffers(gm_graph *g, bool peel, bool truss) {
   std::lock_guard<std::mutex> lk(g->mu);
   HIP_TRY(hipSetDevice(g->device));
   const size_t ne = (size_t)std::max<long long>(g->ne, 1);
-  if (!g->d_lent) HIP_TRY(dev_malloc(&g->d_lent, sizeof(unsigned) * ne));
+  if (!g->d_lent) HIP_TRY(g->d_lent.alloc(sizeof(unsigned) * ne));
   if (peel) {
-    if (!g->d_lrev) HIP_TRY(dev_malloc(&g->d_lrev, sizeof(int) * ne));
-    if (!g->d_lmark) HIP_TRY(dev_malloc(&g->d_lmark, ne));
-    if (!g->d_lfront) HIP_TRY(dev_malloc(&g->d_lfront, sizeof(int) * (ne / 2 + 1)));
-    if (!g->d_lcnt) HIP_TRY(dev_malloc(&g->d_lcnt, 64));
+    if (!g->d_lrev) HIP_TRY(g->d_lrev.alloc(sizeof(int) * ne));
+    if (!g->d_lmark) HIP_TRY(g->d_lmark.alloc(ne));
+    if (!g->d_lfront) HIP_TRY(g->d_lfront.alloc(sizeof(int) * (ne / 2 + 1)));
+    if (!g->d_lcnt) HIP_TRY(g->d_lcnt.alloc(64));
   }
-  if (truss && !g->d_ltruss) HIP_TRY(dev_malloc(&g->d_ltruss, sizeof(unsigned) * ne));
+  if (truss && !g->d_ltruss) HIP_TRY(g->d_ltruss.alloc(sizeof(unsigned) * ne));
   return GM_OK;
 }
 
@@ -2138,7 +2141,7 @@ static int local_supports(gm_graph *g, const gm_launch *l2, double *ms, gm_graph
   if (int rc = diamond_run_on(g, l2, &run_on)) return rc;
   {
     std::lock_guard<std::mutex> lk(run_on->mu);
-    if (!run_on->d_lsup) HIP_TRY(dev_malloc(&run_on->d_lsup, sizeof(unsigned) * (size_t)diamond_support_entries(run_on->ne, 1)));
+    if (!run_on->d_lsup) HIP_TRY(run_on->d_lsup.alloc(sizeof(unsigned) * (size_t)diamond_support_entries(run_on->ne, 1)));
   }
   uint64_t dummy = 0;
   gm_stats s;
@@ -2302,7 +2305,7 @@ extern "C" int gm_tc_list(const gm_graph *sym, const gm_launch *la, uint64_t fir
       const size_t nb = (size_t)((dag->ne + GM_WAVE - 1) / GM_WAVE);
       {
         std::lock_guard<std::mutex> lk(g->mu);
-        if (!g->d_list_off) HIP_TRY(dev_malloc(&g->d_list_off, sizeof(unsigned long long) * (nb + 1)));
+        if (!g->d_list_off) HIP_TRY(g->d_list_off.alloc(sizeof(unsigned long long) * (nb + 1)));
       }
       lp.off = g->d_list_off;
       HIP_TRY(list_count_scan(lp, g->cu_count, ctx.stream));
@@ -2460,7 +2463,7 @@ static int run_wrect(const gm_graph *sym, const gm_launch *la_in, uint64_t out[2
     const long long nranges = std::max<long long>(1, ((long long)g->nv + range - 1) / range);
     g->wrect_range = range;
     g->wrect_grp = (int)((nranges + 63) / 64);
-    HIP_TRY(dev_malloc(&g->d_wrect_mask, sizeof(unsigned long long) * std::max<size_t>(nv, 1)));
+    HIP_TRY(g->d_wrect_mask.alloc(sizeof(unsigned long long) * std::max<size_t>(nv, 1)));
     HIP_TRY(launch_wrect_mask(g->nv, g->d_rp, g->d_col, range, g->wrect_grp, g->d_wrect_mask, g->cu_count, 0));
     std::vector<int> idx0h(std::max<size_t>(nv, 1));
     if (nv) HIP_TRY(hipMemcpy(idx0h.data(), g->d_idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
@@ -2474,7 +2477,7 @@ static int run_wrect(const gm_graph *sym, const gm_launch *la_in, uint64_t out[2
     for (long long v0 = (long long)nv - 1; v0 >= 0; --v0)
       if (idx0h[(size_t)v0] >= 2 && idx0h[(size_t)v0] <= per_wg) tasks.push_back(make_int2((int)v0, -1));
     g->n_wrect_tasks = tasks.size();
-    HIP_TRY(dev_malloc(&g->d_wrect_tasks, sizeof(int2) * std::max<size_t>(tasks.size(), 1)));
+    HIP_TRY(g->d_wrect_tasks.alloc(sizeof(int2) * std::max<size_t>(tasks.size(), 1)));
     if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_wrect_tasks, tasks.data(), sizeof(int2) * tasks.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());
     g->wrect_ready = true;
@@ -2540,7 +2543,7 @@ extern "C" int gm_sgl6_raw(const gm_graph *sym, uint32_t need, const gm_launch *
     if (!run_on->d_w5sup || !run_on->d_w5tv2 || !run_on->d_w5deg) return GM_ERR_INVALID;
     {
       std::lock_guard<std::mutex> lk(run_on->mu);
-      if (!run_on->d_s6e1) HIP_TRY(dev_malloc(&run_on->d_s6e1, sizeof(unsigned) * (size_t)std::max(run_on->nv, 1)));
+      if (!run_on->d_s6e1) HIP_TRY(run_on->d_s6e1.alloc(sizeof(unsigned) * (size_t)std::max(run_on->nv, 1)));
     }
     uint64_t v[4] = {0, 0, 0, 0};
     LaunchCtx ctx;

@@ -5,26 +5,6 @@
 #include "gm_scan.h"
 using namespace gm;
 
-static void free_table(ChunkTable &t) {
-  if (t.d) dev_free(t.d);
-  if (t.d_slot) dev_free(t.d_slot);
-  if (t.d_row_slot && t.own_bitmaps) dev_free(t.d_row_slot);
-  for (int i = 0; i < 2; ++i) if (t.d_order[i]) dev_free(t.d_order[i]);
-  if (t.d_bitmaps && t.own_bitmaps) dev_free(t.d_bitmaps);
-  if (t.d_edges) dev_free(t.d_edges);
-  if (t.d_firstv) dev_free(t.d_firstv);
-  if (t.d_cost) dev_free(t.d_cost);
-  for (auto &sh : t.shares)
-    if (sh.d) dev_free(sh.d);
-  t.shares.clear();
-  t.d_edges = t.d_firstv = nullptr; t.d_cost = nullptr;
-  t.d = nullptr; t.d_slot = nullptr; t.d_row_slot = nullptr; t.d_order[0] = t.d_order[1] = nullptr; t.d_bitmaps = nullptr;
-}
-void free_tables(gm_graph *g) {
-  for (auto &t : g->tables) free_table(t);
-  g->tables.clear();
-}
-
 // ------------------------------------------------------------------------------------------------
 // task chunk tables
 // ------------------------------------------------------------------------------------------------
@@ -351,7 +331,7 @@ static int build_table_device(gm_graph *g, ChunkTable &t, bool sym_table, double
   HIP_TRY(hipMemcpy(&t.max_bit_words, maxbw.p, 8, hipMemcpyDeviceToHost));
   setup_trace("table: walk count + scan");
   t.n = 0;
-  HIP_TRY(dev_malloc(&t.d, sizeof(ChunkRec)));  // (placeholder, replaced below when the table has chunks)
+  HIP_TRY(t.d.alloc(sizeof(ChunkRec)));  // (placeholder, replaced below when the table has chunks)
   if (n0 == 0) {
     t.edge_prefix.assign(1, 0ull);
     t.host_ready = true;
@@ -376,14 +356,12 @@ static int build_table_device(gm_graph *g, ChunkTable &t, bool sym_table, double
   int n = 0;
   HIP_TRY(hipMemcpy(&n, off.p + n0, sizeof(int), hipMemcpyDeviceToHost));
   setup_trace("table: walk emit, cost, parts");
-  dev_free(t.d);
-  t.d = nullptr;
-  HIP_TRY(dev_malloc(&t.d, sizeof(ChunkRec) * (size_t)n));
+  HIP_TRY(t.d.alloc(sizeof(ChunkRec) * (size_t)n));  // (the placeholder goes back first)
   setup_trace("table: free + alloc of the records");
   // per-chunk scalars (cost, task edges, first vertex): they stay on the device, the host takes the two totals (table_host_views: the rest, on demand)
-  HIP_TRY(dev_malloc(&t.d_cost, sizeof(unsigned long long) * (size_t)n));
-  HIP_TRY(dev_malloc(&t.d_edges, sizeof(int) * (size_t)n));
-  HIP_TRY(dev_malloc(&t.d_firstv, sizeof(int) * (size_t)n));
+  HIP_TRY(t.d_cost.alloc(sizeof(unsigned long long) * (size_t)n));
+  HIP_TRY(t.d_edges.alloc(sizeof(int) * (size_t)n));
+  HIP_TRY(t.d_firstv.alloc(sizeof(int) * (size_t)n));
   DevBuf<unsigned long long> totals;
   HIP_TRY(totals.alloc(3));
   HIP_TRY(hipMemsetAsync(totals.p, 0, 24, 0));
@@ -411,12 +389,12 @@ static int build_table_device(gm_graph *g, ChunkTable &t, bool sym_table, double
     hipLaunchKernelGGL(tab_orderkeys_kernel, blocks(n), dim3(256), 0, 0, n, cost_p, heavy, sym_table ? 1 : 0, (!sym_table && g->topo_state == 1) ? 1 : 0,
                        key0.p, key1.p, iota.p);
     for (int m = 0; m < 2; ++m) {
-      HIP_TRY(dev_malloc(&t.d_order[m], sizeof(int) * (size_t)n));
+      HIP_TRY(t.d_order[m].alloc(sizeof(int) * (size_t)n));
       size_t bytes = 0;
       const unsigned long long *keys = m == 0 ? key0.p : key1.p;
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, keys, keyo.p, iota.p, t.d_order[m], n));
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, keys, keyo.p, iota.p, t.d_order[m].get(), n));
       HIP_TRY(tmp.reserve(bytes));
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(tmp.buf.p, bytes, keys, keyo.p, iota.p, t.d_order[m], n));
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(tmp.buf.p, bytes, keys, keyo.p, iota.p, t.d_order[m].get(), n));
     }
   }
   setup_trace("table: dequeue orders");
@@ -474,21 +452,20 @@ static int build_table_device(gm_graph *g, ChunkTable &t, bool sym_table, double
         HIP_TRY(hipMemsetAsync(bitmaps.p, 0, (size_t)nb * (size_t)words * 4, 0));
         hipLaunchKernelGGL(bitmap_build_kernel, dim3((unsigned)nb), dim3(256), 0, 0, g->d_rp, g->d_col, d_rows.p, bitmaps.p, words);
         HIP_TRY(hipDeviceSynchronize());  // (the set is published only after its kernels have succeeded)
-        nb_set.d_bitmaps = bitmaps.release();
-        nb_set.d_row_slot = row_slot.release();
+        nb_set.d_bitmaps.take(bitmaps);
+        nb_set.d_row_slot.take(row_slot);
         nb_set.n = nb;
         nb_set.words = words;
       }
-      g->bitmap_sets.push_back(nb_set);
+      g->bitmap_sets.push_back(std::move(nb_set));
       bs = &g->bitmap_sets.back();
     }
     if (bs->n > 0) {
-      t.own_bitmaps = false;
-      t.d_bitmaps = bs->d_bitmaps;
+      t.d_bitmaps = bs->d_bitmaps;  // (borrowed: the set owns them)
       t.d_row_slot = bs->d_row_slot;
       t.n_bitmaps = bs->n;
       t.bitmap_words = bs->words;
-      HIP_TRY(dev_malloc(&t.d_slot, sizeof(int) * (size_t)n));
+      HIP_TRY(t.d_slot.alloc(sizeof(int) * (size_t)n));
       hipLaunchKernelGGL(tab_chunkslot_kernel, blocks(n), dim3(256), 0, 0, n, t.d, g->d_rp, t.stage_cap, t.d_row_slot, t.d_slot);
     }
     bitmap_ms = bm_timer.ms();
@@ -590,15 +567,12 @@ int get_share_order(gm_graph *g, ChunkTable *t, int world, int rank, int policy,
     HIP_TRY(dev_exclusive_sum(tmp, flag.p, off.p, (size_t)n + 1));
     int cnt = 0;
     HIP_TRY(hipMemcpy(&cnt, off.p + n, sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(dev_malloc(&sh.d, sizeof(int) * (size_t)std::max(cnt, 1)));
+    HIP_TRY(sh.d.alloc(sizeof(int) * (size_t)std::max(cnt, 1)));
     hipLaunchKernelGGL(share_emit_kernel, grid, block, 0, 0, n, order, flag.p, off.p, t->d_edges, sh.d, esum.p);
-    if (hipMemcpy(&sh.edges, esum.p, sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) {
-      dev_free(sh.d);
-      return hip_fail(hipGetLastError(), "share order", __FILE__, __LINE__);
-    }
+    if (hipMemcpy(&sh.edges, esum.p, sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return hip_fail(hipGetLastError(), "share order", __FILE__, __LINE__);
     sh.n = cnt;
   }
-  t->shares.push_back(sh);
+  t->shares.push_back(std::move(sh));
   *out = &t->shares.back();
   g->setup.table_ms += timer.ms();
   return GM_OK;
@@ -626,7 +600,7 @@ int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned
     HIP_TRY(hipSetDevice(g->device));
     PoolScope pool(g);
     int rc = build_table_device(g, t, sym_table, bitmap_ms);
-    if (rc) { free_table(t); return rc; }  // (a partially built table owns device memory: out-of-memory on a large graph must not leak it)
+    if (rc) return rc;  // (what a partially built table owns goes back with `t`)
     if (gm_sweep_env("GM_TABLE_INFO"))
       fprintf(stderr, "[table/device] stage_cap %d rows (%d,%d] skip (%d,%d]: %zu chunks, est. keys %.3e, %zu bitmaps, edges %llu, %.2f ms\n",
               stage_cap, rf.only_lo, rf.only_hi, rf.skip_lo, rf.skip_hi, t.n, (double)t.total_cost, t.n_bitmaps, t.total_edges, timer.ms());
@@ -644,19 +618,17 @@ int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned
   // estimated work per chunk (device), then: cut the heavy ones into parts, and fix the dequeue orders
   std::vector<unsigned long long> cost(recs.size());
   if (!recs.empty()) {
-    ChunkRec *d_tmp = nullptr;
-    unsigned long long *d_cost = nullptr;
-    hipError_t e = dev_malloc(&d_tmp, sizeof(ChunkRec) * recs.size());
-    if (e == hipSuccess) e = dev_malloc(&d_cost, sizeof(unsigned long long) * recs.size());
+    DevOwn<ChunkRec> d_tmp;
+    DevOwn<unsigned long long> d_cost;
+    hipError_t e = d_tmp.alloc(sizeof(ChunkRec) * recs.size());
+    if (e == hipSuccess) e = d_cost.alloc(sizeof(unsigned long long) * recs.size());
     if (e == hipSuccess) e = hipMemcpy(d_tmp, recs.data(), sizeof(ChunkRec) * recs.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(d_cost, 0, sizeof(unsigned long long) * recs.size());
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(chunk_cost_kernel, dim3((unsigned)recs.size()), dim3(256), 0, 0, g->d_rp, g->d_col, d_tmp, d_cost,
+      hipLaunchKernelGGL(chunk_cost_kernel, dim3((unsigned)recs.size()), dim3(256), 0, 0, g->d_rp, g->d_col, d_tmp.get(), d_cost.get(),
                          sym_table ? 1 : 0, kStageCapWide);
       e = hipMemcpy(cost.data(), d_cost, sizeof(unsigned long long) * recs.size(), hipMemcpyDeviceToHost);
     }
-    if (d_tmp) dev_free(d_tmp);
-    if (d_cost) dev_free(d_cost);
     if (e != hipSuccess) return hip_fail(e, "chunk_cost_kernel", __FILE__, __LINE__);
   }
   if ((allow_split || sym_table) && part_cap != 0) {  // (clique chunks are never cut: their second phase needs the whole bit-matrix; part_cap 0: never)
@@ -701,7 +673,7 @@ int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned
   t.total_cost = 0;
   for (auto c : t.cost) t.total_cost += c;
   t.host_ready = true;
-  HIP_TRY(dev_malloc(&t.d, sizeof(ChunkRec) * std::max<size_t>(t.n, 1)));
+  HIP_TRY(t.d.alloc(sizeof(ChunkRec) * std::max<size_t>(t.n, 1)));
   if (t.n) HIP_TRY(hipMemcpy(t.d, recs.data(), sizeof(ChunkRec) * t.n, hipMemcpyHostToDevice));
   if (t.n) {
     // Longest-processing-time-first dequeue order: the dynamic queue then ends on light chunks, so the tail of a launch
@@ -722,7 +694,7 @@ int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned
         if (m == 0) { ca = ca >= heavy ? (classes_only ? 1ull : ca) : 0ull; cb = cb >= heavy ? (classes_only ? 1ull : cb) : 0ull; }
         return ca > cb;
       });
-      HIP_TRY(dev_malloc(&t.d_order[m], sizeof(int) * t.n));
+      HIP_TRY(t.d_order[m].alloc(sizeof(int) * t.n));
       HIP_TRY(hipMemcpy(t.d_order[m], o.data(), sizeof(int) * t.n, hipMemcpyHostToDevice));
     }
   }
@@ -753,22 +725,24 @@ int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned
           if (it != row_slot.end() && it->first == r.u_begin) slots[c] = it->second;
         }
       }
-      HIP_TRY(dev_malloc(&t.d_slot, sizeof(int) * t.n));
+      HIP_TRY(t.d_slot.alloc(sizeof(int) * t.n));
       HIP_TRY(hipMemcpy(t.d_slot, slots.data(), sizeof(int) * t.n, hipMemcpyHostToDevice));
       {
         std::vector<int> by_vertex((size_t)g->nv, -1);
         for (size_t i = 0; i < nb; ++i) by_vertex[(size_t)rows[i]] = (int)i;
-        HIP_TRY(dev_malloc(&t.d_row_slot, sizeof(int) * (size_t)g->nv));
+        HIP_TRY(t.d_row_slot_mem.alloc(sizeof(int) * (size_t)g->nv));
+        t.d_row_slot = t.d_row_slot_mem;
         HIP_TRY(hipMemcpy(t.d_row_slot, by_vertex.data(), sizeof(int) * (size_t)g->nv, hipMemcpyHostToDevice));
       }
-      HIP_TRY(dev_malloc(&t.d_bitmaps, (size_t)nb * (size_t)words * 4));
+      HIP_TRY(t.d_bitmaps_mem.alloc((size_t)nb * (size_t)words * 4));
+      t.d_bitmaps = t.d_bitmaps_mem;
       HIP_TRY(hipMemset(t.d_bitmaps, 0, (size_t)nb * (size_t)words * 4));
-      int *d_rows = nullptr;
-      HIP_TRY(dev_malloc(&d_rows, sizeof(int) * nb));
+      DevOwn<int> d_rows;
+      HIP_TRY(d_rows.alloc(sizeof(int) * nb));
       HIP_TRY(hipMemcpy(d_rows, rows.data(), sizeof(int) * nb, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(bitmap_build_kernel, dim3((unsigned)nb), dim3(256), 0, 0, g->d_rp, g->d_col, d_rows, t.d_bitmaps, words);
+      hipLaunchKernelGGL(bitmap_build_kernel, dim3((unsigned)nb), dim3(256), 0, 0, g->d_rp, g->d_col, d_rows.get(), t.d_bitmaps, words);
       hipError_t e = hipDeviceSynchronize();
-      dev_free(d_rows);
+      d_rows.reset();
       if (e != hipSuccess) return hip_fail(e, "bitmap_build_kernel", __FILE__, __LINE__);
       t.n_bitmaps = nb;
       t.bitmap_words = words;
@@ -835,35 +809,31 @@ static void build_inline_copies(gm_graph *g, ScanTemp &tmp) {
   if (const char *e = gm_sweep_env("GM_TC_INLINE_MAX")) lmax = atoi(e);  // (sweeps; 0: no copies)
   if (lmax <= 0 || g->ne <= 0 || g->d_tdesc == nullptr) return;
   const long long nt = g->ne;
-  unsigned long long *off = nullptr;  // (lengths in, offsets out: the scan runs in place)
-  int *colk = nullptr;
-  int2 *tdk = nullptr;
-  auto fail = [&]() {
-    (void)hipGetLastError();
-    for (void *p : {(void *)off, (void *)colk, (void *)tdk})
-      if (p) dev_free(p);
-  };
-  if (dev_malloc(&off, 8 * (size_t)(nt + 1)) != hipSuccess) return fail();
+  DevOwn<unsigned long long> off;  // (lengths in, offsets out: the scan runs in place)
+  DevOwn<int> colk;
+  DevOwn<int2> tdk;
+  auto fail = [] { (void)hipGetLastError(); };
+  if (off.alloc(8 * (size_t)(nt + 1)) != hipSuccess) return fail();
   const long long blocks = std::min<long long>((nt + 256) / 256, (long long)g->cu_count * 32);
   unsigned long long total = 0;
   for (;;) {  // the copies share the 32-bit index space of col[]: halve the limit until they fit
-    hipLaunchKernelGGL(inl_len_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, nt, g->d_tdesc, lmax, off);
-    if (dev_exclusive_sum(tmp, off, off, (size_t)nt + 1) != hipSuccess) return fail();
+    hipLaunchKernelGGL(inl_len_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, nt, g->d_tdesc, lmax, off.get());
+    if (dev_exclusive_sum(tmp, off.get(), off.get(), (size_t)nt + 1) != hipSuccess) return fail();
     if (hipMemcpy(&total, off + nt, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail();
     if ((unsigned long long)nt + total < 0x7fffff00ull) break;
     lmax >>= 1;
     if (lmax < 4) return fail();
   }
   if (total == 0) return fail();
-  if (dev_malloc(&tdk, sizeof(int2) * (size_t)nt) != hipSuccess) return fail();
-  if (dev_malloc(&colk, 4 * ((size_t)nt + (size_t)total)) != hipSuccess) return fail();
+  if (tdk.alloc(sizeof(int2) * (size_t)nt) != hipSuccess) return fail();
+  if (colk.alloc(4 * ((size_t)nt + (size_t)total)) != hipSuccess) return fail();
   if (hipMemcpyAsync(colk, g->d_col, 4 * (size_t)nt, hipMemcpyDeviceToDevice, 0) != hipSuccess) return fail();
   const long long cblocks = std::min<long long>((nt * 8 + 255) / 256, (long long)g->cu_count * 64);
-  hipLaunchKernelGGL(inl_copy_kernel, dim3((unsigned)cblocks), dim3(256), 0, 0, nt, g->d_tdesc, off, lmax, nt, colk, tdk);
+  hipLaunchKernelGGL(inl_copy_kernel, dim3((unsigned)cblocks), dim3(256), 0, 0, nt, g->d_tdesc, off.get(), lmax, nt, colk.get(), tdk.get());
   if (hipDeviceSynchronize() != hipSuccess) return fail();
-  dev_free(off);
-  g->d_colk = colk;
-  g->d_tdesck = tdk;
+  off.reset();
+  g->d_colk = std::move(colk);
+  g->d_tdesck = std::move(tdk);
   g->n_inline_keys = total;
 }
 
@@ -1276,10 +1246,8 @@ static int tc_pairs_setup(gm_graph *g, const TaskWalk &tw, const int tc_h) {
     return std::min(cb + kCtcBPiece, nc) - cb;
   };
   std::stable_sort(tasks.begin(), tasks.end(), [&](const unsigned a, const unsigned b) { return chunks_of(a) > chunks_of(b); });
-  if (g->d_tc_pair_bits) { dev_free(g->d_tc_pair_bits); g->d_tc_pair_bits = nullptr; }
-  if (g->d_tc_pair_tasks) { dev_free(g->d_tc_pair_tasks); g->d_tc_pair_tasks = nullptr; }
-  HIP_TRY(dev_malloc(&g->d_tc_pair_bits, sizeof(unsigned) * (size_t)nwords));
-  HIP_TRY(dev_malloc(&g->d_tc_pair_tasks, sizeof(unsigned) * std::max<size_t>(tasks.size(), 1)));
+  HIP_TRY(g->d_tc_pair_bits.alloc(sizeof(unsigned) * (size_t)nwords));
+  HIP_TRY(g->d_tc_pair_tasks.alloc(sizeof(unsigned) * std::max<size_t>(tasks.size(), 1)));
   HIP_TRY(hipMemcpy(g->d_tc_pair_bits, bits, sizeof(unsigned) * (size_t)nwords, hipMemcpyHostToDevice));
   if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_tc_pair_tasks, tasks.data(), sizeof(unsigned) * tasks.size(), hipMemcpyHostToDevice));
   g->n_tc_pair_tasks = (int)tasks.size();
@@ -1365,17 +1333,14 @@ int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
   TaskWalk tw_count = tw, tw_place = tw;
   tw_count.hub0 = topo ? std::max(0, g->nv - win_count) : g->nv;
   tw_place.hub0 = topo ? std::max(0, g->nv - win_place) : g->nv;
-  int *krp = second ? g->d_kst_rp : nullptr, *trpl = second ? g->d_trpl : nullptr;
-  unsigned *kst = nullptr;
-  int2 *tdl = nullptr;
-  KstEdges ed{nullptr, nullptr};
-  auto fail = [&](hipError_t e, const char *what) {
-    for (void *q : {second ? nullptr : (void *)krp, second ? nullptr : (void *)trpl, (void *)kst, (void *)tdl, (void *)ed.kst_et, (void *)ed.tedgel})
-      if (q) dev_free(q);
-    return hip_fail(e, what, __FILE__, __LINE__);
-  };
+  DevOwn<int> krp_new, trpl_new, tedgel;  // (what this call builds: handed to the handle at the end, given back on every other return)
+  DevOwn<unsigned> kst;
+  DevOwn<int2> tdl, kst_et;
+  auto fail = [](hipError_t e, const char *what) { return hip_fail(e, what, __FILE__, __LINE__); };
   hipError_t e = hipSuccess;
-  if (!second && ((e = dev_malloc(&krp, sizeof(int) * nv1)) != hipSuccess || (e = dev_malloc(&trpl, sizeof(int) * nv1)) != hipSuccess)) return fail(e, "hipMalloc(key stream offsets)");
+  if (!second && ((e = krp_new.alloc(sizeof(int) * nv1)) != hipSuccess || (e = trpl_new.alloc(sizeof(int) * nv1)) != hipSuccess)) return fail(e, "hipMalloc(key stream offsets)");
+  int *const krp = second ? g->d_kst_rp.get() : krp_new.get(), *const trpl = second ? g->d_trpl.get() : trpl_new.get();
+  KstEdges ed{nullptr, nullptr};
   unsigned long long total = second ? g->n_inline_keys : 0, key_limit = 0x7fffff00ull;
   if (const char *e = gm_opt("GM_KST_MAX_KEYS")) key_limit = std::min<unsigned long long>(key_limit, (unsigned long long)std::max(1ll, atoll(e)));  // (tests)
   int nlong = second ? g->n_long_tasks : 0;
@@ -1391,8 +1356,6 @@ int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
     if (total < key_limit) break;
     lmax >>= 1;
     if (lmax < 4) {
-      dev_free(krp);
-      dev_free(trpl);
       g->kst_state = 2;
       return GM_OK;
     }
@@ -1400,28 +1363,30 @@ int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
   setup_trace("key stream: count pass + scans");
   if (!second) hipLaunchKernelGGL(kst_narrow_kernel, dim3((unsigned)((nv1 + 255) / 256)), dim3(256), 0, 0, g->nv, keyoff.p, krp);
   const size_t nk = (size_t)std::max<unsigned long long>(total, 1), nl = (size_t)std::max(nlong, 1);
-  if ((e = dev_malloc(&kst, sizeof(unsigned) * nk)) != hipSuccess) return fail(e, "hipMalloc(key stream)");
-  if ((e = dev_malloc(&tdl, sizeof(int2) * nl)) != hipSuccess) return fail(e, "hipMalloc(long lists)");
-  if (edges && ((e = dev_malloc(&ed.kst_et, sizeof(int2) * nk)) != hipSuccess || (e = dev_malloc(&ed.tedgel, sizeof(int) * nl)) != hipSuccess))
+  if ((e = kst.alloc(sizeof(unsigned) * nk)) != hipSuccess) return fail(e, "hipMalloc(key stream)");
+  if ((e = tdl.alloc(sizeof(int2) * nl)) != hipSuccess) return fail(e, "hipMalloc(long lists)");
+  if (edges && ((e = kst_et.alloc(sizeof(int2) * nk)) != hipSuccess || (e = tedgel.alloc(sizeof(int) * nl)) != hipSuccess))
     return fail(e, "hipMalloc(key stream entries)");
+  ed.kst_et = kst_et;
+  ed.tedgel = tedgel;
   if ((e = hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * nv1, 0)) != hipSuccess) return fail(e, "hipMemsetAsync");
   const dim3 pg((unsigned)blocks_place), pb(256);
   if (edges) {
-    if (win_place <= 2048) hipLaunchKernelGGL((kst_rows_kernel<true, 2048, true>), pg, pb, 0, 0, tw_place, lmax, cnt.p, krp, trpl, kst, tdl, ed);
-    else hipLaunchKernelGGL((kst_rows_kernel<true, kHubWin, true>), pg, pb, 0, 0, tw_place, lmax, cnt.p, krp, trpl, kst, tdl, ed);
+    if (win_place <= 2048) hipLaunchKernelGGL((kst_rows_kernel<true, 2048, true>), pg, pb, 0, 0, tw_place, lmax, cnt.p, krp, trpl, kst.get(), tdl.get(), ed);
+    else hipLaunchKernelGGL((kst_rows_kernel<true, kHubWin, true>), pg, pb, 0, 0, tw_place, lmax, cnt.p, krp, trpl, kst.get(), tdl.get(), ed);
   } else {
-    if (win_place <= 2048) hipLaunchKernelGGL((kst_rows_kernel<true, 2048, false>), pg, pb, 0, 0, tw_place, lmax, cnt.p, krp, trpl, kst, tdl, ed);
-    else hipLaunchKernelGGL((kst_rows_kernel<true, kHubWin, false>), pg, pb, 0, 0, tw_place, lmax, cnt.p, krp, trpl, kst, tdl, ed);
+    if (win_place <= 2048) hipLaunchKernelGGL((kst_rows_kernel<true, 2048, false>), pg, pb, 0, 0, tw_place, lmax, cnt.p, krp, trpl, kst.get(), tdl.get(), ed);
+    else hipLaunchKernelGGL((kst_rows_kernel<true, kHubWin, false>), pg, pb, 0, 0, tw_place, lmax, cnt.p, krp, trpl, kst.get(), tdl.get(), ed);
   }
   if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) return fail(e, "kst_rows_kernel");
   setup_trace("key stream: place pass");
   if (second) {  // (the first set stays what the triangle count reads)
-    g->d_kst2 = kst;
-    g->d_tdescl2 = tdl;
+    g->d_kst2 = std::move(kst);
+    g->d_tdescl2 = std::move(tdl);
   } else {
-    g->d_kst = kst;
-    g->d_trpl = trpl;
-    g->d_tdescl = tdl;
+    g->d_kst = std::move(kst);
+    g->d_trpl = std::move(trpl_new);
+    g->d_tdescl = std::move(tdl);
     g->n_inline_keys = total;
     g->n_long_tasks = nlong;
     g->kst_lmax = lmax;
@@ -1432,10 +1397,10 @@ int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
     }
   }
   if (edges) {
-    g->d_tedgel = ed.tedgel;
-    g->d_kst_et = ed.kst_et;
+    g->d_tedgel = std::move(tedgel);
+    g->d_kst_et = std::move(kst_et);
   }
-  if (!second) g->d_kst_rp = krp;
+  if (!second) g->d_kst_rp = std::move(krp_new);
   g->setup.table_ms += timer.ms();
   *built = true;
   return GM_OK;
@@ -1480,36 +1445,32 @@ int ensure_tasklists(gm_graph *g, bool /*with_edges*/) {
   tw.skip_from = tl_skip;
   hipLaunchKernelGGL((task_rows_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, 0, tw, cnt.p, nullptr, nullptr, nullptr);
   setup_trace("tasks: count pass");
-  int *trp = nullptr, *tedge = nullptr;
-  int2 *td = nullptr;
-  HIP_TRY(dev_malloc(&trp, sizeof(int) * nv1));
-  hipError_t e = dev_exclusive_sum(tmp, cnt.p, trp, nv1);
-  if (e == hipSuccess) e = dev_malloc(&td, sizeof(int2) * ne);
-  if (e == hipSuccess) e = dev_malloc(&tedge, sizeof(int) * ne);
+  DevOwn<int> trp, tedge;
+  DevOwn<int2> td;
+  HIP_TRY(trp.alloc(sizeof(int) * nv1));
+  hipError_t e = dev_exclusive_sum(tmp, cnt.p, trp.get(), nv1);
+  if (e == hipSuccess) e = td.alloc(sizeof(int2) * ne);
+  if (e == hipSuccess) e = tedge.alloc(sizeof(int) * ne);
   if (e == hipSuccess) e = hipMemsetAsync(td, 0, sizeof(int2) * ne, 0);  // (the edges of rows beyond the stage are no tasks: empty descriptors at the end)
   if (e == hipSuccess) e = hipMemsetAsync(tedge, 0, sizeof(int) * ne, 0);
   if (e == hipSuccess) e = hipMemsetAsync(cnt.p, 0, sizeof(int) * nv1, 0);
   setup_trace("tasks: scan, allocations, clears");
   if (e == hipSuccess) {
     const long long pblocks = std::min<long long>(((long long)g->nv * 8 + 255) / 256, (long long)g->cu_count * (topo ? 16 : 64));  // (the place pass waits for its returning atomics)
-    hipLaunchKernelGGL((task_rows_kernel<true>), dim3((unsigned)pblocks), dim3(256), 0, 0, tw, cnt.p, trp, td, tedge);
+    hipLaunchKernelGGL((task_rows_kernel<true>), dim3((unsigned)pblocks), dim3(256), 0, 0, tw, cnt.p, trp.get(), td.get(), tedge.get());
     e = hipDeviceSynchronize();
   }
-  if (e != hipSuccess) {
-    dev_free(trp);
-    if (td) dev_free(td);
-    if (tedge) dev_free(tedge);
-    return hip_fail(e, "task lists", __FILE__, __LINE__);
-  }
+  if (e != hipSuccess) return hip_fail(e, "task lists", __FILE__, __LINE__);
   if (tl_skip < g->nv) {
     g->tl_skip_from = tl_skip;
     g->tl_core_h = g->nv - tl_skip;
   }
-  g->d_trp = trp;
-  g->d_tedge = tedge;
+  g->d_trp = std::move(trp);
+  g->d_tedge = std::move(tedge);
+  g->d_tdesc_mem = std::move(td);
   // d_tdesc is what the lock-free check at the top reads: published LAST, with release order, so that a first caller on another thread
   // that sees it also sees the corner's skip row and the other arrays
-  __atomic_store_n(&g->d_tdesc, td, __ATOMIC_RELEASE);
+  __atomic_store_n(&g->d_tdesc, g->d_tdesc_mem.get(), __ATOMIC_RELEASE);
   setup_trace("tasks: place pass");
   if (!keystream_possible(g)) build_inline_copies(g, tmp);  // (a handle that cannot have the key stream: task-major copies of the short lists)
   setup_trace("tasks: inline copies");
@@ -1565,23 +1526,19 @@ int ensure_sup_corner(gm_graph *g) {
   HIP_TRY(hipSetDevice(g->device));
   const int h = g->tl_core_h, words = h / 32;
   const size_t cells = (size_t)h * (size_t)words;
-  unsigned *bits = nullptr;
-  unsigned short *first_pos = nullptr;
-  HIP_TRY(dev_malloc(&bits, cells * sizeof(unsigned)));
-  hipError_t e = dev_malloc(&first_pos, cells * sizeof(unsigned short));
+  DevOwn<unsigned> bits;
+  DevOwn<unsigned short> first_pos;
+  HIP_TRY(bits.alloc(cells * sizeof(unsigned)));
+  hipError_t e = first_pos.alloc(cells * sizeof(unsigned short));
   if (e == hipSuccess) e = hipMemsetAsync(bits, 0, cells * sizeof(unsigned), 0);
   if (e == hipSuccess) e = hipMemsetAsync(first_pos, 0, cells * sizeof(unsigned short), 0);
   int e0 = 0;
   if (e == hipSuccess) e = hipMemcpy(&e0, g->d_rp + g->tl_skip_from, sizeof(int), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = launch_core_sym_fill(g->nv, g->tl_skip_from, words, (long long)e0, g->ne, g->d_rp, g->d_col, bits, first_pos, g->cu_count, 0);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    dev_free(bits);
-    if (first_pos) dev_free(first_pos);
-    return hip_fail(e, "symmetric corner", __FILE__, __LINE__);
-  }
-  g->d_cfirst = first_pos;
-  g->d_csym = bits;
+  if (e != hipSuccess) return hip_fail(e, "symmetric corner", __FILE__, __LINE__);
+  g->d_cfirst = std::move(first_pos);
+  g->d_csym = std::move(bits);
   setup_trace("supports: symmetric corner");
   g->setup.table_ms += timer.ms();
   return GM_OK;
@@ -1638,35 +1595,33 @@ int ensure_sup_masks(gm_graph *g) {
   HIP_TRY(dev_exclusive_sum(tmp, fflag.p, fpos.p, (size_t)g->nv + 1));
   int nfar = 0;
   HIP_TRY(hipMemcpy(&nfar, fpos.p + g->nv, sizeof nfar, hipMemcpyDeviceToHost));
-  unsigned *emoff = nullptr, *tmoff = nullptr;
-  unsigned long long *arena = nullptr;
-  int *far_rows = nullptr;
-  hipError_t e = dev_malloc(&emoff, sizeof(unsigned) * ne);
-  if (e == hipSuccess) e = dev_malloc(&far_rows, sizeof(int) * (size_t)std::max(nfar, 1));
-  if (e == hipSuccess) hipLaunchKernelGGL(sup_far_list_kernel, dim3((unsigned)((g->nv + 255) / 256)), dim3(256), 0, 0, g->nv, fflag.p, fpos.p, far_rows);
-  if (e == hipSuccess) e = dev_malloc(&tmoff, sizeof(unsigned) * ne);
-  if (e == hipSuccess) e = dev_malloc(&arena, sizeof(unsigned long long) * (size_t)total);
+  DevOwn<unsigned> emoff, tmoff;
+  DevOwn<unsigned long long> arena;
+  DevOwn<int> far_rows;
+  hipError_t e = emoff.alloc(sizeof(unsigned) * ne);
+  if (e == hipSuccess) e = far_rows.alloc(sizeof(int) * (size_t)std::max(nfar, 1));
+  if (e == hipSuccess) hipLaunchKernelGGL(sup_far_list_kernel, dim3((unsigned)((g->nv + 255) / 256)), dim3(256), 0, 0, g->nv, fflag.p, fpos.p, far_rows.get());
+  if (e == hipSuccess) e = tmoff.alloc(sizeof(unsigned) * ne);
+  if (e == hipSuccess) e = arena.alloc(sizeof(unsigned long long) * (size_t)total);
   // (every launch rewrites the words of the tasks it runs; a launch that leaves masked tasks out -- a chunk filter, an aborted launch --
   // must find zeros, not what hipMalloc handed over: ADVICE r5)
   if (e == hipSuccess) e = hipMemsetAsync(arena, 0, sizeof(unsigned long long) * (size_t)total, 0);
   if (e == hipSuccess) {
     const long long eb = std::min<long long>(((long long)ne + 255) / 256, (long long)g->cu_count * 32);
-    hipLaunchKernelGGL(sup_mask_off_kernel, dim3((unsigned)eb), dim3(256), 0, 0, (long long)ne, off.p, emoff);
-    hipLaunchKernelGGL(sup_mask_task_kernel, dim3((unsigned)eb), dim3(256), 0, 0, (long long)ne, g->d_tdesc, g->d_tedge, emoff, tmoff);
+    hipLaunchKernelGGL(sup_mask_off_kernel, dim3((unsigned)eb), dim3(256), 0, 0, (long long)ne, off.p, emoff.get());
+    hipLaunchKernelGGL(sup_mask_task_kernel, dim3((unsigned)eb), dim3(256), 0, 0, (long long)ne, g->d_tdesc, g->d_tedge, emoff.get(), tmoff.get());
     e = hipDeviceSynchronize();
   }
   if (e != hipSuccess) {  // (an optimisation that did not fit: the atomics stay)
-    for (void *q : {(void *)emoff, (void *)tmoff, (void *)arena, (void *)far_rows})
-      if (q) dev_free(q);
     (void)hipGetLastError();
     g->smask_state = 2;
     g->setup.table_ms += timer.ms();
     return GM_OK;
   }
-  g->d_emoff = emoff;
-  g->d_tmoff = tmoff;
-  g->d_smask = arena;
-  g->d_sup_far_rows = far_rows;
+  g->d_emoff = std::move(emoff);
+  g->d_tmoff = std::move(tmoff);
+  g->d_smask = std::move(arena);
+  g->d_sup_far_rows = std::move(far_rows);
   g->n_sup_far_rows = nfar;
   g->smask_words = total;
   g->smask_state = 1;
@@ -1694,8 +1649,8 @@ int ensure_long_rows(gm_graph *g) {
   }
   if (!rows.empty()) {
     HIP_TRY(hipSetDevice(g->device));
-    HIP_TRY(dev_malloc(&g->d_long_rows, sizeof(int) * rows.size()));
-    HIP_TRY(dev_malloc(&g->d_long_prefix, sizeof(long long) * prefix.size()));
+    HIP_TRY(g->d_long_rows.alloc(sizeof(int) * rows.size()));
+    HIP_TRY(g->d_long_prefix.alloc(sizeof(long long) * prefix.size()));
     HIP_TRY(copy_to_device(g->d_long_rows, rows.data(), sizeof(int) * rows.size()));
     HIP_TRY(copy_to_device(g->d_long_prefix, prefix.data(), sizeof(long long) * prefix.size()));
   }
@@ -1709,14 +1664,14 @@ int ensure_edesc(gm_graph *g) {
   std::lock_guard<std::mutex> lk(g->mu);
   if (g->d_edesc) return GM_OK;
   SetupTimer timer;
-  int2 *d = nullptr;
-  HIP_TRY(dev_malloc(&d, sizeof(int2) * (size_t)g->ne));
+  DevOwn<int2> d;
+  HIP_TRY(d.alloc(sizeof(int2) * (size_t)g->ne));
   const long long blocks = std::min<long long>((g->ne + 255) / 256, (long long)g->cu_count * 32);
-  hipLaunchKernelGGL(edesc_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, g->ne, g->d_rp, g->d_col, d);
+  hipLaunchKernelGGL(edesc_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, g->ne, g->d_rp, g->d_col, d.get());
   hipError_t e = hipDeviceSynchronize();
   setup_trace("edge descriptors");
-  if (e != hipSuccess) { dev_free(d); return hip_fail(e, "edesc_kernel", __FILE__, __LINE__); }
-  g->d_edesc = d;
+  if (e != hipSuccess) return hip_fail(e, "edesc_kernel", __FILE__, __LINE__);
+  g->d_edesc = std::move(d);
   g->setup.table_ms += timer.ms();
   return GM_OK;
 }
@@ -1914,9 +1869,8 @@ int ensure_core_bitmap(gm_graph *g) {
   const int base = g->nv - h;
   const int words = (h + 31) / 32;
   const size_t bytes = (size_t)h * (size_t)words * 4;
-  if (dev_malloc(&g->d_core, bytes) != hipSuccess) {  // no room: the streamed build does everything
+  if (g->d_core.alloc(bytes) != hipSuccess) {  // no room: the streamed build does everything
     (void)hipGetLastError();
-    g->d_core = nullptr;
     g->core_state = 2;
     return GM_OK;
   }
@@ -2001,14 +1955,14 @@ int ensure_core_tri(gm_graph *g) {
     g->cg_tri_state = 2;
     return GM_OK;
   }
-  unsigned *tri = nullptr;
-  int *d_bid = nullptr, *d_rowbase = nullptr;
-  int4 *d_blk = nullptr;
+  DevOwn<unsigned> tri;
+  DevOwn<int> d_bid, d_rowbase;
+  DevOwn<int4> d_blk;
   int e01[2] = {0, 0};
-  hipError_t e = dev_malloc(&tri, sizeof(unsigned) * (size_t)std::max<long long>(total, 4));
-  if (e == hipSuccess) e = dev_malloc(&d_bid, sizeof(int) * (size_t)h);
-  if (e == hipSuccess) e = dev_malloc(&d_rowbase, sizeof(int) * (size_t)h);
-  if (e == hipSuccess) e = dev_malloc(&d_blk, sizeof(int4) * blk.size());
+  hipError_t e = tri.alloc(sizeof(unsigned) * (size_t)std::max<long long>(total, 4));
+  if (e == hipSuccess) e = d_bid.alloc(sizeof(int) * (size_t)h);
+  if (e == hipSuccess) e = d_rowbase.alloc(sizeof(int) * (size_t)h);
+  if (e == hipSuccess) e = d_blk.alloc(sizeof(int4) * blk.size());
   if (e == hipSuccess) e = hipMemsetAsync(tri, 0, sizeof(unsigned) * (size_t)std::max<long long>(total, 4), 0);
   if (e == hipSuccess) e = copy_to_device(d_bid, bid.data(), sizeof(int) * (size_t)h);
   if (e == hipSuccess) e = copy_to_device(d_rowbase, rowbase.data(), sizeof(int) * (size_t)h);
@@ -2023,16 +1977,14 @@ int ensure_core_tri(gm_graph *g) {
     e = hipDeviceSynchronize();
   }
   if (e != hipSuccess) {  // (no room: the row-major gather does the work)
-    for (void *q : {(void *)tri, (void *)d_bid, (void *)d_rowbase, (void *)d_blk})
-      if (q) dev_free(q);
     (void)hipGetLastError();
     g->cg_tri_state = 2;
     return GM_OK;
   }
-  g->d_cg_tri = tri;
-  g->d_cg_bid = d_bid;
-  g->d_cg_rowbase = d_rowbase;
-  g->d_cg_blk = d_blk;
+  g->d_cg_tri = std::move(tri);
+  g->d_cg_bid = std::move(d_bid);
+  g->d_cg_rowbase = std::move(d_rowbase);
+  g->d_cg_blk = std::move(d_blk);
   g->n_cg_blocks = (int)blk.size();
   g->cg_tri_state = 1;
   setup_trace("clique: core blocks");
@@ -2162,16 +2114,12 @@ static int build_gather_index(gm_graph *g, CliquePlan &pl, CliqueRound &rd, Scan
   HIP_TRY(dev_exclusive_sum(tmp, tsz.p, poff.p, (size_t)nslots + 1));
   unsigned tab_words = 0;
   HIP_TRY(hipMemcpy(&tab_words, poff.p + nslots, sizeof(unsigned), hipMemcpyDeviceToHost));
-  unsigned *tab = nullptr;
+  DevOwn<unsigned> tab;  // (the round's once the index is complete)
   // (+ nine tile pairs of slack: the kernel requests nine pairs from a unit's first one on without looking at the table's end -- what lies
   // beyond belongs to tiles the vertex does not have and is never used; byte offsets are 32 bits)
   if ((unsigned long long)tab_words * 4ull + 4096ull >= (1ull << 32)) return GM_OK;  // (no index: the row-major gather)
-  HIP_TRY(dev_malloc(&tab, sizeof(unsigned) * ((size_t)std::max(tab_words, 64u) + 9 * 64)));
+  HIP_TRY(tab.alloc(sizeof(unsigned) * ((size_t)std::max(tab_words, 64u) + 9 * 64)));
   hipLaunchKernelGGL(cgb_table_fill_kernel, wgrid, dim3(256), 0, 0, (int)rd.w0, nslots, pl.d_verts, g->d_rp, g->d_col, pl.core_base, poff.p, tab);
-  struct TabGuard {  // (the table belongs to the round once the index is complete)
-    unsigned *p;
-    ~TabGuard() { if (p) dev_free(p); }
-  } tab_guard{tab};
   DevBuf<unsigned> keys, keys_s, idx, idx_s;
   DevBuf<uint4> recs;
   DevBuf<unsigned long long> cost, cum;
@@ -2192,14 +2140,14 @@ static int build_gather_index(gm_graph *g, CliquePlan &pl, CliqueRound &rd, Scan
     HIP_TRY(tmp.reserve(bytes));
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.buf.p, bytes, keys.p, keys_s.p, idx.p, idx_s.p, nu, 0, bits));  // (stable: a block's units stay in slot order)
   }
-  uint4 *units = nullptr;
-  HIP_TRY(dev_malloc(&units, sizeof(uint4) * (size_t)nu));
+  DevOwn<uint4> units;
+  HIP_TRY(units.alloc(sizeof(uint4) * (size_t)nu));
   hipError_t e = cost.alloc((size_t)nu + 1);
   if (e == hipSuccess) e = cum.alloc((size_t)nu + 1);
   if (e == hipSuccess) e = flag.alloc((size_t)nu + 1);
   if (e == hipSuccess) e = pos.alloc((size_t)nu + 1);
   int ni = 0;
-  int2 *items = nullptr;
+  DevOwn<int2> items;
   if (e == hipSuccess) {
     hipLaunchKernelGGL(cgb_gather_kernel, blocks(nu), dim3(256), 0, 0, (long long)nu, idx_s.p, recs.p, units, cost.p, cum.p);
     size_t bytes = 0;  // (cum holds the units' table bytes for a moment: their sum is the kernel's own bytes, gm_clique4_gather_info)
@@ -2217,20 +2165,15 @@ static int build_gather_index(gm_graph *g, CliquePlan &pl, CliqueRound &rd, Scan
     e = dev_exclusive_sum(tmp, flag.p, pos.p, (size_t)nu + 1);
   }
   if (e == hipSuccess) e = hipMemcpy(&ni, pos.p + nu, sizeof(int), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = dev_malloc(&items, sizeof(int2) * ((size_t)ni + 1));
+  if (e == hipSuccess) e = items.alloc(sizeof(int2) * ((size_t)ni + 1));
   if (e == hipSuccess) {
     hipLaunchKernelGGL(cgb_item_place_kernel, blocks(nu), dim3(256), 0, 0, (long long)nu, keys_s.p, flag.p, pos.p, items, ni);
     e = hipDeviceSynchronize();
   }
-  if (e != hipSuccess) {
-    dev_free(units);
-    if (items) dev_free(items);
-    return hip_fail(e, "gather index", __FILE__, __LINE__);
-  }
-  rd.d_gunits = units;
-  rd.d_gtab = tab;
-  tab_guard.p = nullptr;
-  rd.d_gitems = items;
+  if (e != hipSuccess) return hip_fail(e, "gather index", __FILE__, __LINE__);
+  rd.d_gunits = std::move(units);
+  rd.d_gtab = std::move(tab);
+  rd.d_gitems = std::move(items);
   rd.n_gunits = (size_t)nu;
   rd.n_gitems = (size_t)ni;
   return GM_OK;
@@ -2252,27 +2195,6 @@ __global__ __launch_bounds__(256) void mcls_rec_kernel(int n, const int *__restr
   const unsigned long long b = slot_base[slot];
   rec[k] = make_int4(rp[u + 1] - rp[u], (int)(unsigned)b, (int)(unsigned)(b >> 32), 0);
 }
-static void free_clique_plan(CliquePlan &pl) {
-  if (pl.d_verts) dev_free(pl.d_verts);
-  if (pl.d_slot_base) dev_free(pl.d_slot_base);
-  if (pl.d_mcls_slots) dev_free(pl.d_mcls_slots);
-  if (pl.d_mcls_rec) dev_free(pl.d_mcls_rec);
-  for (auto &rd : pl.rounds) {
-    if (rd.d_base) dev_free(rd.d_base);
-    if (rd.d_tasks) dev_free(rd.d_tasks);
-    if (rd.d_trp) dev_free(rd.d_trp);
-    if (rd.d_gunits) dev_free(rd.d_gunits);
-    if (rd.d_gtab) dev_free(rd.d_gtab);
-    if (rd.d_gitems) dev_free(rd.d_gitems);
-    free_table(rd.host_tab);
-  }
-  pl.rounds.clear();
-  pl.d_verts = nullptr; pl.d_slot_base = nullptr; pl.d_mcls_slots = nullptr; pl.d_mcls_rec = nullptr;
-}
-void free_clique_plans(gm_graph *g) {
-  for (auto &pl : g->clique_plans) free_clique_plan(pl);
-  g->clique_plans.clear();
-}
 
 // one round: owners -> offsets -> task lists -> host-chunk table
 static int build_clique_round(gm_graph *g, CliquePlan &pl, CliqueRound &rd, ScanTemp &tmp) {
@@ -2291,14 +2213,14 @@ static int build_clique_round(gm_graph *g, CliquePlan &pl, CliqueRound &rd, Scan
   if (rd.w1 > rd.w0)
     hipLaunchKernelGGL(cb_own_verts_kernel, blocks((long long)(rd.w1 - rd.w0)), dim3(256), 0, 0, (int)(rd.w1 - rd.w0), pl.d_verts + rd.w0, own.p);
   hipLaunchKernelGGL(cb_owner_sizes_kernel, blocks((long long)nv1), dim3(256), 0, 0, nv, g->d_rp, g->d_col, own.p, pl.core_base, words.p, ntask_of.p);
-  HIP_TRY(dev_malloc(&rd.d_base, sizeof(unsigned long long) * nv1));
-  HIP_TRY(dev_exclusive_sum(tmp, words.p, rd.d_base, nv1));
+  HIP_TRY(rd.d_base.alloc(sizeof(unsigned long long) * nv1));
+  HIP_TRY(dev_exclusive_sum(tmp, words.p, rd.d_base.get(), nv1));
   HIP_TRY(dev_exclusive_sum(tmp, ntask_of.p, tpos.p, nv1));
   int nt = 0;
   HIP_TRY(hipMemcpy(&rd.words, rd.d_base + nv, 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(&nt, tpos.p + nv, sizeof(int), hipMemcpyDeviceToHost));
   rd.n_tasks = (size_t)nt;
-  HIP_TRY(dev_malloc(&rd.d_trp, sizeof(int) * nv1));
+  HIP_TRY(rd.d_trp.alloc(sizeof(int) * nv1));
   if (rd.w1 > rd.w0)  // (before the early return: a round whose wide rows all come from the core bitmap has no streamed task at all)
     hipLaunchKernelGGL(cb_slot_base_kernel, blocks((long long)(rd.w1 - rd.w0)), dim3(256), 0, 0, (int)rd.w0, (int)rd.w1, pl.d_verts, rd.d_base, pl.d_slot_base);
   if (nt == 0) {
@@ -2312,8 +2234,8 @@ static int build_clique_round(gm_graph *g, CliquePlan &pl, CliqueRound &rd, Scan
   const int hub0 = pl.topo ? std::max(0, nv - kHubWin) : nv;
   hipLaunchKernelGGL((cb_task_rows_kernel<false>), dim3((unsigned)kblocks), dim3(256), 0, 0, nv, g->d_rp, g->d_col, g->d_edesc, ntask_of.p, pl.topo ? 1 : 0, hub0,
                      cnt.p, nullptr, nullptr, nullptr);
-  HIP_TRY(dev_exclusive_sum(tmp, cnt.p, rd.d_trp, nv1));
-  HIP_TRY(dev_malloc(&rd.d_tasks, sizeof(CBuildTask) * (size_t)nt));
+  HIP_TRY(dev_exclusive_sum(tmp, cnt.p, rd.d_trp.get(), nv1));
+  HIP_TRY(rd.d_tasks.alloc(sizeof(CBuildTask) * (size_t)nt));
   HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(int) * nv1, 0));
   hipLaunchKernelGGL((cb_task_rows_kernel<true>), dim3((unsigned)kblocks), dim3(256), 0, 0, nv, g->d_rp, g->d_col, g->d_edesc, ntask_of.p, pl.topo ? 1 : 0, hub0,
                      cnt.p, rd.d_trp, rd.d_base, rd.d_tasks);
@@ -2387,11 +2309,11 @@ int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, un
       HIP_TRY(degs.alloc((size_t)m));
       HIP_TRY(keyo.alloc((size_t)m));
       hipLaunchKernelGGL(gather_deg_kernel, blocks(m), dim3(256), 0, 0, m, sel.p, g->d_rp, degs.p);
-      HIP_TRY(dev_malloc(&g->d_wide_sorted, sizeof(int) * (size_t)m));
+      HIP_TRY(g->d_wide_sorted.alloc(sizeof(int) * (size_t)m));
       size_t bytes = 0;
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, degs.p, keyo.p, sel.p, g->d_wide_sorted, m));
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, degs.p, keyo.p, sel.p, g->d_wide_sorted.get(), m));
       HIP_TRY(tmp.reserve(bytes));
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(tmp.buf.p, bytes, degs.p, keyo.p, sel.p, g->d_wide_sorted, m));
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(tmp.buf.p, bytes, degs.p, keyo.p, sel.p, g->d_wide_sorted.get(), m));
     }
     g->wide_valid = true;
   }
@@ -2437,8 +2359,8 @@ int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, un
   std::vector<int> hd((size_t)wcount);
   if (wcount > 0) {
     DevBuf<int> degs;
-    HIP_TRY(dev_malloc(&pl.d_verts, sizeof(int) * (size_t)wcount));
-    HIP_TRY(dev_malloc(&pl.d_slot_base, sizeof(unsigned long long) * (size_t)wcount));
+    HIP_TRY(pl.d_verts.alloc(sizeof(int) * (size_t)wcount));
+    HIP_TRY(pl.d_slot_base.alloc(sizeof(unsigned long long) * (size_t)wcount));
     HIP_TRY(degs.alloc((size_t)wcount));
     hipLaunchKernelGGL(wide_share_kernel, blocks(wcount), dim3(256), 0, 0, (int)wcount, (long long)wfirst, (long long)wstep, g->d_wide_sorted, g->d_rp, pl.d_verts, degs.p);
     pl.verts.resize((size_t)wcount);
@@ -2510,35 +2432,33 @@ int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, un
     }
   }
   setup_trace("clique: rounds (host loop)");
-  HIP_TRY(dev_malloc(&pl.d_mcls_slots, sizeof(int) * std::max<size_t>(mcls_slots.size(), 1)));
+  HIP_TRY(pl.d_mcls_slots.alloc(sizeof(int) * std::max<size_t>(mcls_slots.size(), 1)));
   if (!mcls_slots.empty()) HIP_TRY(copy_to_device(pl.d_mcls_slots, mcls_slots.data(), sizeof(int) * mcls_slots.size()));
   setup_trace("clique: wide list, classes, rounds (host)");
   unsigned long long need_words = 0;
   for (size_t r = 0; r < pl.rounds.size(); ++r) {
     const int rc = build_clique_round(g, pl, pl.rounds[r], tmp);
-    if (rc) { free_clique_plan(pl); return rc; }
+    if (rc) return rc;  // (the half-built plan goes back with `pl`)
     if (pl.core_base >= 0) {
       int rc2 = ensure_core_tri(g);
       if (rc2 == GM_OK) rc2 = build_gather_index(g, pl, pl.rounds[r], tmp);
-      if (rc2) { free_clique_plan(pl); return rc2; }
+      if (rc2) return rc2;
     }
     need_words = std::max(need_words, pl.rounds[r].words);
   }
   if (!mcls_slots.empty()) {  // (the slot offsets are known now: the records the count kernels read behind their dequeue)
-    HIP_TRY(dev_malloc(&pl.d_mcls_rec, sizeof(int4) * mcls_slots.size()));
+    HIP_TRY(pl.d_mcls_rec.alloc(sizeof(int4) * mcls_slots.size()));
     hipLaunchKernelGGL(mcls_rec_kernel, blocks((long long)mcls_slots.size()), dim3(256), 0, 0, (int)mcls_slots.size(), pl.d_mcls_slots, pl.d_verts, g->d_rp,
                        pl.d_slot_base, pl.d_mcls_rec);
   }
   setup_trace("clique: rounds built");
   const size_t need = (size_t)need_words * 4;
   if (need > g->wide_mat_bytes) {
-    if (g->d_wide_mat) dev_free(g->d_wide_mat);
-    g->d_wide_mat = nullptr;
     g->wide_mat_bytes = 0;
-    HIP_TRY(dev_malloc(&g->d_wide_mat, std::max<size_t>(need, 16)));
+    HIP_TRY(g->d_wide_mat.alloc(std::max<size_t>(need, 16)));
     g->wide_mat_bytes = need;
   }
-  if (!g->d_wide_queue) HIP_TRY(dev_malloc(&g->d_wide_queue, 65536));
+  if (!g->d_wide_queue) HIP_TRY(g->d_wide_queue.alloc(65536));
   setup_trace("clique: arena");
   HIP_TRY(hipDeviceSynchronize());
   std::lock_guard<std::mutex> lk(g->mu);

@@ -194,12 +194,12 @@ __global__ void selftest_kernel(int *out) {
 extern "C" int gm_selftest(int device, int *n_fail) {
   if (n_fail) *n_fail = -1;
   HIP_TRY(hipSetDevice(device));
-  int *d = nullptr;
-  HIP_TRY(dev_malloc(&d, sizeof(int) * 512));
-  hipLaunchKernelGGL(selftest_kernel, dim3(1), dim3(64), 0, 0, d);
+  DevOwn<int> d;
+  HIP_TRY(d.alloc(sizeof(int) * 512));
+  hipLaunchKernelGGL(selftest_kernel, dim3(1), dim3(64), 0, 0, d.get());
   int h[512];
   hipError_t e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-  dev_free(d);
+  d.reset();
   if (e != hipSuccess) return hip_fail(e, "selftest", __FILE__, __LINE__);
   int bad = 0, acc = 0, mx = 0, rk = 0;
   for (int l = 0; l < 64; ++l) {

@@ -480,6 +480,11 @@ int gm_constant(const char *name, int64_t *value);
 int gm_dev_option(const char *name, const char *value);
 const char *gm_dev_option_get(const char *name);
 
+/* Tooling: the number of device blocks the library has allocated and not yet got back, over all devices and handles of the process.  A block
+ * that a freed handle left in the per-device cache of large blocks counts as returned.  Equal before creating a handle and after freeing it
+ * (whatever ran in between), or the handle leaked. */
+int gm_dev_live_blocks(int64_t *n);
+
 /* wave-primitive self test (DPP scans, ballot rank, LDS search); returns GM_OK when the device
  * results equal the host expectation. *n_fail receives the number of mismatching lanes. */
 int gm_selftest(int device, int *n_fail);
