@@ -12,6 +12,7 @@
 // instead of per-GPU COO copies, and the multi-GPU split is index arithmetic on chunk ids.
 #pragma once
 #include "../../include/graphminer_amd.h"
+#include "gm_centre_plan.h"
 #include "gm_devown.h"
 #include "gm_mine.h"
 #include "gm_setops.h"
@@ -268,6 +269,16 @@ struct BitmapSet {
   unsigned long long words = 0;
 };
 
+// The plan of a map solver whose heavy centres count in LDS maps (rectangle, house; ensure_rect_plan / ensure_house_plan, gm_launch.hip)
+struct CentrePlan {             // once per graph, published whole
+  DevOwn<int> d_bnd;            // nv x (n + 1) row bounds
+  DevOwn<int2> d_lds_tasks;     // (centre, range) tasks of the *_lds_kernel
+  DevOwn<int4> d_acc_tasks;     // the "cut" list: first n_cut tasks walk only ends below cut
+  unsigned long long n_lds_tasks = 0, n_acc_tasks = 0, n_cut = 0;
+  int cut = 0, bnd_stride = 0;
+  bool ready = false;
+};
+
 struct gm_graph {
   int device = 0;
   int nv = 0;
@@ -379,15 +390,10 @@ struct gm_graph {
   unsigned long long n_wblocks = 0;
   DevOwn<int4> d_rect_tasks;          // rectangle by wedge accumulation: task list, counter maps
   unsigned long long n_rect_tasks = 0;
-  // rectangle with the heavy centres' counter maps in LDS (round 6, gm_mine.hip rect_lds_kernel): row bounds per range boundary, the
-  // (centre, range) tasks, and rect_acc_kernel's list with the centres that keep only their ends below `rect_cut` first
-  DevOwn<int> d_rect_bnd;
-  DevOwn<int2> d_rect_lds_tasks;
-  DevOwn<int4> d_rect_cut_tasks;
-  unsigned long long n_rect_lds_tasks = 0, n_rect_cut_tasks = 0, n_rect_cut = 0;
-  int rect_cut = 0;
+  // rectangle / house with the heavy centres' maps in LDS (round 6, gm_mine.hip rect_lds_kernel / house_lds_kernel): the id ranges, the plans
   gm::RectLdsRanges rect_ranges;
-  bool rect_lds_ready = false;
+  gm::HouseLdsRanges house_ranges;
+  CentrePlan rect_plan, house_plan;
   DevOwn<unsigned> d_rect_acc;
   size_t rect_acc_bytes = 0;
   DevOwn<unsigned> d_house_t;         // house by wedge accumulation: per-entry tables, task list, 64-bit maps
@@ -397,13 +403,6 @@ struct gm_graph {
   DevOwn<unsigned long long> d_house_acc;
   size_t house_acc_bytes = 0;
   DevOwn<int> d_house_touched;
-  // house with the heavy centres' maps in LDS (round 6, gm_mine.hip house_lds_kernel): as for the rectangle
-  DevOwn<int> d_house_bnd;
-  DevOwn<int2> d_house_lds_tasks;
-  DevOwn<int4> d_house_cut_tasks;
-  unsigned long long n_house_lds_tasks = 0, n_house_cut_tasks = 0, n_house_cut = 0;
-  gm::HouseLdsRanges house_ranges;
-  bool house_lds_ready = false;
   DevOwn<int> d_pent_touched;         // pentagon by wedge accumulation: touched-vertex lists (same shape as d_rect_acc)
   size_t pent_touched_bytes = 0;
   DevOwn<unsigned long long> d_house_prefix;  // house: per-entry task-block prefix

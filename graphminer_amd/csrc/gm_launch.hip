@@ -1277,41 +1277,42 @@ extern "C" int gm_tc_pairs_info(const gm_graph *dag, int64_t info[6]) {
   return GM_OK;
 }
 
-// The tasks of the map kernels (rect_acc_kernel / pent_acc_kernel / house_acc_kernel) from centres ordered heaviest first: a centre with at
-// least 2^15 2-paths gets a whole workgroup (a task of its own), the light ones go four to a task
-static void emit_centre_tasks(const std::vector<int> &vs, const std::vector<unsigned long long> &w, std::vector<int4> &tasks) {
-  const unsigned long long heavy = 1ull << 15;  // 2-paths above which a centre gets a whole workgroup
-  size_t i = 0;
-  for (; i < vs.size() && w[(size_t)vs[i]] >= heavy; ++i) tasks.push_back(make_int4(vs[i], -2, -2, -2));
-  for (; i < vs.size(); i += 4) {
-    int4 t = make_int4(vs[i], -1, -1, -1);
-    if (i + 1 < vs.size()) t.y = vs[i + 1];
-    if (i + 2 < vs.size()) t.z = vs[i + 2];
-    if (i + 3 < vs.size()) t.w = vs[i + 3];
-    tasks.push_back(t);
-  }
+constexpr unsigned long long kHeavyCentre = 1ull << 15;  // 2-paths above which a centre of the map kernels gets a whole workgroup (emit_centre_tasks, gm_centre_plan.h)
+// a host vector as a fresh device array (of at least one element)
+template <class T>
+static int upload(DevOwn<T> &d, const std::vector<T> &h) {
+  HIP_TRY(d.alloc(sizeof(T) * std::max<size_t>(h.size(), 1)));
+  if (!h.empty()) HIP_TRY(hipMemcpy(d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+  return GM_OK;
 }
-// ... every centre with work, by its 2-path estimate (work_launch: the kernel that writes it per centre), as one task list on the device
-// (the form with every end in the global maps)
-template <class WorkLaunch>
-static int build_centre_tasks(size_t nv, WorkLaunch work_launch, const char *what, DevOwn<int4> &d_tasks, unsigned long long *n_tasks) {
+// the 2-path estimates of every centre on the host (launch: the kernel that writes them, `parts` arrays of nv)
+template <class Launch>
+static int centre_estimates(size_t nv, int parts, Launch launch, const char *what, std::vector<unsigned long long> &est) {
   DevOwn<unsigned long long> d_work;
-  HIP_TRY(d_work.alloc(sizeof(unsigned long long) * std::max<size_t>(nv, 1)));
-  std::vector<unsigned long long> work(std::max<size_t>(nv, 1));
-  hipError_t e = nv ? work_launch(d_work) : hipSuccess;
-  if (e == hipSuccess) e = hipMemcpy(work.data(), d_work, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost);
-  d_work.reset();
-  if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
+  HIP_TRY(d_work.alloc(sizeof(unsigned long long) * parts * std::max<size_t>(nv, 1)));
+  est.assign(parts * std::max<size_t>(nv, 1), 0);
+  hipError_t e = nv ? launch(d_work) : hipSuccess;
+  if (e == hipSuccess) e = hipMemcpy(est.data(), d_work, sizeof(unsigned long long) * parts * nv, hipMemcpyDeviceToHost);
+  return e == hipSuccess ? GM_OK : hip_fail(e, what, __FILE__, __LINE__);
+}
+// Every centre with work, by its 2-path estimate (work_launch: the kernel that writes it per centre), as one task list on the device, once
+// per graph (the form with every end in the global maps): heavy first, then light by 4
+template <class WorkLaunch>
+static int build_centre_tasks(gm_graph *g, WorkLaunch work_launch, const char *what, DevOwn<int4> &d_tasks, unsigned long long *n_tasks) {
+  if (d_tasks) return GM_OK;
+  OtherSetupScope scope(g);
+  const size_t nv = (size_t)g->nv;
+  std::vector<unsigned long long> work;
+  if (int rc = centre_estimates(nv, 1, work_launch, what, work)) return rc;
   std::vector<int> vs;
   vs.reserve(nv);
   for (size_t v = 0; v < nv; ++v)
     if (work[v] > 0) vs.push_back((int)v);
   std::stable_sort(vs.begin(), vs.end(), [&](int a, int b) { return work[(size_t)a] > work[(size_t)b]; });
   std::vector<int4> tasks;
-  emit_centre_tasks(vs, work, tasks);
+  emit_centre_tasks(vs, work.data(), kHeavyCentre, tasks);
   DevOwn<int4> d;
-  HIP_TRY(d.alloc(sizeof(int4) * std::max<size_t>(tasks.size(), 1)));
-  if (!tasks.empty()) HIP_TRY(hipMemcpy(d, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice));
+  if (int rc = upload(d, tasks)) return rc;
   *n_tasks = tasks.size();
   d_tasks = std::move(d);  // (the list is what says "built": handed over whole)
   return GM_OK;
@@ -1375,7 +1376,118 @@ static int run_rect_flat(const gm_graph *cg, const gm_launch *la_in, uint64_t *h
 
 static int ensure_edge_tables(gm_graph *g, const GraphView &gv);
 
-// rectangle (rect_acc_kernel) and pentagon (pent_acc_kernel) by wedge accumulation: same centres, same counter maps
+// A CentrePlan (the logic: gm_centre_plan.h) is built in locals -- a call that fails leaves the handle as it was.  Its last step: both task lists onto the device
+static int upload_centre_tasks(const CentreTasks &t, CentrePlan &pl) {
+  if (int rc = upload(pl.d_acc_tasks, t.acc_tasks)) return rc;
+  if (int rc = upload(pl.d_lds_tasks, t.lds_tasks)) return rc;
+  pl.n_acc_tasks = t.acc_tasks.size();
+  pl.n_lds_tasks = t.lds_tasks.size();
+  pl.n_cut = t.n_cut;
+  pl.ready = true;
+  return GM_OK;
+}
+static int max_lds_ranges(int limit) {
+  const char *e = gm_opt("GM_RECT_LDS_RANGES");
+  return e ? std::max(1, std::min(limit, std::atoi(e))) : limit;
+}
+// rectangle: the 2-path ends in the last ranges of ids (at most kRectLdsRanges) of the centres with >= GM_RECT_LDS_MIN 2-paths are counted in
+// LDS maps (rect_lds_kernel): the ranges, the row bounds, the (centre, range) tasks, rect_acc_kernel's list with those centres in front
+static int ensure_rect_plan(gm_graph *g, const GraphView &gv) {
+  if (g->rect_plan.ready) return GM_OK;
+  OtherSetupScope scope(g);
+  const size_t nv = (size_t)g->nv;
+  unsigned long long lds_min = 4096;
+  if (const char *e = gm_opt("GM_RECT_LDS_MIN")) lds_min = std::strtoull(e, nullptr, 10);
+  const int nblk = (int)((nv + kRectLdsWords - 1) / kRectLdsWords);
+  std::vector<int> bmax((size_t)std::max(nblk, 1), 0);
+  if (nv) {
+    DevOwn<int> d_bmax;
+    HIP_TRY(d_bmax.alloc(sizeof(int) * (size_t)nblk));
+    hipError_t e0 = hipMemset(d_bmax, 0, sizeof(int) * (size_t)nblk);
+    if (e0 == hipSuccess) e0 = launch_rect_blockmax(gv, d_bmax, 0);
+    if (e0 == hipSuccess) e0 = hipMemcpy(bmax.data(), d_bmax, sizeof(int) * (size_t)nblk, hipMemcpyDeviceToHost);
+    if (e0 != hipSuccess) return hip_fail(e0, "rect_blockmax_kernel", __FILE__, __LINE__);
+  }
+  RectLdsRanges rr{};  // (whatever the numbering: tune[6] & GM_T6_AS_NUMBERED runs on the graph as given)
+  rr.n = rect_lds_ranges((long long)g->nv, bmax, kRectLdsWords, max_lds_ranges(kRectLdsRanges), rr.rb, rr.lb);
+  setup_trace("rect: ranges");
+  CentrePlan pl;
+  pl.cut = rr.rb[0];
+  pl.bnd_stride = rr.n + 1;
+  HIP_TRY(pl.d_bnd.alloc(sizeof(int) * (size_t)pl.bnd_stride * std::max<size_t>(nv, 1)));
+  std::vector<unsigned long long> est;  // (both estimates: [0, nv) all ends, [nv, 2 nv) the ends below the cut)
+  if (nv) HIP_TRY(launch_rect_bounds(gv, rr, pl.d_bnd, 0));
+  if (int rc = centre_estimates(nv, 2, [&](unsigned long long *d_work) { return launch_rect_work_cut(gv, g->d_idx0, pl.d_bnd, pl.bnd_stride, d_work, 0); }, "rect_work_cut_kernel", est)) return rc;
+  setup_trace("rect: bounds + work estimates");
+  std::vector<int> idx0h(std::max<size_t>(nv, 1));
+  if (nv) HIP_TRY(hipMemcpy(idx0h.data(), g->d_idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
+  const CentreTasks tasks = plan_rect_tasks(nv, est.data(), est.data() + nv, idx0h.data(), rr.rb, rr.n, lds_min, kRectLdsWaves * GM_WAVE, kHeavyCentre);
+  if (int rc = upload_centre_tasks(tasks, pl)) return rc;
+  g->rect_ranges = rr, g->rect_plan = std::move(pl);
+  setup_trace("rect: task lists");
+  return GM_OK;
+}
+// house: the same with ranges of kHouseLdsIds ids (at most kHouseLdsRanges) and plan_house_tasks' policy (GM_HOUSE_WALK_MIN: its 2-paths per walk)
+static int ensure_house_plan(gm_graph *g, const GraphView &gv) {
+  if (g->house_plan.ready) return GM_OK;
+  OtherSetupScope scope(g);
+  const size_t nv = (size_t)g->nv;
+  const char *lds_min_given = gm_opt("GM_RECT_LDS_MIN");
+  const unsigned long long lds_min = lds_min_given ? std::strtoull(lds_min_given, nullptr, 10) : 4096;
+  HouseLdsRanges rr = {0, 0, g->nv};
+  rr.n = house_lds_ranges((long long)g->nv, kHouseLdsIds, max_lds_ranges(kHouseLdsRanges), &rr.cut);
+  CentrePlan pl;
+  pl.cut = rr.cut;
+  pl.bnd_stride = rr.n + 1;
+  HIP_TRY(pl.d_bnd.alloc(sizeof(int) * (size_t)pl.bnd_stride * std::max<size_t>(nv, 1)));
+  std::vector<unsigned long long> est;
+  if (nv) HIP_TRY(launch_house_bounds(gv, rr, pl.d_bnd, 0));
+  if (int rc = centre_estimates(nv, 2, [&](unsigned long long *d_work) { return launch_house_work_cut(gv, pl.d_bnd, pl.bnd_stride, d_work, 0); }, "house_work_cut_kernel", est)) return rc;
+  std::vector<int> deg(nv + 1, 0);  // (the offsets, then their differences)
+  if (nv) HIP_TRY(hipMemcpy(deg.data(), g->d_rp, sizeof(int) * (nv + 1), hipMemcpyDeviceToHost));
+  for (size_t v = 0; v < nv; ++v) deg[v] = deg[v + 1] - deg[v];
+  unsigned long long per_walk = 200;
+  if (const char *e = gm_sweep_env("GM_HOUSE_WALK_MIN")) per_walk = std::strtoull(e, nullptr, 10);
+  const CentreTasks tasks = plan_house_tasks(nv, est.data(), est.data() + nv, deg.data(), rr.n, lds_min, lds_min_given != nullptr, per_walk, kRectLdsWaves * GM_WAVE, kHeavyCentre);
+  if (int rc = upload_centre_tasks(tasks, pl)) return rc;
+  g->house_ranges = rr, g->house_plan = std::move(pl);
+  return GM_OK;
+}
+// what the acc / LDS kernel reads of the plan (the two patterns' parameter structs name these members alike); returns the LDS kernel's share of the tasks
+template <class P>
+static void acc_params_from_plan(P &p, const CentrePlan &pl) {
+  p.tasks = pl.d_acc_tasks;
+  p.n_cut = pl.n_cut;
+  p.cut = pl.cut;
+  p.bnd0 = pl.d_bnd;
+  p.bnd_stride = pl.bnd_stride;
+}
+template <class P, class Ranges>
+static int64_t lds_params_from_plan(P &lp, const LaunchCtx &ctx, const GraphView &gv, const CentrePlan &pl, const Ranges &r) {
+  lp.g = gv;
+  lp.tasks = pl.d_lds_tasks;
+  lp.bnd = pl.d_bnd;
+  lp.r = r;
+  lp.queue = queue_word64(ctx.g, QW64_LDS);  // (its own dequeue word inside the zeroed 64-byte block)
+  lp.counters = ctx.g->d_counters;
+  return take_range(ctx, (int64_t)pl.n_lds_tasks, lp);
+}
+// The acc kernel's grid: one counter map (p.acc_stride = nv counters, rounded up to 64) per wave, wgs_per_cu workgroups per CU, within a budget of
+// 1 / free_div of the free memory on top of the `held` bytes of the handle's maps, at most 32 GB (maps + touched lists); *need = the bytes of its maps
+template <class P>
+static int map_grid(const gm_graph *g, int64_t count, P &p, unsigned bytes_per_counter, unsigned free_div, int wgs_per_cu, size_t held, size_t *need) {
+  p.acc_stride = ((unsigned long long)g->nv + 63ull) & ~63ull;
+  const unsigned long long per_wg = p.acc_stride * bytes_per_counter * kWavesPerBlock;
+  size_t free_b = 0, total_b = 0;
+  (void)hipMemGetInfo(&free_b, &total_b);
+  const unsigned long long budget = std::min<unsigned long long>(32ull << 30, (unsigned long long)free_b / free_div + (unsigned long long)held);
+  const int grid = clamp_grid(count, std::min<long long>((long long)g->cu_count * wgs_per_cu, (long long)std::max<unsigned long long>(1, budget / std::max<unsigned long long>(per_wg, 1))));
+  *need = (size_t)per_wg * (size_t)grid;
+  return grid;
+}
+
+// rectangle (rect_acc_kernel + rect_lds_kernel) and pentagon (pent_acc_kernel) by wedge accumulation: same centres, same counter maps.
+// tune[6] & GM_T6_GLOBAL_MAPS, and the pentagon: every end in the global maps, round 5's form
 static int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm_stats *st, bool pentagon = false) {
   LaunchCtx ctx;
   int rc = begin_launch(cg, la_in, h_out, ctx);
@@ -1386,147 +1498,25 @@ static int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_
   rc = ensure_idx0(g, gv);
   if (rc) return rc;
   const bool lds_maps = !pentagon && !(la->tune[6] & GM_T6_GLOBAL_MAPS);
-  if (!g->d_rect_tasks && !lds_maps) {  // once per graph: 2-path estimate per centre (device), task list (host): heavy first, then light by 4
-    OtherSetupScope scope(g);
-    const int rc_t = build_centre_tasks((size_t)g->nv, [&](unsigned long long *d_work) { return launch_rect_work(gv, g->d_idx0, d_work, 0); }, "rect_work_kernel", g->d_rect_tasks, &g->n_rect_tasks);
-    if (rc_t) return rc_t;
-  }
-  // rectangle: the 2-path ends in the last kRectLdsRanges * kRectLdsRange ids of the centres with >= GM_RECT_LDS_MIN 2-paths are counted in
-  // LDS maps (rect_lds_kernel); tune[6] & GM_T6_GLOBAL_MAPS: every end in the global maps, round 5's form.  Once per graph: the row bounds, the
-  // (centre, range) tasks -- every centre's own top range first, the centres heaviest first -- and rect_acc_kernel's list again with
-  // those centres (now only their ends below the cut) in front.
+  if (!lds_maps) rc = build_centre_tasks(g, [&](unsigned long long *d_work) { return launch_rect_work(gv, g->d_idx0, d_work, 0); }, "rect_work_kernel", g->d_rect_tasks, &g->n_rect_tasks);
+  if (rc) return rc;
   setup_trace("rect: idx0 / old tasks");
-  if (lds_maps && !g->rect_lds_ready) {
-    OtherSetupScope scope(g);
-    const size_t nv = (size_t)g->nv;
-    unsigned long long lds_min = 4096;
-    if (const char *e = gm_opt("GM_RECT_LDS_MIN")) lds_min = std::strtoull(e, nullptr, 10);
-    // the ranges, from the last ids down (the hubs of a graph numbered ascending in degree): a range's counters are as wide as the largest
-    // degree among its vertices needs -- whatever the numbering (tune[6] & GM_T6_AS_NUMBERED runs on the graph as given)
-    RectLdsRanges &rr = g->rect_ranges;
-    memset(&rr, 0, sizeof rr);
-    {
-      const int nblk = (int)((nv + kRectLdsWords - 1) / kRectLdsWords);
-      std::vector<int> bmax((size_t)std::max(nblk, 1), 0);
-      if (nv) {
-        DevOwn<int> d_bmax;
-        HIP_TRY(d_bmax.alloc(sizeof(int) * (size_t)nblk));
-        hipError_t e0 = hipMemset(d_bmax, 0, sizeof(int) * (size_t)nblk);
-        if (e0 == hipSuccess) e0 = launch_rect_blockmax(gv, d_bmax, 0);
-        if (e0 == hipSuccess) e0 = hipMemcpy(bmax.data(), d_bmax, sizeof(int) * (size_t)nblk, hipMemcpyDeviceToHost);
-        if (e0 != hipSuccess) return hip_fail(e0, "rect_blockmax_kernel", __FILE__, __LINE__);
-      }
-      auto max_deg_of_blocks = [&](int b0, int nb) {  // blocks b0 .. b0 + nb - 1 (counted from the top), those that exist
-        int m = 0;
-        for (int b = b0; b < std::min(b0 + nb, nblk); ++b) m = std::max(m, bmax[(size_t)b]);
-        return m;
-      };
-      int blk = 0;
-      int top[kRectLdsRanges + 1], lbs[kRectLdsRanges], n = 0;
-      long long hi = (long long)g->nv;
-      top[0] = (int)hi;
-      int max_ranges = kRectLdsRanges;
-      if (const char *e = gm_opt("GM_RECT_LDS_RANGES")) max_ranges = std::max(1, std::min(kRectLdsRanges, std::atoi(e)));
-      while (hi > 0 && n < max_ranges) {
-        const int lb = max_deg_of_blocks(blk, 4) < 256 ? 3 : max_deg_of_blocks(blk, 2) < 65536 ? 4 : 5;
-        const long long width = (long long)kRectLdsWords << (5 - lb);
-        blk += 1 << (5 - lb);
-        hi = std::max<long long>(0, hi - width);
-        lbs[n] = lb;
-        top[++n] = (int)hi;
-      }
-      rr.n = n;
-      for (int k = 0; k <= n; ++k) rr.rb[k] = top[n - k];
-      for (int k = 0; k < n; ++k) rr.lb[k] = lbs[n - 1 - k];
-    }
-    setup_trace("rect: ranges");
-    g->rect_cut = rr.rb[0];
-    HIP_TRY(g->d_rect_bnd.alloc(sizeof(int) * (size_t)(rr.n + 1) * std::max<size_t>(nv, 1)));
-    DevOwn<unsigned long long> d_work;
-    HIP_TRY(d_work.alloc(sizeof(unsigned long long) * 2 * std::max<size_t>(nv, 1)));
-    std::vector<unsigned long long> work(std::max<size_t>(nv, 1)), wcut(std::max<size_t>(nv, 1));
-    hipError_t e = hipSuccess;
-    if (nv) {
-      e = launch_rect_bounds(gv, rr, g->d_rect_bnd, 0);
-      if (e == hipSuccess) e = launch_rect_work_cut(gv, g->d_idx0, g->d_rect_bnd, rr.n + 1, d_work, 0);  // (both estimates: [0, nv) all ends, [nv, 2 nv) the ends below the cut)
-      if (e == hipSuccess) e = hipMemcpy(work.data(), d_work, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(wcut.data(), d_work + nv, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost);
-    }
-    d_work.reset();
-    if (e != hipSuccess) return hip_fail(e, "rect_bounds_kernel", __FILE__, __LINE__);
-    setup_trace("rect: bounds + work estimates");
-    std::vector<int> lds, rest;
-    for (size_t v = 0; v < nv; ++v) {
-      if (work[v] == 0) continue;
-      if (work[v] >= lds_min && (long long)v > (long long)g->rect_cut) lds.push_back((int)v);
-      else rest.push_back((int)v);
-    }
-    auto by = [](const std::vector<unsigned long long> &w) { return [&w](int a, int b) { return w[(size_t)a] > w[(size_t)b]; }; };
-    std::stable_sort(lds.begin(), lds.end(), by(work));
-    std::stable_sort(rest.begin(), rest.end(), by(work));
-    std::vector<int2> lt;
-    auto range_of = [&](int w) {  // the range that holds id w >= cut
-      int k = 0;
-      while (k + 1 < rr.n && rr.rb[k + 1] <= w) ++k;
-      return k;
-    };
-    // a centre with more neighbours below it than rect_lds_kernel has threads: a task per range, every centre's own top range first; the
-    // others: one task for all their ranges
-    std::vector<int> idx0h(std::max<size_t>(nv, 1));
-    if (nv) HIP_TRY(hipMemcpy(idx0h.data(), g->d_idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
-    const int per_wg = kRectLdsWaves * GM_WAVE;
-    for (int j = 0; j < rr.n; ++j)
-      for (int v : lds) {
-        if (idx0h[(size_t)v] <= per_wg) continue;
-        const int k = range_of(v - 1) - j;
-        if (k >= 0) lt.push_back(make_int2(v, k));
-      }
-    for (int v : lds)
-      if (idx0h[(size_t)v] <= per_wg) lt.push_back(make_int2(v, -1));
-    std::vector<int4> tasks;
-    std::vector<int> ldscut;  // the LDS centres that have ends below the cut (none when the ranges cover the whole graph)
-    for (int v : lds)
-      if (wcut[(size_t)v] > 0) ldscut.push_back(v);
-    std::stable_sort(ldscut.begin(), ldscut.end(), by(wcut));
-    emit_centre_tasks(ldscut, wcut, tasks);
-    g->n_rect_cut = tasks.size();
-    emit_centre_tasks(rest, work, tasks);
-    g->n_rect_cut_tasks = tasks.size();
-    g->n_rect_lds_tasks = lt.size();
-    HIP_TRY(g->d_rect_cut_tasks.alloc(sizeof(int4) * std::max<size_t>(tasks.size(), 1)));
-    if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_rect_cut_tasks, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice));
-    HIP_TRY(g->d_rect_lds_tasks.alloc(sizeof(int2) * std::max<size_t>(lt.size(), 1)));
-    if (!lt.empty()) HIP_TRY(hipMemcpy(g->d_rect_lds_tasks, lt.data(), sizeof(int2) * lt.size(), hipMemcpyHostToDevice));
-    g->rect_lds_ready = true;
-    setup_trace("rect: task lists");
-  }
+  if (lds_maps && (rc = ensure_rect_plan(g, gv))) return rc;
   RectAccParams p;
   memset(&p, 0, sizeof p);
   p.g = gv;
   p.idx0 = g->d_idx0;
-  p.tasks = lds_maps ? g->d_rect_cut_tasks : g->d_rect_tasks;
-  if (lds_maps) {
-    p.n_cut = g->n_rect_cut;
-    p.cut = g->rect_cut;
-    p.bnd0 = g->d_rect_bnd;
-    p.bnd_stride = g->rect_ranges.n + 1;
-  }
-  const int64_t count = take_range(ctx, (int64_t)(lds_maps ? g->n_rect_cut_tasks : g->n_rect_tasks), p);
+  p.tasks = g->d_rect_tasks;
+  if (lds_maps) acc_params_from_plan(p, g->rect_plan);
+  const int64_t count = take_range(ctx, (int64_t)(lds_maps ? g->rect_plan.n_acc_tasks : g->n_rect_tasks), p);
   p.counters = g->d_counters;
   p.queue = queue_word64(g, QW64_MAIN);
-  // one counter map (nv words) per wave, within a memory budget
-  p.acc_stride = ((unsigned long long)g->nv + 63ull) & ~63ull;
-  const unsigned long long per_wg = p.acc_stride * 4ull * kWavesPerBlock;
-  size_t free_b = 0, total_b = 0;
-  (void)hipMemGetInfo(&free_b, &total_b);
-  const unsigned long long budget = std::min<unsigned long long>(32ull << 30, (unsigned long long)free_b / 4 + (unsigned long long)g->rect_acc_bytes);  // (maps + touched lists)
   // (with the heavy centres in LDS what is left for the global maps is light: 1 / 2 / 4 / 8 workgroups per CU measured 11.15 / 10.95 /
   // 11.1 / 11.0 ms for the rectangle of R-MAT-20 -- two, so that a first call does not allocate 2 x 32 GB of maps and lists)
   int acc_wgs_per_cu = lds_maps ? 2 : 8;
   if (const char *e = gm_sweep_env("GM_RECT_ACC_WGS")) acc_wgs_per_cu = std::max(1, std::atoi(e));
-  long long grid = std::min<long long>((long long)g->cu_count * acc_wgs_per_cu, (long long)std::max<unsigned long long>(1, budget / std::max<unsigned long long>(per_wg, 1)));
-  grid = clamp_grid(count, grid);
-  const size_t need = (size_t)per_wg * (size_t)grid;
+  size_t need = 0;
+  const int grid = map_grid(g, count, p, 4, 4, acc_wgs_per_cu, g->rect_acc_bytes, &need);
   if (need > g->rect_acc_bytes) {
     if (int rc_a = grow_dev(g->d_rect_acc, &g->rect_acc_bytes, need)) return rc_a;
     HIP_TRY(hipMemset(g->d_rect_acc, 0, need));  // every launch leaves the maps zeroed again
@@ -1554,31 +1544,21 @@ static int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_
     q.queue = p.queue;
     q.counters = p.counters;
     if (int rc_t = start_timer(ctx)) return rc_t;
-    if (count > 0) HIP_TRY(launch_pent_acc(q, (int)grid, ctx.stream));
-    fill_stats(st, (uint64_t)(g->ne / 2 / ctx.world), (uint64_t)count, (int)grid, 256);
+    if (count > 0) HIP_TRY(launch_pent_acc(q, grid, ctx.stream));
+    fill_stats(st, (uint64_t)(g->ne / 2 / ctx.world), (uint64_t)count, grid, 256);
     return end_launch(ctx, FIN_HALF_SIGNED, 0, h_out, 1, st);
   }
-  RectLdsParams lp;
-  memset(&lp, 0, sizeof lp);
-  int64_t lcount = 0;
-  if (lds_maps) {
-    lp.g = gv;
-    lp.idx0 = g->d_idx0;
-    lp.tasks = g->d_rect_lds_tasks;
-    lcount = take_range(ctx, (int64_t)g->n_rect_lds_tasks, lp);
-    lp.bnd = g->d_rect_bnd;
-    lp.r = g->rect_ranges;
-    lp.queue = queue_word64(g, QW64_LDS);  // (its own dequeue word inside the zeroed 64-byte block)
-    lp.counters = g->d_counters;
-  }
+  RectLdsParams lp{};
+  lp.idx0 = g->d_idx0;
+  const int64_t lcount = lds_maps ? lds_params_from_plan(lp, ctx, gv, g->rect_plan, g->rect_ranges) : 0;
   if (int rc_t = start_timer(ctx)) return rc_t;
   // (workgroups per CU: what its LDS -- the map + 1.5 KB of scratch per wave -- lets run together)
   const int lds_wgs = std::max(1, (int)((160 * 1024) / (kRectLdsWords * 4 + kRectLdsWaves * 1536 + 1024)));
   if (lcount > 0) HIP_TRY(launch_rect_lds(lp, (int)std::min<long long>((long long)g->cu_count * lds_wgs, (long long)lcount), ctx.stream));
   setup_trace("rect: lds kernel enqueued");
-  if (count > 0) HIP_TRY(launch_rect_acc(p, (int)grid, ctx.stream));
+  if (count > 0) HIP_TRY(launch_rect_acc(p, grid, ctx.stream));
   setup_trace("rect: acc kernel enqueued");
-  fill_stats(st, (uint64_t)(g->ne / 2 / ctx.world), (uint64_t)(count + lcount), (int)grid, 256);
+  fill_stats(st, (uint64_t)(g->ne / 2 / ctx.world), (uint64_t)(count + lcount), grid, 256);
   return end_launch(ctx, FIN_COPY, 0, h_out, 1, st);
 }
 
@@ -1603,7 +1583,8 @@ static int ensure_edge_tables(gm_graph *g, const GraphView &gv) {
   return GM_OK;
 }
 
-// house by wedge accumulation (edge_tab_kernel + house_acc_kernel in gm_mine.hip)
+// house by wedge accumulation (edge_tab_kernel + house_acc_kernel + house_lds_kernel in gm_mine.hip); tune[6] & GM_T6_GLOBAL_MAPS: every end in
+// the global maps, round 5's form
 static int run_house_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm_stats *st) {
   LaunchCtx ctx;
   int rc = begin_launch(cg, la_in, h_out, ctx);
@@ -1613,113 +1594,21 @@ static int run_house_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h
   const GraphView gv = graph_view(g);
   rc = ensure_edge_tables(g, gv);
   if (rc) return rc;
-  // the maps of the centres with >= GM_RECT_LDS_MIN 2-paths in LDS, range by range (house_lds_kernel); tune[6] & GM_T6_GLOBAL_MAPS: every end in the
-  // global maps, round 5's form.  Once per graph: ranges of kHouseLdsIds ids from the last id down, the row bounds, the tasks.
   const bool lds_maps = !(la->tune[6] & GM_T6_GLOBAL_MAPS);
-  if (lds_maps && !g->house_lds_ready) {
-    OtherSetupScope scope(g);
-    const size_t nv = (size_t)g->nv;
-    unsigned long long lds_min = 4096;
-    if (const char *e = gm_opt("GM_RECT_LDS_MIN")) lds_min = std::strtoull(e, nullptr, 10);
-    int max_ranges = kHouseLdsRanges;
-    if (const char *e = gm_opt("GM_RECT_LDS_RANGES")) max_ranges = std::max(1, std::min(kHouseLdsRanges, std::atoi(e)));
-    HouseLdsRanges &rr = g->house_ranges;
-    memset(&rr, 0, sizeof rr);
-    // (the row-bound table has n + 1 entries per vertex: at most 4 GB of it)
-    const long long by_memory = std::max<long long>(1, (4ll << 30) / (4ll * (long long)std::max<size_t>(nv, 1)) - 1);
-    rr.n = (int)std::min<long long>(std::min<long long>(max_ranges, by_memory), ((long long)g->nv + kHouseLdsIds - 1) / kHouseLdsIds);
-    rr.nv = g->nv;
-    rr.cut = (int)std::max<long long>(0, (long long)g->nv - (long long)rr.n * kHouseLdsIds);
-    HIP_TRY(g->d_house_bnd.alloc(sizeof(int) * (size_t)(rr.n + 1) * std::max<size_t>(nv, 1)));
-    DevOwn<unsigned long long> d_work;
-    HIP_TRY(d_work.alloc(sizeof(unsigned long long) * 2 * std::max<size_t>(nv, 1)));
-    std::vector<unsigned long long> work(std::max<size_t>(nv, 1)), wcut(std::max<size_t>(nv, 1));
-    std::vector<int> rph(nv + 1, 0);
-    hipError_t e = hipSuccess;
-    if (nv) {
-      e = launch_house_bounds(gv, rr, g->d_house_bnd, 0);
-      if (e == hipSuccess) e = launch_house_work_cut(gv, g->d_house_bnd, rr.n + 1, d_work, 0);
-      if (e == hipSuccess) e = hipMemcpy(work.data(), d_work, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(wcut.data(), d_work + nv, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(rph.data(), g->d_rp, sizeof(int) * (nv + 1), hipMemcpyDeviceToHost);
-    }
-    d_work.reset();
-    if (e != hipSuccess) return hip_fail(e, "house_bounds_kernel", __FILE__, __LINE__);
-    // A centre with at most one neighbour per thread is ONE task that walks every range -- two per walk -- at ~2.5 us of a CU per walk
-    // whatever it finds there, against ~12 ns per 2-path in the global maps (both measured on R-MAT-20): it pays from ~200 2-paths per
-    // walk on.  (On a LiveJournal-sized power-law graph -- 4.8 M vertices, 111 walks -- the fixed 4096 made the house 1.27 x SLOWER than
-    // the global maps.)  A developer option that sets the threshold is taken as given.
-    const bool lds_min_given = gm_opt("GM_RECT_LDS_MIN") != nullptr;
-    unsigned long long per_walk = 200;
-    if (const char *e = gm_sweep_env("GM_HOUSE_WALK_MIN")) per_walk = std::strtoull(e, nullptr, 10);
-    auto lds_min_of = [&](int v) {
-      const int d = rph[(size_t)v + 1] - rph[(size_t)v];
-      if (lds_min_given || d > kRectLdsWaves * GM_WAVE) return lds_min;
-      const int per = d <= 32 ? 4 : 2;  // ranges per walk (house_lds_kernel: 16-bit counters up to 32 neighbours)
-      return std::max<unsigned long long>(lds_min, per_walk * (unsigned long long)((rr.n + per - 1) / per));
-    };
-    std::vector<int> lds, rest;
-    for (size_t v = 0; v < nv; ++v) {
-      if (work[v] == 0) continue;
-      if (rr.n > 0 && work[v] >= lds_min_of((int)v)) lds.push_back((int)v);
-      else rest.push_back((int)v);
-    }
-    auto by = [](const std::vector<unsigned long long> &w) { return [&w](int a, int b) { return w[(size_t)a] > w[(size_t)b]; }; };
-    std::stable_sort(lds.begin(), lds.end(), by(work));
-    std::stable_sort(rest.begin(), rest.end(), by(work));
-    const int per_wg = kRectLdsWaves * GM_WAVE;
-    auto deg = [&](int v) { return rph[(size_t)v + 1] - rph[(size_t)v]; };
-    std::vector<int2> lt;
-    for (int k = rr.n - 1; k >= 0; --k)  // (the hubs' ranges first: they hold most ends)
-      for (int v : lds)
-        if (deg(v) > per_wg) lt.push_back(make_int2(v, k));
-    for (int v : lds)
-      if (deg(v) <= per_wg) lt.push_back(make_int2(v, -1));
-    std::vector<int4> tasks;
-    // (every LDS centre stays in house_acc_kernel's list: its phase 0 -- the table terms and the intersections -- is done there, and of its
-    // 2-paths the ends below the cut; ordered by that remainder, the intersections taken as its degree)
-    std::vector<unsigned long long> wrem(std::max<size_t>(nv, 1), 0);
-    for (int v : lds) wrem[(size_t)v] = wcut[(size_t)v] + (unsigned long long)deg(v);
-    std::stable_sort(lds.begin(), lds.end(), by(wrem));
-    emit_centre_tasks(lds, wrem, tasks);
-    g->n_house_cut = tasks.size();
-    emit_centre_tasks(rest, work, tasks);
-    g->n_house_cut_tasks = tasks.size();
-    g->n_house_lds_tasks = lt.size();
-    HIP_TRY(g->d_house_cut_tasks.alloc(sizeof(int4) * std::max<size_t>(tasks.size(), 1)));
-    if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_house_cut_tasks, tasks.data(), sizeof(int4) * tasks.size(), hipMemcpyHostToDevice));
-    HIP_TRY(g->d_house_lds_tasks.alloc(sizeof(int2) * std::max<size_t>(lt.size(), 1)));
-    if (!lt.empty()) HIP_TRY(hipMemcpy(g->d_house_lds_tasks, lt.data(), sizeof(int2) * lt.size(), hipMemcpyHostToDevice));
-    g->house_lds_ready = true;
-  }
-  if (!g->d_house_tasks && !lds_maps) {  // once per graph
-    OtherSetupScope scope(g);
-    const int rc_t = build_centre_tasks((size_t)g->nv, [&](unsigned long long *d_work) { return launch_house_work(gv, d_work, 0); }, "house_work_kernel", g->d_house_tasks, &g->n_house_tasks);
-    if (rc_t) return rc_t;
-  }
+  rc = lds_maps ? ensure_house_plan(g, gv) : build_centre_tasks(g, [&](unsigned long long *d_work) { return launch_house_work(gv, d_work, 0); }, "house_work_kernel", g->d_house_tasks, &g->n_house_tasks);
+  if (rc) return rc;
   HouseAccParams p;
   memset(&p, 0, sizeof p);
   p.g = gv;
   p.t = g->d_house_t;
   p.tlt = g->d_house_tlt;
-  p.tasks = lds_maps ? g->d_house_cut_tasks : g->d_house_tasks;
-  if (lds_maps) {
-    p.n_cut = g->n_house_cut;
-    p.cut = g->house_ranges.cut;
-    p.bnd0 = g->d_house_bnd;
-    p.bnd_stride = g->house_ranges.n + 1;
-  }
-  const int64_t count = take_range(ctx, (int64_t)(lds_maps ? g->n_house_cut_tasks : g->n_house_tasks), p);
+  p.tasks = g->d_house_tasks;
+  if (lds_maps) acc_params_from_plan(p, g->house_plan);
+  const int64_t count = take_range(ctx, (int64_t)(lds_maps ? g->house_plan.n_acc_tasks : g->n_house_tasks), p);
   p.counters = g->d_counters;
   p.queue = queue_word64(g, QW64_MAIN);
-  p.acc_stride = ((unsigned long long)g->nv + 63ull) & ~63ull;
-  const unsigned long long per_wg = p.acc_stride * 8ull * kWavesPerBlock;
-  size_t free_b = 0, total_b = 0;
-  (void)hipMemGetInfo(&free_b, &total_b);
-  const unsigned long long budget = std::min<unsigned long long>(32ull << 30, (unsigned long long)free_b / 3 + (unsigned long long)g->house_acc_bytes);  // (maps + touched lists)
-  long long grid = std::min<long long>((long long)g->cu_count * (lds_maps ? 4 : 8), (long long)std::max<unsigned long long>(1, budget / std::max<unsigned long long>(per_wg, 1)));
-  grid = clamp_grid(count, grid);
-  const size_t need = (size_t)per_wg * (size_t)grid;
+  size_t need = 0;
+  const int grid = map_grid(g, count, p, 8, 3, lds_maps ? 4 : 8, g->house_acc_bytes, &need);
   if (need > g->house_acc_bytes) {
     g->house_acc_bytes = 0;
     HIP_TRY(g->d_house_acc.alloc(need));
@@ -1729,23 +1618,13 @@ static int run_house_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h
   }
   p.acc = g->d_house_acc;
   p.touched = g->d_house_touched;
-  HouseLdsParams lp;
-  memset(&lp, 0, sizeof lp);
-  int64_t lcount = 0;
-  if (lds_maps) {
-    lp.g = gv;
-    lp.t = g->d_house_t;
-    lp.tasks = g->d_house_lds_tasks;
-    lcount = take_range(ctx, (int64_t)g->n_house_lds_tasks, lp);
-    lp.bnd = g->d_house_bnd;
-    lp.r = g->house_ranges;
-    lp.queue = queue_word64(g, QW64_LDS);  // (its own dequeue word inside the zeroed 64-byte block)
-    lp.counters = g->d_counters;
-  }
+  HouseLdsParams lp{};
+  lp.t = g->d_house_t;
+  const int64_t lcount = lds_maps ? lds_params_from_plan(lp, ctx, gv, g->house_plan, g->house_ranges) : 0;
   if (int rc_t = start_timer(ctx)) return rc_t;
   if (lcount > 0) HIP_TRY(launch_house_lds(lp, (int)std::min<long long>((long long)g->cu_count, (long long)lcount), ctx.stream));
-  if (count > 0) HIP_TRY(launch_house_acc(p, (int)grid, ctx.stream));
-  fill_stats(st, (uint64_t)(g->ne / 2 / ctx.world), (uint64_t)(count + lcount), (int)grid, 256);
+  if (count > 0) HIP_TRY(launch_house_acc(p, grid, ctx.stream));
+  fill_stats(st, (uint64_t)(g->ne / 2 / ctx.world), (uint64_t)(count + lcount), grid, 256);
   return end_launch(ctx, FIN_COPY, 0, h_out, 1, st);
 }
 
@@ -2467,15 +2346,7 @@ static int run_wrect(const gm_graph *sym, const gm_launch *la_in, uint64_t out[2
     HIP_TRY(launch_wrect_mask(g->nv, g->d_rp, g->d_col, range, g->wrect_grp, g->d_wrect_mask, g->cu_count, 0));
     std::vector<int> idx0h(std::max<size_t>(nv, 1));
     if (nv) HIP_TRY(hipMemcpy(idx0h.data(), g->d_idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
-    // the centres with more neighbours below them than the workgroup has threads first, a task per range (hubs are the last ids of the
-    // default numbering: from the last id down, every centre's top range first), then one task per remaining centre that can hold a 4-cycle
-    constexpr int per_wg = kWrectThreads;
-    std::vector<int2> tasks;
-    for (long long v0 = (long long)nv - 1; v0 >= 0; --v0)
-      if (idx0h[(size_t)v0] > per_wg)
-        for (int k = (int)((v0 - 1) / range); k >= 0; --k) tasks.push_back(make_int2((int)v0, k));
-    for (long long v0 = (long long)nv - 1; v0 >= 0; --v0)
-      if (idx0h[(size_t)v0] >= 2 && idx0h[(size_t)v0] <= per_wg) tasks.push_back(make_int2((int)v0, -1));
+    const std::vector<int2> tasks = wrect_tasks(idx0h.data(), nv, range, kWrectThreads);  // (the hubs' per-range tasks first)
     g->n_wrect_tasks = tasks.size();
     HIP_TRY(g->d_wrect_tasks.alloc(sizeof(int2) * std::max<size_t>(tasks.size(), 1)));
     if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_wrect_tasks, tasks.data(), sizeof(int2) * tasks.size(), hipMemcpyHostToDevice));
