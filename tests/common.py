@@ -43,6 +43,26 @@ def random_graph(nv, ne_target, seed):
     return csr_from_pairs(nv, s, d)
 
 
+def renumbering(keydeg, descending=False):
+    """new id of every vertex under get_relabeled: ids by (degree, old id), ascending (descending: the same order counted from the top)"""
+    nv = len(keydeg)
+    order = np.lexsort((np.arange(nv), keydeg))
+    newid = np.empty(nv, dtype=np.int64)
+    newid[order] = (nv - 1 - np.arange(nv)) if descending else np.arange(nv)
+    return newid
+
+
+def renumbered_expected(g, keydeg, descending):
+    """numpy restatement of get_relabeled: ids by (degree, old id), rows ascending"""
+    nv = g.V()
+    newid = renumbering(keydeg, descending)
+    src = np.repeat(np.arange(nv), np.diff(g.row_ptr))
+    keys = np.sort((newid[src] << 32) | newid[g.col_idx.astype(np.int64)])
+    rp = np.zeros(nv + 1, dtype=np.int64)
+    np.cumsum(np.bincount(keys >> 32, minlength=nv), out=rp[1:])
+    return rp, (keys & 0xFFFFFFFF).astype(np.int32)
+
+
 def MotifSolverE(g, k, tune=None, **kw):
     """k-motif through the ENUMERATION kernels (tune[6] & 0x10000000: automine_3motif's loop nest, one bounded intersection per edge of
     the symmetric graph); gm_motif's default for k = 3 is the reference's formula solver (triangles of the DAG, wedges derived)"""
@@ -51,3 +71,33 @@ def MotifSolverE(g, k, tune=None, **kw):
     t = (list(tune or []) + [0] * 7)[:7]
     t[6] |= 0x10000000
     return MotifSolver(g, k, tune=t, **kw)
+
+
+def check_rows(label, got, want):
+    """two int32[n, 3] lists of triangles are the same rows in the same order; the first differing rows are printed before the assertion"""
+    got, want = np.asarray(got), np.asarray(want)
+    same = got.shape == want.shape and got.dtype == want.dtype
+    bad = np.flatnonzero((got != want).any(axis=1)) if same else np.zeros(0, np.int64)
+    print(f"{label}: got {got.shape} {got.dtype} want {want.shape} {want.dtype}, {bad.size} rows differ, first at {bad[:3].tolist()}: "
+          f"got {got[bad[:3]].tolist() if same else '-'} want {want[bad[:3]].tolist() if same else '-'}", flush=True)
+    assert same and bad.size == 0, label
+
+
+def list_windows(sym, size, upto, sentinel=-7):
+    """gm_tc_list in the windows [0, size), [size, 2 size), ... up to `upto` triangles: every call writes behind the one before it into one
+    device buffer (pre-filled with the sentinel, with slack), which comes back once"""
+    import ctypes as C
+
+    import torch
+
+    from graphminer_amd import _lib
+
+    buf = torch.full((3 * upto + 64,), sentinel, dtype=torch.int32, device=f"cuda:{sym.device}")
+    lib, written = _lib.load(), C.c_uint64(0)
+    for f in range(0, upto, size):
+        want = min(size, upto - f)
+        rc = lib.gm_tc_list(sym.handle, None, f, want, buf.data_ptr() + 12 * f, None, C.byref(written), None)
+        assert (rc, int(written.value)) == (_lib.GM_OK, want), (f, rc, written.value)
+    host = buf.cpu().numpy()
+    assert bool((host[3 * upto:] == sentinel).all()), "nothing behind the last window"
+    return host[:3 * upto].reshape(-1, 3)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import twin_graphs as T
-from common import GOLDEN, load_graph
+from common import GOLDEN, check_rows, list_windows, load_graph
 from graphminer_amd import Graph, SglSolver, TCSolver, _lib, ktruss, tc_list, tc_local
 from graphminer_amd.rmat import csr_from_pairs
 from list_ref import list_ref, sort_rows
@@ -49,15 +49,6 @@ def check(label, got, want):
     assert got == want, label
 
 
-def check_rows(label, got, want):
-    got, want = np.asarray(got), np.asarray(want)
-    same = got.shape == want.shape and got.dtype == want.dtype
-    bad = np.flatnonzero((got != want).any(axis=1)) if same else np.zeros(0, np.int64)
-    print(f"{label}: got {got.shape} {got.dtype} want {want.shape} {want.dtype}, {bad.size} rows differ, first at {bad[:3].tolist()}: "
-          f"got {got[bad[:3]].tolist() if same else '-'} want {want[bad[:3]].tolist() if same else '-'}", flush=True)
-    assert same and bad.size == 0, label
-
-
 def ascending(tri):
     return bool((tri[:, 0] < tri[:, 1]).all() and (tri[:, 1] < tri[:, 2]).all())
 
@@ -71,19 +62,7 @@ def raw_call(sym, first, cap, buf, la=None):
 
 
 def windows(sym, size, upto):
-    """the windows [0, size), [size, 2 size), ... up to `upto` triangles: every call writes behind the one before it into one device
-    buffer (pre-filled, with slack), which comes back once"""
-    import torch
-
-    buf = torch.full((3 * upto + 64,), SENTINEL, dtype=torch.int32, device=f"cuda:{sym.device}")
-    lib, written = _lib.load(), C.c_uint64(0)
-    for f in range(0, upto, size):
-        want = min(size, upto - f)
-        rc = lib.gm_tc_list(sym.handle, None, f, want, buf.data_ptr() + 12 * f, None, C.byref(written), None)
-        assert (rc, int(written.value)) == (_lib.GM_OK, want), (f, rc, written.value)
-    host = buf.cpu().numpy()
-    assert bool((host[3 * upto:] == SENTINEL).all()), "nothing behind the last window"
-    return host[:3 * upto].reshape(-1, 3)
+    return list_windows(sym, size, upto, SENTINEL)
 
 
 @pytest.mark.parametrize("name", SMALL)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from common import GOLDEN, GRAPH_NAMES, MotifSolverE, load_graph, random_graph
+from common import GOLDEN, GRAPH_NAMES, MotifSolverE, load_graph, random_graph, renumbered_expected as _renumbered_expected
 from graphminer_amd import CliqueSolver, DeviceGraph, Graph, MotifSolver, SglSolver, TCSolver, _lib
 from graphminer_amd._lib import dev_option
 from graphminer_amd.rmat import csr_from_pairs, rmat_csr_numpy
@@ -1163,19 +1163,6 @@ def test_edge_supports_from_the_key_stream(dev, devopt):
             per = n // world
             assert sum(diamond_support_finish(s, total[r * per:(r + 1) * per].contiguous().data_ptr(), per) for r in range(world)) == want
     devopt("GM_SUP_STREAM", None)
-
-
-def _renumbered_expected(g, keydeg, descending):
-    """numpy restatement of get_relabeled: ids by (degree, old id), rows ascending"""
-    nv = g.V()
-    order = np.lexsort((np.arange(nv), keydeg))
-    newid = np.empty(nv, dtype=np.int64)
-    newid[order] = (nv - 1 - np.arange(nv)) if descending else np.arange(nv)
-    src = np.repeat(np.arange(nv), np.diff(g.row_ptr))
-    keys = np.sort((newid[src] << 32) | newid[g.col_idx.astype(np.int64)])
-    rp = np.zeros(nv + 1, dtype=np.int64)
-    np.cumsum(np.bincount(keys >> 32, minlength=nv), out=rp[1:])
-    return rp, (keys & 0xFFFFFFFF).astype(np.int32)
 
 
 def _hub_graph(seed, hub_degs, nv=9000, background=30000):
