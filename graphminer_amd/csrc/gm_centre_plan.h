@@ -1,5 +1,5 @@
 // gm_centre_plan.h -- the once-per-graph plans of the map solvers (rectangle / house by wedge accumulation, the weighted 4-cycles) as pure
-// functions of host arrays: no HIP runtime, no globals, no developer options (gm_launch.hip reads those and builds the device side).  A slip
+// functions of host arrays: no HIP runtime, no globals, no developer options (gm_solve_sgl.hip reads those and builds the device side).  A slip
 // here costs time, not counts, so no parity test sees it: tests/centre_plan_host_check.cc checks them with a plain host compiler.
 #pragma once
 #include <hip/hip_vector_types.h>

@@ -1,7 +1,10 @@
 // gm_host.h -- host-side internals shared by the translation units behind the C ABI (include/graphminer_amd.h):
 //   gm_graph.hip   handle, upload / adopt, orientation, neighbour sort, degree renumbering      (GraphGPU::init, Graph::orientation)
 //   gm_tables.hip  task-chunk tables, edge descriptors, task lists, k-clique plans, partitions  (Graph::init_edgelist, Scheduler)
-//   gm_launch.hip  the solvers: launch prologue / epilogue, run_pattern, gm_tc / gm_sgl / gm_clique / gm_motif
+//   gm_launch.hip  the launch layer (interface: gm_launch.h, for the three solver units only): launch prologue / epilogue, run_pattern,
+//                  gm_kernel_times, gm_tc / gm_clique / gm_motif, and every kernel of the layer
+//   gm_solve_sgl.hip    the SgL family: gm_sgl, the rectangle / house / pentagon map solvers, gm_diamond_support_*, gm_sgl4 / 5 / 6   (host code only)
+//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list                                                      (host code only)
 //   gm_tools.hip   set-op batch, R-MAT generator, PMC / issue-rate calibration kernels, self test
 // Host-side counterparts in the reference:
 //   GraphGPU::init / init_edgelist          include/graph_gpu.h:69-194
@@ -213,6 +216,19 @@ struct ChunkTable {
   std::list<ShareOrder> shares;  // the shares handed out so far (get_share_order)
 };
 int table_host_views(gm_graph *g, ChunkTable *t);  // gm_tables.hip
+// GM_PART_VERTEX: the contiguous run of chunks whose first vertex lies in the vertex range of rank / world (after table_host_views)
+static inline void chunk_range_of_vertex_share(const ChunkTable *tb, int nv, int rank, int world, long long *first, long long *count) {
+  auto first_chunk_at = [&](long long v) {
+    long long lo = 0, hi = (long long)tb->n;
+    while (lo < hi) {
+      const long long mid = (lo + hi) / 2;
+      if (tb->first_vertex[(size_t)mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+  };
+  *first = first_chunk_at((long long)nv * rank / world);
+  *count = first_chunk_at((long long)nv * (rank + 1) / world) - *first;
+}
 // the share of rank / world under `policy` (round robin: every world-th CHUNK of the order; range: a contiguous run of chunks), cut from
 // dequeue order `which` (0 / 1, or -1 = record order); needs the device twins of the per-record scalars (a device-built table)
 int get_share_order(gm_graph *g, ChunkTable *t, int world, int rank, int policy, int which, const ShareOrder **out);
@@ -269,7 +285,7 @@ struct BitmapSet {
   unsigned long long words = 0;
 };
 
-// The plan of a map solver whose heavy centres count in LDS maps (rectangle, house; ensure_rect_plan / ensure_house_plan, gm_launch.hip)
+// The plan of a map solver whose heavy centres count in LDS maps (rectangle, house; ensure_rect_plan / ensure_house_plan, gm_solve_sgl.hip)
 struct CentrePlan {             // once per graph, published whole
   DevOwn<int> d_bnd;            // nv x (n + 1) row bounds
   DevOwn<int2> d_lds_tasks;     // (centre, range) tasks of the *_lds_kernel
@@ -328,7 +344,6 @@ struct gm_graph {
   DevOwn<unsigned> d_w5sup, d_w5ed;
   DevOwn<int> d_w5deg;
   DevOwn<unsigned long long> d_w5tv2, d_w5out;
-  bool w5_tri = false, w5_vert = false;  // what the PAT_WTRI launch in flight was asked for (gm_sgl5_raw)
   // the 6-vertex closed forms (gm_wrect.hip, gm_sgl6_raw).  On the DAG of the 5-vertex pass: e1 per vertex.  On the graph the weighted
   // 4-cycle kernel walks (the copy numbered ascending in degree, or the handle itself): its plan, built once -- ids per range
   // (GM_WRECT_RANGE), ranges per bit of the row masks, the masks, the task list
@@ -610,5 +625,3 @@ int ensure_tri_per_edge(gm_graph *g);  // (gm_launch.hip) |N+(u) ^ N+(v)| averag
 unsigned long long task_part_cap(gm_graph *g, int world);
 int clique_wide_min_words();
 int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, unsigned long long part_cap, CliquePlan **out);
-int run_pattern(gm::Pattern pat, const gm_graph *cg, const gm_launch *la, int k, uint64_t *h_out, int nout, gm_stats *st, int fin_mode = -1,
-                unsigned long long fin_base = 0, unsigned *sup_out = nullptr);  // gm_launch.hip (sup_out: PAT_SUPPORT_PART's buffer)

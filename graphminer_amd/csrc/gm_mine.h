@@ -306,7 +306,7 @@ struct HouseAccParams {
 // house, the (count | weighted sum) maps of the heavy centres in LDS (gm_mine.hip house_lds_kernel): ranges of kHouseLdsIds ids with one 64-bit
 // word each -- the same packing as the global maps -- from the last id down; tasks as for the rectangle (RectLdsParams)
 constexpr int kHouseLdsIds = 16384;  // 128 KB of 64-bit counters
-constexpr int kHouseLdsRanges = 256;  // at most: the last 4 M ids (and a row-bound table of at most 4 GB: gm_launch.hip)
+constexpr int kHouseLdsRanges = 256;  // at most: the last 4 M ids (and a row-bound table of at most 4 GB: gm_solve_sgl.hip)
 struct HouseLdsRanges {
   int n, cut, nv;  // range k = ids [rb(k), rb(k + 1)), ascending; rb(0) = cut, rb(n) = nv
   __host__ __device__ int rb(int k) const {

@@ -1,0 +1,211 @@
+// gm_solve_local.hip -- local counts, the k-truss and the triangle listing over the launch layer (gm_launch.h): gm_tc_local, gm_ktruss,
+// gm_truss_decompose, gm_tc_list.  Host code only: the kernels are gm_local.hip's and gm_list.hip's, so this unit has no code object and no warm-up.
+#include "gm_launch.h"
+
+// ---- local counts and the k-truss (gm_local.hip; DESIGN.md "Local counts and k-truss") ----------------------------------------------------
+// the arrays of the symmetric handle, in the caller's entry order (peel: also the marks, the frontier list and the round counters)
+static int ensure_local_buffers(gm_graph *g, bool peel, bool truss) {
+  std::lock_guard<std::mutex> lk(g->mu);
+  HIP_TRY(hipSetDevice(g->device));
+  const size_t ne = (size_t)std::max<long long>(g->ne, 1);
+  if (!g->d_lent) HIP_TRY(g->d_lent.alloc(sizeof(unsigned) * ne));
+  if (peel) {
+    if (!g->d_lrev) HIP_TRY(g->d_lrev.alloc(sizeof(int) * ne));
+    if (!g->d_lmark) HIP_TRY(g->d_lmark.alloc(ne));
+    if (!g->d_lfront) HIP_TRY(g->d_lfront.alloc(sizeof(int) * (ne / 2 + 1)));
+    if (!g->d_lcnt) HIP_TRY(g->d_lcnt.alloc(64));
+  }
+  if (truss && !g->d_ltruss) HIP_TRY(g->d_ltruss.alloc(sizeof(unsigned) * ne));
+  return GM_OK;
+}
+
+// the refusals the three calls share, in the order of the header
+static int local_refusals(const gm_graph *sym, const gm_launch *la) {
+  if (!sym) return GM_ERR_INVALID;
+  if (int rc = reject_big(sym)) return rc;
+  if (la && (la->world > 1 || la->d_counts)) return GM_ERR_UNSUPPORTED;  // (the arrays are whole-graph results, read back by the call)
+  return GM_OK;
+}
+
+// The supports of every entry of the oriented copy -- one rank's PAT_SUPPORT_PART into run_on->d_lsup, every path of the triangle pass --
+// and their way back: `c` is the open launch on the SYMMETRIC handle, the mapping kernel writes `out` (caller's entry order) and adds the
+// sum of the supports to its counters[0].
+static int local_supports(gm_graph *g, const gm_launch *l2, SubLaunches &sub, gm_graph **run_on_out) {
+  gm_graph *run_on = nullptr;
+  if (int rc = diamond_run_on(g, l2, &run_on)) return rc;
+  {
+    std::lock_guard<std::mutex> lk(run_on->mu);
+    if (!run_on->d_lsup) HIP_TRY(run_on->d_lsup.alloc(sizeof(unsigned) * (size_t)diamond_support_entries(run_on->ne, 1)));
+  }
+  uint64_t dummy = 0;
+  if (int rc = sub.run([&](gm_stats *s) { return run_pattern({PAT_SUPPORT_PART, 3, -1, 0, run_on->d_lsup}, run_on, l2, &dummy, 1, s); })) return rc;
+  *run_on_out = run_on;
+  return GM_OK;
+}
+static int local_map(LaunchCtx &c, gm_graph *run_on, unsigned *out) {
+  gm_graph *g = c.g;
+  const gm_graph *dag = g->dag_cache;
+  if (run_on != dag && !run_on->d_newid) return GM_ERR_INVALID;  // (a renumbered copy always remembers its numbering)
+  LocalMapParams mp;
+  memset(&mp, 0, sizeof mp);
+  mp.nv = g->nv; mp.ne = g->ne; mp.rp = g->d_rp; mp.col = g->d_col;
+  mp.newid = run_on != dag ? run_on->d_newid : nullptr;  // (the oriented copy keeps the symmetric graph's ids: one level of numbering)
+  mp.drp = run_on->d_rp; mp.dcol = run_on->d_col; mp.dsup = run_on->d_lsup;
+  mp.topo = run_on->topo_state == 1 ? 1 : 0;
+  mp.out = out; mp.sum = g->d_counters;
+  HIP_TRY(launch_local_map(mp, g->cu_count, c.stream));
+  return GM_OK;
+}
+
+extern "C" int gm_tc_local(const gm_graph *sym, const gm_launch *la, uint64_t *d_vertex_tri, uint32_t *d_entry_sup, uint64_t *total, gm_stats *st) {
+  if (int rc = local_refusals(sym, la)) return rc;
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  uint64_t sum = 0;
+  if (total) *total = 0;
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, &sum, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+  if (sym->ne == 0) {
+    if (d_vertex_tri && sym->nv > 0) HIP_TRY(hipMemsetAsync(d_vertex_tri, 0, sizeof(uint64_t) * (size_t)sym->nv, ctx.stream));
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    return GM_OK;
+  }
+  if (int rc = ensure_local_buffers(g, false, false)) return rc;
+  SubLaunches sub;
+  gm_graph *run_on = nullptr;
+  if (int rc = local_supports(g, &l2, sub, &run_on)) return rc;
+  HIP_TRY(hipMemsetAsync(g->d_counters, 0, kCounterBlockBytes, ctx.stream));  // (a first call oriented the graph since begin_launch)
+  if (int rc = start_timer(ctx)) return rc;
+  unsigned *ent = d_entry_sup ? d_entry_sup : g->d_lent;
+  if (int rc = local_map(ctx, run_on, ent)) return rc;
+  if (d_vertex_tri) HIP_TRY(launch_local_vertices(g->nv, g->d_rp, ent, (unsigned long long *)d_vertex_tri, g->cu_count, ctx.stream));
+  if (int rc = sub.run([&](gm_stats *s) { return end_launch(ctx, FIN_COPY, 0, &sum, 1, s); })) return rc;
+  if (total) *total = sum / 6ull;  // sum_e t(e) over both directions = 2 sum_v T_v = 6 T
+  if (st) st->kernel_ms = sub.ms;
+  return GM_OK;
+}
+
+// gm_ktruss (decompose = false) and gm_truss_decompose: the supports in the caller's order, then whole-frontier rounds.  One 8-byte word
+// comes back per round: the frontier's size and the smallest support that stays alive.
+static int run_truss(const gm_graph *sym, bool decompose, int k_in, const gm_launch *la, uint32_t *d_out, uint64_t *n_edges, int32_t *k_max,
+                     int32_t *rounds_out, gm_stats *st) {
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  if (n_edges) *n_edges = 0;
+  if (k_max) *k_max = 0;
+  if (rounds_out) *rounds_out = 0;
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  uint64_t alive = 0;
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, &alive, ctx)) return rc;
+  if (sym->ne == 0) return GM_OK;
+  if (int rc = ensure_local_buffers(g, true, decompose)) return rc;
+  SubLaunches sub;
+  gm_graph *run_on = nullptr;
+  if (int rc = local_supports(g, &l2, sub, &run_on)) return rc;
+  if (int rc = start_timer(ctx)) return rc;
+  hipStream_t stream = ctx.stream;
+  if (int rc = local_map(ctx, run_on, g->d_lent)) return rc;
+  if (!g->lrev_ready) {  // (once per handle)
+    HIP_TRY(launch_local_rev(g->nv, g->ne, g->d_rp, g->d_col, g->d_lrev, g->cu_count, stream));
+    g->lrev_ready = true;
+  }
+  HIP_TRY(launch_local_peel_init(g->ne, g->d_lrev, g->d_lmark, g->cu_count, stream));
+  LocalPeelParams pp;
+  memset(&pp, 0, sizeof pp);
+  pp.nv = g->nv; pp.ne = g->ne; pp.rp = g->d_rp; pp.col = g->d_col; pp.rev = g->d_lrev;
+  pp.sup = g->d_lent; pp.mark = g->d_lmark; pp.front = g->d_lfront; pp.cnt = g->d_lcnt;
+  pp.truss = decompose ? g->d_ltruss : nullptr;
+  long long k = decompose ? 3 : k_in, kmax = 0;
+  int rounds = 0;
+  for (;;) {
+    unsigned word[2] = {0u, 0u};
+    for (;;) {  // the rounds of level k: threshold k - 2
+      pp.thr = (unsigned)(k - 2);
+      pp.level = (unsigned)(k - 1);
+      HIP_TRY(hipMemsetAsync(g->d_lcnt, 0, 8, stream));
+      HIP_TRY(launch_local_mark(pp, g->cu_count, stream));
+      HIP_TRY(hipMemcpyAsync(word, g->d_lcnt, sizeof word, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      ++rounds;
+      if (word[0] == 0u) break;
+      kmax = k - 1;
+      HIP_TRY(launch_local_peel(pp, word[0], g->cu_count, stream));
+    }
+    if (!decompose || word[1] == 0u) break;  // (decompose: nothing is alive any more)
+    // every alive edge has support >= m: the (m + 2)-truss still holds all of them, the first level that removes one is m + 3
+    k = (long long)(0xFFFFFFFFu - word[1]) + 3;
+  }
+  HIP_TRY(hipMemsetAsync(g->d_counters, 0, 8, stream));  // (the mapping kernel's sum is not a result of these calls)
+  HIP_TRY(launch_local_truss_out(pp, d_out, g->d_counters, g->cu_count, stream));
+  if (int rc = sub.run([&](gm_stats *s) { return end_launch(ctx, FIN_COPY, 0, &alive, 1, s); })) return rc;
+  if (n_edges) *n_edges = alive;
+  if (k_max) *k_max = (int32_t)kmax;  // (the last level that removed an edge)
+  if (rounds_out) *rounds_out = rounds;
+  if (st) st->kernel_ms = sub.ms;
+  return GM_OK;
+}
+
+extern "C" int gm_ktruss(const gm_graph *sym, int k, const gm_launch *la, uint32_t *d_entry_sup, uint64_t *n_edges, int32_t *rounds, gm_stats *st) {
+  if (!sym || k < 2) return GM_ERR_INVALID;
+  if (int rc = local_refusals(sym, la)) return rc;
+  return run_truss(sym, false, k, la, d_entry_sup, n_edges, nullptr, rounds, st);
+}
+
+extern "C" int gm_truss_decompose(const gm_graph *sym, const gm_launch *la, uint32_t *d_entry_truss, int32_t *k_max, int32_t *rounds, gm_stats *st) {
+  if (!sym || !d_entry_truss) return GM_ERR_INVALID;
+  if (int rc = local_refusals(sym, la)) return rc;
+  return run_truss(sym, true, 0, la, d_entry_truss, nullptr, k_max, rounds, st);
+}
+
+// ---- triangle listing (gm_list.hip; DESIGN.md "Triangle listing") -----------------------------------------------------------------------
+// On the oriented copy as numbered: it keeps the caller's ids, so a match is written as it is found.  The count stage runs once per handle
+// (the batches' first slots stay on the SYMMETRIC handle); a window is one fill launch that walks only the batches it meets.
+extern "C" int gm_tc_list(const gm_graph *sym, const gm_launch *la, uint64_t first, uint64_t cap, int32_t *d_tri, uint64_t *total,
+                          uint64_t *n_written, gm_stats *st) {
+  if (total) *total = 0;
+  if (n_written) *n_written = 0;
+  if (int rc = local_refusals(sym, la)) return rc;
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  uint64_t unused = 0;
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, &unused, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+  if (sym->ne == 0) return GM_OK;
+  if (const int rc_dag = ensure_dag_cache(g)) return rc_dag;  // (the oriented copy, cached on the handle)
+  const gm_graph *dag = g->dag_cache;
+  if (int rc = reject_big(dag)) return rc;
+  ListParams lp;
+  memset(&lp, 0, sizeof lp);
+  lp.nv = dag->nv; lp.ne = dag->ne; lp.rp = dag->d_rp; lp.col = dag->d_col;
+  if (int rc = start_timer(ctx)) return rc;
+  if (!g->list_ready) {  // (once per handle)
+    if (dag->ne > 0) {
+      const size_t nb = (size_t)((dag->ne + GM_WAVE - 1) / GM_WAVE);
+      {
+        std::lock_guard<std::mutex> lk(g->mu);
+        if (!g->d_list_off) HIP_TRY(g->d_list_off.alloc(sizeof(unsigned long long) * (nb + 1)));
+      }
+      lp.off = g->d_list_off;
+      HIP_TRY(list_count_scan(lp, g->cu_count, ctx.stream));
+      HIP_TRY(hipMemcpyAsync(&g->list_total, g->d_list_off + nb, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx.stream));
+      HIP_TRY(hipStreamSynchronize(ctx.stream));
+    }
+    g->list_ready = true;
+  }
+  const uint64_t T = g->list_total;
+  const uint64_t nw = (d_tri && first < T) ? std::min<uint64_t>(cap, T - first) : 0;
+  if (nw > 0) {
+    lp.off = g->d_list_off; lp.first = first; lp.nw = nw; lp.tri = d_tri;
+    HIP_TRY(launch_list_fill(lp, g->cu_count, ctx.stream));
+  }
+  gm_stats s;
+  memset(&s, 0, sizeof s);
+  if (int rc = end_launch(ctx, FIN_COPY, 0, &unused, 1, &s)) return rc;
+  if (total) *total = T;
+  if (n_written) *n_written = nw;
+  if (st) st->kernel_ms = s.kernel_ms;
+  return GM_OK;
+}

@@ -2336,17 +2336,7 @@ int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, un
     if (policy == GM_PART_VERTEX) {
       const int rc = table_host_views(g, tb);
       if (rc) return rc;
-      const long long vlo = (long long)g->nv * rank / world, vhi = (long long)g->nv * (rank + 1) / world;
-      auto first_chunk_at = [&](long long v) {
-        long long lo = 0, hi = n;
-        while (lo < hi) {
-          const long long mid = (lo + hi) / 2;
-          if (tb->first_vertex[(size_t)mid] < v) lo = mid + 1; else hi = mid;
-        }
-        return lo;
-      };
-      first = first_chunk_at(vlo);
-      count = first_chunk_at(vhi) - first;
+      chunk_range_of_vertex_share(tb, g->nv, rank, world, &first, &count);
     } else {
       gm_partition((int64_t)n, rank, world, policy, (int64_t *)&first, (int64_t *)&step, (int64_t *)&count);
     }

@@ -132,7 +132,7 @@ def test_diamond_matches_reference(gg):
 @pytest.mark.parametrize("pattern", ["tailedtriangle", "4path", "3star"])
 def test_sgl_four_vertex_patterns_from_the_per_edge_sums(gg, pattern):
     """tailedtriangle.h / 4path.h / 3star.h (src/sgl/omp_base.cc:21-31): the HIP path takes them from the four per-edge sums of the formula
-    4-motif (one |N(u) ^ N(v)| per edge, csrc/gm_launch.hip gm_sgl); goldens from sgl_omp_base, the oracle restates the loop nests"""
+    4-motif (one |N(u) ^ N(v)| per edge, csrc/gm_solve_sgl.hip gm_sgl); goldens from sgl_omp_base, the oracle restates the loop nests"""
     name, g, sym, _ = gg
     e = GOLDEN[name]
     if pattern not in e:

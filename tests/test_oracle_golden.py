@@ -44,7 +44,7 @@ def test_diamond_rectangle(graphs):
 
 def test_tailedtriangle_4path_3star(graphs):
     """the other 4-vertex SgL patterns (src/sgl/cpu_kernels/tailedtriangle.h, 4path.h, 3star.h): oracle = sgl_omp_base on every golden graph,
-    = the closed forms the HIP path uses (sums of the per-edge quantities of the formula 4-motif, csrc/gm_launch.hip gm_sgl)"""
+    = the closed forms the HIP path uses (sums of the per-edge quantities of the formula 4-motif, csrc/gm_solve_sgl.hip gm_sgl)"""
     name, g, sym, _ = graphs
     e = GOLDEN[name]
     if "3star" not in e:
