@@ -1,8 +1,8 @@
 // gm_cli.cc -- one source for the whole command-line surface of the HIP solvers.
 //
-// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
+// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
 //   tc_gpu_base tc_multigpu tc_multigpu_base | sgl_gpu_base sgl_multigpu | clique_gpu_base clique_multigpu kcl_gpu_base |
-//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base
+//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base | cliquelocal_gpu_base
 // The observable behaviour -- positional argv, defaults, usage text, banner and FINAL result lines -- is that of the
 // reference mains (src/triangle/main.cc:7-27, src/sgl/main.cc:9-35, src/clique/main.cc:8-28, src/motif/main.cc:9-31,
 // Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.  truss_gpu_base <graph prefix> [k] has no
@@ -11,6 +11,9 @@
 // banner and the last line `total_num = N` are sgl_gpu_base's.
 // tclist_gpu_base <graph prefix> [out.bin [first [cap]]] lists the triangles (gm_tc_list): `total_num_triangles = N` in tc_gpu_base's
 // spelling, then `triangles_written = M`; with out.bin the M triples of the window go there as raw little-endian int32, a < b < c.
+// cliquelocal_gpu_base <graph prefix> <k> [out prefix] counts the k-cliques at every vertex and on every edge (gm_clique_local):
+// `total_num_cliques = N` in kcl_gpu_base's spelling, then `max_vertex_cliques = A` and `max_edge_cliques = B`; with an out prefix the
+// per-vertex counts go to <out>.vertex.u64 and the per-entry counts to <out>.entry.u64 as raw little-endian uint64.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -27,11 +30,12 @@
 #define GM_TRUSS 5
 #define GM_SGL6 6
 #define GM_TCLIST 7
-#if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST)
+#define GM_CLIQUELOCAL 8
+#if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL)
 #include <hip/hip_runtime_api.h>
 #endif
 #ifndef GM_APP
-#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST"
+#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL"
 #endif
 
 namespace {
@@ -44,7 +48,7 @@ struct Cli {
   int adj_sorted = 1;  // [adj_sorted(1)] (tc only)
 };
 
-#if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST
+#if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_CLIQUELOCAL
 // positional layout: TC has no <second>; the others do
 Cli parse(int argc, char **argv, bool has_second) {
   Cli c;
@@ -77,6 +81,9 @@ void usage_and_exit(const char *self) {
 #elif GM_APP == GM_TCLIST
   std::printf("Usage: %s <graph prefix> [out.bin [first [cap]]]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph triangles.bin 0 1000000\n", self);
+#elif GM_APP == GM_CLIQUELOCAL
+  std::printf("Usage: %s <graph prefix> <k> [out prefix]\n", self);
+  std::printf("Example: %s /graph_inputs/mico/graph 4 cliques\n", self);
 #else
   std::printf("Usage: %s<graph> <k> [ngpu(0)] [chunk_size(1024)]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4\n", self);
@@ -111,10 +118,10 @@ int main(int argc, char **argv) {
   argc = strip_dev_options(argc, argv);
   const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS && GM_APP != GM_TCLIST);
   if (argc < (has_second ? 3 : 2)) usage_and_exit(argv[0]);
-#if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST
+#if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL
   Cli c;
   c.graph = argv[1];
-  if (argc > 2) c.second = argv[2];  // [k] / [out.bin]
+  if (argc > 2) c.second = argv[2];  // [k] / [out.bin] / <k>
 #else
   const Cli c = parse(argc, argv, has_second);
 #endif
@@ -221,6 +228,46 @@ int main(int argc, char **argv) {
   }
   std::printf("total_num_triangles = %llu\n", (unsigned long long)total);
   std::printf("triangles_written = %llu\n", (unsigned long long)written);
+
+#elif GM_APP == GM_CLIQUELOCAL
+  std::printf("local k-clique counts (undirected graph only)\n");
+  std::fflush(stdout);
+  Graph g(c.graph);
+  g.print_meta_data();
+  const gm_csr csr = g.csr();
+  const int k = std::atoi(c.second.c_str());
+  const std::string out = argc > 3 ? argv[3] : "";
+  const size_t nv = (size_t)csr.nv, ne = (size_t)csr.ne;
+  gm_graph *h = nullptr;
+  int rc = gm_graph_upload(&csr, 0, &h);
+  uint64_t total = 0;
+  std::vector<uint64_t> kv(nv), ke(ne);
+  uint64_t *d_kv = nullptr, *d_ke = nullptr;
+  // (the two arrays are the call's results and the caller's buffers)
+  if (rc == GM_OK && hipMalloc(reinterpret_cast<void **>(&d_kv), sizeof(uint64_t) * (nv > 0 ? nv : 1)) != hipSuccess) rc = GM_ERR_HIP;
+  if (rc == GM_OK && hipMalloc(reinterpret_cast<void **>(&d_ke), sizeof(uint64_t) * (ne > 0 ? ne : 1)) != hipSuccess) rc = GM_ERR_HIP;
+  if (rc == GM_OK) rc = gm_clique_local(h, k, nullptr, d_kv, d_ke, &total, nullptr);
+  if (rc == GM_OK && nv > 0 && hipMemcpy(kv.data(), d_kv, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+  if (rc == GM_OK && ne > 0 && hipMemcpy(ke.data(), d_ke, sizeof(uint64_t) * ne, hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+  if (d_kv) (void)hipFree(d_kv);
+  if (d_ke) (void)hipFree(d_ke);
+  gm_graph_free(h);
+  if (rc == GM_OK && !out.empty()) {  // (the hosts this runs on are little-endian: the counts go out as they lie in memory)
+    const struct { std::string path; const std::vector<uint64_t> *v; } files[2] = {{out + ".vertex.u64", &kv}, {out + ".entry.u64", &ke}};
+    for (const auto &file : files) {
+      FILE *f = std::fopen(file.path.c_str(), "wb");
+      const bool ok = f && std::fwrite(file.v->data(), sizeof(uint64_t), file.v->size(), f) == file.v->size();
+      if (f && std::fclose(f) != 0) rc = GM_ERR_IO;
+      if (!ok) rc = GM_ERR_IO;
+    }
+  }
+  if (rc != GM_OK) {
+    std::fprintf(stderr, "%s: %s %s\n", argv[0], gm_strerror(rc), gm_last_error());
+    return 1;
+  }
+  std::printf("\ntotal_num_cliques = %llu\n\n", (unsigned long long)total);
+  std::printf("max_vertex_cliques = %llu\n", (unsigned long long)(kv.empty() ? 0 : *std::max_element(kv.begin(), kv.end())));
+  std::printf("max_edge_cliques = %llu\n", (unsigned long long)(ke.empty() ? 0 : *std::max_element(ke.begin(), ke.end())));
 
 #elif GM_APP == GM_SGL6
   std::printf("Subgraph Listing/Counting (undirected graph only)\n");

@@ -4,7 +4,7 @@
 //   gm_launch.hip  the launch layer (interface: gm_launch.h, for the three solver units only): launch prologue / epilogue, run_pattern,
 //                  gm_kernel_times, gm_tc / gm_clique / gm_motif, and every kernel of the layer
 //   gm_solve_sgl.hip    the SgL family: gm_sgl, the rectangle / house / pentagon map solvers, gm_diamond_support_*, gm_sgl4 / 5 / 6   (host code only)
-//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list                                                      (host code only)
+//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local                                                    (host code only)
 //   gm_tools.hip   set-op batch, R-MAT generator, PMC / issue-rate calibration kernels, self test
 // Host-side counterparts in the reference:
 //   GraphGPU::init / init_edgelist          include/graph_gpu.h:69-194
@@ -366,6 +366,14 @@ struct gm_graph {
   DevOwn<int> d_lfront;      // ne / 2 + 1 canonical entries
   DevOwn<unsigned> d_ltruss;
   DevOwn<unsigned> d_lcnt;   // 64 bytes: [0] frontier size, [1] 0xFFFFFFFF - smallest alive support
+  // local k-clique counts (gm_kcl_local.hip, gm_clique_local).  On the DAG the kernels run on: the k-cliques of every entry, the list of
+  // the rows beyond the LDS matrix, the workgroups' scratch slots.  On the SYMMETRIC handle: the counts in the caller's entry order when
+  // the caller gives no array for them
+  DevOwn<unsigned long long> d_lkcl;   // per DAG entry: the counts, then (ne further values) the undivided sums of the out-edges
+  DevOwn<int> d_kcl_heavy;             // ne / (kKclLocalLdsRow + 1) + 1 rows, then ne / (kKclLocalSplitRow + 1) + 1 split rows
+  DevOwn<unsigned> d_kcl_scratch;
+  size_t kcl_scratch_bytes = 0;
+  DevOwn<unsigned long long> d_lent64; // per entry of the symmetric graph
   // triangle listing (gm_list.hip, gm_tc_list), on the SYMMETRIC handle: the first slot of every batch of 64 entries of the oriented copy
   // (batches + 1 values, the last one T), counted and scanned by the first call and kept for the windows that follow
   DevOwn<unsigned long long> d_list_off;
@@ -593,6 +601,7 @@ void gm_touch_wtri();
 void gm_touch_wrect();
 void gm_touch_local();
 void gm_touch_list();
+void gm_touch_kcl_local();
 void gm_touch_cbuild();
 void gm_touch_cmma();
 void gm_touch_cgather();

@@ -4,7 +4,9 @@
 //   local_map_kernel       per entry (u, v) of the CALLER's symmetric CSR (a lane each; the row from two bisections per WAVE): both ends through the numbering of the renumbered copy, the DAG
 //                          entry by a bisection of the renumbered row (the row of the smaller end under a topological numbering, else
 //                          either row), its support to the caller's entry index; the sum of all of them is 6 T
+//                          (a template on the value: 32-bit supports, or the 64-bit k-clique counts of gm_clique_local)
 //   local_vertex_kernel    T_v = 1/2 sum of the supports of row v in 64 bits: a lane per short row, the whole wave per long one
+//                          (64-bit values: the sum / (k - 1), the k-cliques at a vertex)
 //   local_rev_kernel       once per handle: per entry (u, v) the index of (v, u).  An undirected edge lives at its CANONICAL entry
 //                          min(e, rev[e]) -- the one in the row of its smaller end
 //   local_mark_kernel      a round, steps 1 + 2: last round's frontier becomes removed, the alive edges below the threshold become the
@@ -34,7 +36,8 @@ __device__ __forceinline__ void local_block_add(unsigned long long v, unsigned l
   }
 }
 
-__global__ __launch_bounds__(256) void local_map_kernel(const LocalMapParams p) {
+template <class V>
+__global__ __launch_bounds__(256) void local_map_kernel(const LocalMapParamsT<V> p) {
   const int lane = threadIdx.x & (GM_WAVE - 1);
   const long long stride = (long long)gridDim.x * blockDim.x;
   unsigned long long s = 0;
@@ -44,7 +47,7 @@ __global__ __launch_bounds__(256) void local_map_kernel(const LocalMapParams p) 
     if (e >= p.ne) continue;
     const int v = p.col[e];
     const int a = p.newid ? p.newid[u] : u, b = p.newid ? p.newid[v] : v;
-    unsigned t = 0;
+    V t = 0;
     if (a != b) {
       // (topological: the edge is an entry of the row of its smaller end; else it is in one of the two rows)
       int x = p.topo ? min(a, b) : a, y = p.topo ? max(a, b) : b;
@@ -64,8 +67,10 @@ __global__ __launch_bounds__(256) void local_map_kernel(const LocalMapParams p) 
 }
 
 // a wave takes 64 consecutive rows: every lane sums its own short row, the rows beyond kLocalShortRow entries are summed by all 64 lanes
-__global__ __launch_bounds__(256) void local_vertex_kernel(int nv, const int *__restrict__ rp, const unsigned *__restrict__ sup,
-                                                           unsigned long long *__restrict__ tv) {
+// (HALF: half the sum, the triangles at a vertex; else the sum / div, the k-cliques at a vertex with div = k - 1)
+template <class V, bool HALF>
+__global__ __launch_bounds__(256) void local_vertex_kernel(int nv, const int *__restrict__ rp, const V *__restrict__ sup,
+                                                           unsigned long long *__restrict__ tv, const unsigned div) {
   const int lane = threadIdx.x & (GM_WAVE - 1);
   const long long wave0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
   for (long long base = wave0 * GM_WAVE; base < nv; base += nwaves * GM_WAVE) {
@@ -84,7 +89,7 @@ __global__ __launch_bounds__(256) void local_vertex_kernel(int nv, const int *__
       part = wave_sum_u64(part);
       if (lane == l) s = part;
     }
-    if (v < nv) tv[v] = s >> 1;
+    if (v < nv) tv[v] = HALF ? s >> 1 : s / (unsigned long long)div;
   }
 }
 
@@ -207,12 +212,24 @@ static inline dim3 local_grid(long long n, long long per_block, int cu_count) {
 hipError_t launch_local_map(const LocalMapParams &p, int cu_count, hipStream_t stream) {
   if (p.ne <= 0) return hipSuccess;
   if (!p.out || !p.dsup || !p.sum) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(local_map_kernel, local_grid(p.ne, 256, cu_count), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(local_map_kernel<unsigned>, local_grid(p.ne, 256, cu_count), dim3(256), 0, stream, p);
+  return hipGetLastError();
+}
+hipError_t launch_local_map(const LocalMapParams64 &p, int cu_count, hipStream_t stream) {
+  if (p.ne <= 0) return hipSuccess;
+  if (!p.out || !p.dsup || !p.sum) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(local_map_kernel<unsigned long long>, local_grid(p.ne, 256, cu_count), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 hipError_t launch_local_vertices(int nv, const int *rp, const unsigned *sup, unsigned long long *tv, int cu_count, hipStream_t stream) {
   if (nv <= 0) return hipSuccess;
-  hipLaunchKernelGGL(local_vertex_kernel, local_grid(nv, 256, cu_count), dim3(256), 0, stream, nv, rp, sup, tv);
+  hipLaunchKernelGGL((local_vertex_kernel<unsigned, true>), local_grid(nv, 256, cu_count), dim3(256), 0, stream, nv, rp, sup, tv, 2u);
+  return hipGetLastError();
+}
+hipError_t launch_local_vertices(int nv, const int *rp, const unsigned long long *cnt, unsigned div, unsigned long long *kv, int cu_count, hipStream_t stream) {
+  if (nv <= 0) return hipSuccess;
+  if (div == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((local_vertex_kernel<unsigned long long, false>), local_grid(nv, 256, cu_count), dim3(256), 0, stream, nv, rp, cnt, kv, div);
   return hipGetLastError();
 }
 hipError_t launch_local_rev(int nv, long long ne, const int *rp, const int *col, int *rev, int cu_count, hipStream_t stream) {

@@ -664,17 +664,20 @@ hipError_t launch_wrect_mask(int nv, const int *rp, const int *col, int range, i
 hipError_t launch_sgl6_sums(const Sgl6EntryParams &p, int cu_count, hipStream_t stream);
 // local counts and the k-truss (gm_local.hip): the supports of the oriented copy back at the caller's entries, the triangles per vertex, and
 // the peeling rounds on the symmetric graph
-struct LocalMapParams {
+template <class V>  // the value per entry: unsigned = a support (gm_tc_local, the k-truss), unsigned long long = a k-clique count (gm_clique_local)
+struct LocalMapParamsT {
   int nv;
   long long ne;
   const int *rp, *col;        // the caller's symmetric CSR
   const int *newid;           // caller's id -> id of the DAG the supports were counted on (nullptr: the same ids)
   const int *drp, *dcol;      // that DAG
-  const unsigned *dsup;       // its supports, one per entry
+  const V *dsup;              // its supports, one per entry
   int topo;                   // every DAG edge goes to a larger id: the edge sits in the row of its smaller end
-  unsigned *out;              // per caller's entry: the support of its edge
+  V *out;                     // per caller's entry: the support of its edge
   unsigned long long *sum;    // [0] += the sum of out[] (6 T)
 };
+using LocalMapParams = LocalMapParamsT<unsigned>;
+using LocalMapParams64 = LocalMapParamsT<unsigned long long>;
 constexpr int kLocalShortRow = 32;  // local_vertex_kernel: a row of more entries is summed by the whole wave
 enum LocalMark : unsigned char { LM_ALIVE = 0, LM_FRONTIER = 1, LM_REMOVED = 2 };
 struct LocalPeelParams {
@@ -691,6 +694,33 @@ struct LocalPeelParams {
 };
 hipError_t launch_local_map(const LocalMapParams &p, int cu_count, hipStream_t stream);
 hipError_t launch_local_vertices(int nv, const int *rp, const unsigned *sup, unsigned long long *tv, int cu_count, hipStream_t stream);
+// ... the 64-bit forms (gm_clique_local): the k-clique count of every entry, and per vertex the sum of its row / div (div = k - 1)
+hipError_t launch_local_map(const LocalMapParams64 &p, int cu_count, hipStream_t stream);
+hipError_t launch_local_vertices(int nv, const int *rp, const unsigned long long *cnt, unsigned div, unsigned long long *kv, int cu_count, hipStream_t stream);
+// local k-clique counts (gm_kcl_local.hip): the k-cliques on every entry of the DAG.  Rows of up to kKclLocalLdsRow entries keep the
+// adjacency matrix of the row in LDS -- a candidate set of a descent takes 2 registers for rows of up to kKclLocalRegs2Row entries, 8 up
+// to kKclLocalRegs8Row, 12 up to kKclLocalRegs12Row, 16 beyond; longer rows are listed by that kernel and taken by the second one out of a global scratch slot per
+// workgroup.  Exported through gm_constant ("kcl_local_regs2_row", "kcl_local_regs8_row", "kcl_local_regs12_row", "kcl_local_lds_row"): the tests place rows on
+// both sides of each of them.
+constexpr int kKclLocalRegs2Row = 64, kKclLocalRegs8Row = 256, kKclLocalRegs12Row = 384, kKclLocalLdsRow = 512;
+// k >= 5: a row of more entries than this is shared by several workgroups ("kcl_local_split_row")
+constexpr int kKclLocalSplitRow = 128;
+enum KclStage : int { KCL_STAGE_ROOTS = 0, KCL_STAGE_SPLIT = 1, KCL_STAGE_WIDE = 2, KCL_STAGE_FOLD = 3 };
+struct KclLocalParams {
+  int nv, k, max_deg;               // max_deg: the longest row (sizes the scratch slot)
+  long long ne;
+  const int *rp, *col;              // the DAG
+  unsigned long long *cnt;          // per DAG entry: += its k-cliques (zeroed by the caller)
+  unsigned long long *spk;          // per DAG entry: += (k - 2) x the cliques it holds as an out-edge of their root (zeroed by the caller)
+  int *heavy, *mid;                 // the rows beyond kKclLocalLdsRow entries / the split rows, in order of arrival (heavy_cap / mid_cap ints)
+  unsigned heavy_cap, mid_cap;
+  unsigned *n_heavy, *n_mid, *queue, *queue_wide, *queue_mid;  // zeroed by the caller: the lengths of the lists, the dequeue words of the kernels
+  unsigned *scratch;                // wide: gridDim.x slots of scratch_words (kcl_local_scratch_words(max_deg)) words
+  unsigned long long scratch_words;
+  unsigned long long *err;          // += 1 for what cannot happen (an adjacent pair without an entry, a row beyond max_deg)
+};
+unsigned long long kcl_local_scratch_words(int max_deg);
+hipError_t launch_kcl_local(const KclLocalParams &p, int stage, int grid_blocks, hipStream_t stream);  // stage: KclStage
 hipError_t launch_local_rev(int nv, long long ne, const int *rp, const int *col, int *rev, int cu_count, hipStream_t stream);
 hipError_t launch_local_peel_init(long long ne, const int *rev, unsigned char *mark, int cu_count, hipStream_t stream);
 hipError_t launch_local_mark(const LocalPeelParams &p, int cu_count, hipStream_t stream);

@@ -1,5 +1,6 @@
-// gm_solve_local.hip -- local counts, the k-truss and the triangle listing over the launch layer (gm_launch.h): gm_tc_local, gm_ktruss,
-// gm_truss_decompose, gm_tc_list.  Host code only: the kernels are gm_local.hip's and gm_list.hip's, so this unit has no code object and no warm-up.
+// gm_solve_local.hip -- local counts, the k-truss, the triangle listing and the local k-clique counts over the launch layer (gm_launch.h):
+// gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local.  Host code only: the kernels are gm_local.hip's, gm_list.hip's and
+// gm_kcl_local.hip's, so this unit has no code object and no warm-up.
 #include "gm_launch.h"
 
 // ---- local counts and the k-truss (gm_local.hip; DESIGN.md "Local counts and k-truss") ----------------------------------------------------
@@ -83,6 +84,94 @@ extern "C" int gm_tc_local(const gm_graph *sym, const gm_launch *la, uint64_t *d
   if (int rc = sub.run([&](gm_stats *s) { return end_launch(ctx, FIN_COPY, 0, &sum, 1, s); })) return rc;
   if (total) *total = sum / 6ull;  // sum_e t(e) over both directions = 2 sum_v T_v = 6 T
   if (st) st->kernel_ms = sub.ms;
+  return GM_OK;
+}
+
+// ---- local k-clique counts (gm_kcl_local.hip; DESIGN.md "Local k-clique counts") -----------------------------------------------------------
+// The k-cliques of every entry of the DAG (the oriented copy, or its topological copy: topo_view) into run_on->d_lkcl, then the way back
+// the supports take: the 64-bit mapping kernel into the caller's entry order, the row sums / (k - 1) per vertex.
+constexpr size_t kKclScratchBudget = (size_t)1 << 30;  // bytes of scratch slots the wide kernel's grid is cut to (at least one slot)
+extern "C" int gm_clique_local(const gm_graph *sym, int k, const gm_launch *la, uint64_t *d_vertex_cnt, uint64_t *d_entry_cnt, uint64_t *total,
+                               gm_stats *st) {
+  if (total) *total = 0;
+  if (!sym || k < 3 || k > GM_MAX_CLIQUE_K) return GM_ERR_INVALID;
+  if (int rc = local_refusals(sym, la)) return rc;
+  if (k > 8) {
+    g_last_error = "gm_clique_local: k = 9 .. " + std::to_string(GM_MAX_CLIQUE_K) + " is not supported yet (3 <= k <= 8)";
+    return GM_ERR_UNSUPPORTED;
+  }
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  uint64_t out[4] = {0, 0, 0, 0};
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, out, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+  if (sym->ne == 0) {
+    if (d_vertex_cnt && sym->nv > 0) HIP_TRY(hipMemsetAsync(d_vertex_cnt, 0, sizeof(uint64_t) * (size_t)sym->nv, ctx.stream));
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    return GM_OK;
+  }
+  gm_graph *run_on = nullptr;
+  if (int rc = diamond_run_on(g, &l2, &run_on)) return rc;  // (the oriented copy, or its topological copy: tune[6] & GM_T6_AS_NUMBERED)
+  const gm_graph *dag = g->dag_cache;
+  if (run_on != dag && !run_on->d_newid) return GM_ERR_INVALID;  // (a renumbered copy always remembers its numbering)
+  const bool wide = run_on->max_deg > kKclLocalLdsRow;
+  const size_t slot_bytes = sizeof(unsigned) * (size_t)kcl_local_scratch_words(run_on->max_deg);
+  const int grid = grid_for(run_on->nv, g->cu_count, 8);
+  const int grid_wide = wide ? clamp_grid((long long)(kKclScratchBudget / slot_bytes), (long long)g->cu_count * 2) : 0;
+  const size_t heavy_cap = (size_t)(run_on->ne / (kKclLocalLdsRow + 1)) + 1, mid_cap = (size_t)(run_on->ne / (kKclLocalSplitRow + 1)) + 1;
+  const size_t dne = (size_t)std::max<long long>(run_on->ne, 1);
+  {
+    std::lock_guard<std::mutex> lk(run_on->mu);
+    HIP_TRY(hipSetDevice(run_on->device));
+    if (!run_on->d_lkcl) HIP_TRY(run_on->d_lkcl.alloc(sizeof(unsigned long long) * 2 * dne));
+    if (!run_on->d_kcl_heavy) HIP_TRY(run_on->d_kcl_heavy.alloc(sizeof(int) * (heavy_cap + mid_cap)));
+    if (wide)
+      if (int rc = grow_dev(run_on->d_kcl_scratch, &run_on->kcl_scratch_bytes, slot_bytes * (size_t)grid_wide)) return rc;
+  }
+  if (!d_entry_cnt) {
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (!g->d_lent64) HIP_TRY(g->d_lent64.alloc(sizeof(unsigned long long) * (size_t)g->ne));
+  }
+  HIP_TRY(hipMemsetAsync(g->d_counters, 0, kCounterBlockBytes, ctx.stream));  // (a first call oriented the graph since begin_launch)
+  if (int rc = start_timer(ctx)) return rc;
+  HIP_TRY(hipMemsetAsync(run_on->d_lkcl, 0, sizeof(unsigned long long) * 2 * dne, ctx.stream));
+  KclLocalParams kp;
+  memset(&kp, 0, sizeof kp);
+  kp.nv = run_on->nv; kp.ne = run_on->ne; kp.k = k; kp.max_deg = std::max(run_on->max_deg, 1);
+  kp.rp = run_on->d_rp; kp.col = run_on->d_col; kp.cnt = run_on->d_lkcl; kp.spk = run_on->d_lkcl + dne;
+  kp.heavy = run_on->d_kcl_heavy; kp.heavy_cap = (unsigned)heavy_cap;
+  kp.mid = run_on->d_kcl_heavy + heavy_cap; kp.mid_cap = (unsigned)mid_cap;
+  kp.queue = queue_word(g, QW_MAIN); kp.queue_wide = queue_word(g, QW_CLASS1); kp.n_heavy = queue_word(g, QW_CLASS2);
+  kp.queue_mid = queue_word(g, QW_CLASS3); kp.n_mid = queue_word(g, QW_CORNER);
+  kp.scratch = run_on->d_kcl_scratch; kp.scratch_words = kcl_local_scratch_words(run_on->max_deg);
+  kp.err = g->d_counters + 1;
+  HIP_TRY(launch_kcl_local(kp, KCL_STAGE_ROOTS, grid, ctx.stream));
+  if (k >= 5 && run_on->max_deg > kKclLocalSplitRow) HIP_TRY(launch_kcl_local(kp, KCL_STAGE_SPLIT, grid, ctx.stream));
+  if (wide) HIP_TRY(launch_kcl_local(kp, KCL_STAGE_WIDE, grid_wide, ctx.stream));
+  HIP_TRY(launch_kcl_local(kp, KCL_STAGE_FOLD, grid_for((run_on->ne + 255) / 256, g->cu_count, 8), ctx.stream));
+  LocalMapParams64 mp;
+  memset(&mp, 0, sizeof mp);
+  mp.nv = g->nv; mp.ne = g->ne; mp.rp = g->d_rp; mp.col = g->d_col;
+  mp.newid = run_on != dag ? run_on->d_newid : nullptr;
+  mp.drp = run_on->d_rp; mp.dcol = run_on->d_col; mp.dsup = run_on->d_lkcl;
+  mp.topo = run_on->topo_state == 1 ? 1 : 0;
+  unsigned long long *ent = d_entry_cnt ? (unsigned long long *)d_entry_cnt : g->d_lent64.get();
+  mp.out = ent; mp.sum = g->d_counters;
+  HIP_TRY(launch_local_map(mp, g->cu_count, ctx.stream));
+  if (d_vertex_cnt) HIP_TRY(launch_local_vertices(g->nv, g->d_rp, ent, (unsigned)(k - 1), (unsigned long long *)d_vertex_cnt, g->cu_count, ctx.stream));
+  gm_stats s;
+  memset(&s, 0, sizeof s);
+  if (int rc = end_launch(ctx, FIN_RAW4, 0, out, 4, &s)) return rc;
+  if (out[1] != 0) {
+    g_last_error = "gm_clique_local: the kernel met " + std::to_string(out[1]) + " adjacent pairs without an entry (internal error)";
+    return GM_ERR_INVALID;
+  }
+  if (total) *total = out[0] / ((uint64_t)k * (uint64_t)(k - 1));  // sum_e K_e over both directions = k (k - 1) K
+  if (st) {
+    st->kernel_ms = s.kernel_ms;
+    st->grid = (uint32_t)grid;
+  }
   return GM_OK;
 }
 

@@ -147,6 +147,8 @@ extern "C" int gm_constant(const char *name, int64_t *value) {
       {"stage_cap", kStageCap},              {"default_chunk", kDefaultChunk},        {"mma_words_small", kMmaWordsS},
       {"mma_words_big", kMmaWordsL},         {"core_h_default", kCoreHDefault},  {"wide_min_words", kWideMinWordsDefault},
               {"wide_max_deg", kWideMaxDeg},           {"bit_words", kBitWords},
+      {"kcl_local_lds_row", kKclLocalLdsRow}, {"kcl_local_regs2_row", kKclLocalRegs2Row}, {"kcl_local_regs8_row", kKclLocalRegs8Row}, {"kcl_local_regs12_row", kKclLocalRegs12Row},
+      {"kcl_local_split_row", kKclLocalSplitRow},
   };
   for (const auto &e : tab)
     if (strcmp(e.name, name) == 0) {

@@ -276,6 +276,21 @@ def truss_decompose(g: DeviceGraph, *, chunk=0, return_stats=False, **kw):
     return (*res, _stats(st)) if return_stats else res
 
 
+# ---- local k-clique counts (include/graphminer_amd.h: gm_clique_local) --------------------------------------------------------------------
+def clique_local(g: DeviceGraph, k: int, *, vertex=True, entries=True, chunk=0, return_stats=False, **kw):
+    """(total, K_v as np.uint64[nv] or None, K_uv per entry as np.uint64[ne] or None) of a SYMMETRIC graph, in the caller's numbering and
+    entry order: K_v the k-cliques that contain v, K_uv the k-cliques that contain the edge of entry (u, v).  3 <= k <= 8.  One GPU."""
+    import torch
+
+    la, st, total = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0)
+    kv = _dev_array(g, g.nv, torch.int64) if vertex else None
+    ke = _dev_array(g, g.ne, torch.int64) if entries else None
+    _lib.check(_lib.load().gm_clique_local(g.handle, int(k), C.byref(la), kv.data_ptr() if vertex else None, ke.data_ptr() if entries else None,
+                                           C.byref(total), C.byref(st)), "gm_clique_local")
+    res = (int(total.value), _to_numpy(kv, g.nv, "uint64") if vertex else None, _to_numpy(ke, g.ne, "uint64") if entries else None)
+    return (*res, _stats(st)) if return_stats else res
+
+
 # ---- triangle listing (include/graphminer_amd.h: gm_tc_list) ------------------------------------------------------------------------------
 def tc_list(g: DeviceGraph, *, first=0, cap=None, chunk=0, return_stats=False, **kw):
     """(total, triangles as np.int32[n_written, 3]) of a SYMMETRIC graph: rows a < b < c in the caller's numbering, every triangle once, in

@@ -381,6 +381,33 @@ int gm_tc_list(const gm_graph *sym, const gm_launch *launch, uint64_t first, uin
  * rows are long (cached on the handle; tune[6] & GM_T6_AS_NUMBERED: as numbered). */
 int gm_clique(const gm_graph *dag, int k, const gm_launch *launch, uint64_t *total, gm_stats *stats);
 
+/* ---- local k-clique counts (csrc/gm_kcl_local.hip; DESIGN.md "Local k-clique counts") ------------------------------------------------
+ * What a caller asks of a clique counter after the total: the k-cliques at every vertex and on every edge, in the CALLER's numbering and
+ * entry order (the input of a k-clique densest subgraph, a nucleus decomposition, higher-order clustering coefficients).  SYMMETRIC
+ * graph, as for the local triangle counts; the call takes the oriented copy from the handle itself.
+ *   d_vertex_cnt: DEVICE uint64[nv] or NULL -- K_v, the k-cliques that contain v (the sum of row v of the entry counts / (k - 1)).
+ *   d_entry_cnt:  DEVICE uint64[ne] or NULL -- for entry i = (u, v) of row u: K_uv, the k-cliques that contain the edge; the two
+ *                 directions of an edge are equal.  Both arrays are 64-bit: an edge of a graph of a few hundred vertices can lie in
+ *                 more than 2^32 cliques.
+ *   total (may be NULL): the k-clique count, sum_v K_v / k.
+ * All arithmetic is integer: the results do not depend on the launch or on the order in which the workgroups arrive.
+ * 3 <= k <= 8.  k < 3 or k > GM_MAX_CLIQUE_K -> GM_ERR_INVALID as in the clique solver above; 9 <= k <= GM_MAX_CLIQUE_K ->
+ * GM_ERR_UNSUPPORTED for now.  k = 3 gives the supports and triangles of the local triangle counts, widened to 64 bits.
+ * Every root u of the DAG builds the symmetric adjacency bit-matrix of its out-list and attributes the cliques it roots with ONE 64-bit
+ * atomic per DAG triangle and one per out-edge, nothing per clique.  Out-lists of up to 512 entries keep the matrix in LDS (k >= 5:
+ * those beyond 128 entries are shared by several workgroups); longer ones, of any length, take a slot of a global scratch per workgroup
+ * (slow, exact; the slots must fit the device memory, else GM_ERR_HIP -- a count is refused, never wrong).
+ * By default the call runs on the copy the one-GPU diamond's triangle pass runs on: the oriented copy renumbered topologically when its
+ * rows are long (cached on the handle), else the oriented copy as numbered.  launch->tune[6] & GM_T6_AS_NUMBERED: always the oriented
+ * copy as numbered, no renumbered copy.  The counts are the same on both.
+ * The contract of the local counts above: one GPU, synchronous; a null handle -> GM_ERR_INVALID, >= 2^31 entries -> GM_ERR_TOO_LARGE,
+ * world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED, unsorted rows -> GM_ERR_INVALID, ne == 0 -> GM_OK with zeros (d_vertex_cnt is
+ * zeroed when given); launch->stream is honoured; stats->kernel_ms covers every kernel of the call, stats->tasks = the directed
+ * entries; before or after any other solver on the handle, whose arrays it leaves alone; ONE such call at a time per handle; every
+ * array it keeps on the handle is freed with the handle. */
+int gm_clique_local(const gm_graph *sym, int k, const gm_launch *launch, uint64_t *d_vertex_cnt, uint64_t *d_entry_cnt, uint64_t *total,
+                    gm_stats *stats);
+
 /* MotifSolver on the SYMMETRIC graph. k = 3: counts[0] = wedges, counts[1] = triangles
  * (the CPU order, src/motif/cpu_kernels/automine_base.h:13,18; NOT the swapped order of
  * src/motif/gpu_kernels/motif3_edge_warp.cuh:19-22). ncounts must be
