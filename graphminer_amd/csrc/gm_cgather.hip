@@ -4,7 +4,7 @@
 // numbering).  The streamed build (gm_cbuild.hip) finds those bits as a set intersection N+(u) ^ N+(s_i): a hashed lookup per streamed
 // key, 44 VALU per 64 keys, 23 G keys on the com-Orkut stand-in -- 34.5 of the 42.5 ms left after the pair counts moved to the matrix
 // cores.  But M_u is just the adjacency matrix of the subgraph induced by N+(u), and for a WIDE vertex (d+ > 256) of a DAG numbered by
-// degree nearly all of N+(u) lies among the LAST few 10^4 ids -- the hubs.  Their adjacency is kept DENSE (gm_graph::d_core: core_h x
+// degree nearly all of N+(u) lies among the LAST few 10^4 ids -- the hubs.  Their adjacency is kept DENSE (gm_graph::core, HubCore: h x
 // core_h bits, one row per core vertex, built once per graph), and a row of M_u is a bit GATHER:
 //     M_u[i][j] = core[s_i - base][s_j - base],   j > i, s_i >= base  (then every s_j > s_i is in the core too)
 // -- lane j of a 64-column tile loads the word that holds its bit (the positions are ascending and dense at the top of the id range:

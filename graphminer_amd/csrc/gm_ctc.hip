@@ -5,7 +5,7 @@
 // triangle kernel (gm_tch.hip) moves -- a task costs min(d+(v), tail_u(v)) keys, and those are the longest lists of the graph
 // (R-MAT-22: H = 8 K / 16 K / 32 K vertices = 3.7 / 6.0 / 10.8 M of 40.6 M edges = 29 / 42 / 66 % of the 2.98 G streamed keys).
 // With M = the corner as a bit matrix (strictly upper triangular under the topological numbering; the 4-clique's core bitmap, gm_host.h
-// d_core) the triangles whose smallest member is a core vertex are
+// HubCore) the triangles whose smallest member is a core vertex are
 //     sum_{i<j, M_ij} popc(M_i & M_j)  =  sum_{i,j} M_ij (M M^T)_ij                                   (omp_base.cc:15-21 on bit rows)
 // -- the masked binary matrix product of the 4-clique's second level (gm_cmma.hip), once, on one H x H matrix: FP4 MFMA with a set bit
 // as the E2M1 value 1.0, f32 accumulators (exact: a sum is at most H <= 2^15), a wave per 64 x 64 block of (i, j) with I <= J over the

@@ -48,5 +48,5 @@ class DevOwn {
     p_ = b.release();
   }
   T *get() const { return p_; }
-  operator T *() const { return p_; }  // kernel arguments, `g->d_rp + v`, `if (!g->d_x)`, `p.idx0 = g->d_idx0` read as with a raw pointer
+  operator T *() const { return p_; }  // kernel arguments, `g->d_rp + v`, `if (!g->d_x)`, `p.rp = g->d_rp` read as with a raw pointer
 };

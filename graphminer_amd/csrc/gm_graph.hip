@@ -302,13 +302,14 @@ int finish_handle(gm_graph *g) {
 
 // host copy of the 32-bit offsets, fetched from the device on first use
 int host_rp(gm_graph *g, const std::vector<int> **out) {
-  if (g->h_rp.size() != (size_t)g->nv + 1) {
-    g->h_rp.resize((size_t)g->nv + 1);
+  const int rc = g->facts.h_rp.ensure(g->mu, [&](std::vector<int> &rp) {
+    rp.resize((size_t)g->nv + 1);
     HIP_TRY(hipSetDevice(g->device));
-    HIP_TRY(hipMemcpy(g->h_rp.data(), g->d_rp, sizeof(int) * ((size_t)g->nv + 1), hipMemcpyDeviceToHost));
-  }
-  if (out) *out = &g->h_rp;
-  return GM_OK;
+    HIP_TRY(hipMemcpy(rp.data(), g->d_rp, sizeof(int) * ((size_t)g->nv + 1), hipMemcpyDeviceToHost));
+    return kOnceBuilt;
+  });
+  if (rc == GM_OK && out) *out = &*g->facts.h_rp;
+  return rc;
 }
 // int64 offsets of the ABI -> the internal int32 copy, validated on the device: err bit 0 = not an offset array (first != 0,
 // last != ne, or decreasing), bit 1 = a row of 2^24 entries or more; info[1] = longest row
@@ -469,10 +470,7 @@ extern "C" int gm_graph_sort_neighbors(gm_graph *g) {
   if (g->d_rp64) { g_last_error = "gm_graph_sort_neighbors: not for graphs of 2^31 entries or more (the segmented sort counts items in 32 bits)"; return GM_ERR_TOO_LARGE; }
   // before any solver ran: every cached structure describes the rows as they are now (tables, descriptors, task lists, derived
   // handles, the per-pattern tables of the SgL / 4-motif paths, hub bitmaps, the sum of C(d,2))
-  if (!g->tables.empty() || g->d_edesc || g->d_trp || g->d_tdesc || g->d_kst_rp || g->dag_cache || g->relabel_cache[0] || g->relabel_cache[1] || g->d_idx0 ||
-      g->d_wblock_prefix || g->d_rect_tasks || g->d_house_t || g->d_house_tlt || g->d_house_tasks || g->d_house_prefix || !g->bitmap_sets.empty() ||
-      g->wide_valid || g->sum_c2_valid)
-    return GM_ERR_INVALID;
+  if (g->rows_in_use()) return GM_ERR_INVALID;
   HIP_TRY(hipDeviceSynchronize());  // a caller stream may still be reading a borrowed col_idx array: the sort runs on the null stream
   HIP_TRY(hipSetDevice(g->device));
   PoolScope pool(g);
@@ -487,8 +485,8 @@ extern "C" int gm_graph_sort_neighbors(gm_graph *g) {
   HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.buf.p, bytes, g->d_col, sorted.p, (int)g->ne, g->nv, g->d_rp.get(), g->d_rp + 1, 0, bits));
   HIP_TRY(hipMemcpy(g->d_col, sorted.p, sizeof(int) * (size_t)g->ne, hipMemcpyDeviceToDevice));
   HIP_TRY(hipDeviceSynchronize());
-  g->sorted_state = 0;  // (checked again by the first solver: duplicates are still not "strictly ascending")
-  g->topo_state = 0;
+  g->facts.rows_sorted.reset();  // (checked again by the first solver: duplicates are still not "strictly ascending")
+  g->facts.topological.reset();
   return GM_OK;
 }
 
@@ -830,7 +828,7 @@ extern "C" int gm_graph_renumbered(gm_graph *g, int mode, gm_graph **view) {
     return GM_ERR_INVALID;
   }
   const int rc2 = get_relabeled(g, mode, view);
-  if (rc2 == GM_OK && *view && (*view)->sorted_state == 2) {
+  if (rc2 == GM_OK && *view && (*view)->facts.rows_sorted.known() && !*(*view)->facts.rows_sorted) {
     *view = nullptr;
     g_last_error = "gm_graph_renumbered: the renumbered copy has duplicate neighbours";
     return GM_ERR_INVALID;
@@ -1148,33 +1146,34 @@ __global__ __launch_bounds__(256) void topo_check_kernel(int nv, const int *__re
 }
 
 int graph_rows_sorted(gm_graph *g, bool *out) {
-  if (g->sorted_state == 0) {
-    if (g->d_rp == nullptr || g->ne < 2) {  // (a handle of >= 2^31 entries is validated when it is oriented)
-      g->sorted_state = 1;
-    } else {
-      HIP_TRY(hipSetDevice(g->device));
-      DevBuf<unsigned long long> counts;
-      HIP_TRY(counts.alloc(2));
-      HIP_TRY(hipMemsetAsync(counts.p, 0, sizeof(unsigned long long) * 2, 0));
-      const long long blocks = std::min<long long>((g->ne + 255) / 256, (long long)g->cu_count * 8);
-      hipLaunchKernelGGL(sorted_check_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, g->ne, g->d_col, counts.p);
-      hipLaunchKernelGGL(sorted_rowstart_kernel, dim3((unsigned)std::min<long long>(((long long)g->nv + 255) / 256, (long long)g->cu_count * 8)), dim3(256), 0, 0, g->nv, g->d_rp, g->d_col, counts.p);
-      unsigned long long c[2] = {0, 0};
-      HIP_TRY(hipMemcpy(c, counts.p, sizeof(c), hipMemcpyDeviceToHost));
-      g->sorted_state = c[0] != c[1] ? 2 : 1;
-    }
-  }
-  *out = g->sorted_state == 1;
-  return GM_OK;
+  const int rc = g->facts.rows_sorted.ensure(g->mu, [&](bool &sorted) {
+    sorted = true;
+    if (g->d_rp == nullptr || g->ne < 2) return kOnceBuilt;  // (a handle of >= 2^31 entries is validated when it is oriented)
+    HIP_TRY(hipSetDevice(g->device));
+    DevBuf<unsigned long long> counts;
+    HIP_TRY(counts.alloc(2));
+    HIP_TRY(hipMemsetAsync(counts.p, 0, sizeof(unsigned long long) * 2, 0));
+    const long long blocks = std::min<long long>((g->ne + 255) / 256, (long long)g->cu_count * 8);
+    hipLaunchKernelGGL(sorted_check_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, g->ne, g->d_col, counts.p);
+    hipLaunchKernelGGL(sorted_rowstart_kernel, dim3((unsigned)std::min<long long>(((long long)g->nv + 255) / 256, (long long)g->cu_count * 8)), dim3(256), 0, 0, g->nv, g->d_rp, g->d_col, counts.p);
+    unsigned long long c[2] = {0, 0};
+    HIP_TRY(hipMemcpy(c, counts.p, sizeof(c), hipMemcpyDeviceToHost));
+    sorted = c[0] == c[1];
+    return kOnceBuilt;
+  });
+  *out = *g->facts.rows_sorted;
+  return rc;
 }
 
 // "topological" as the task lists use it (an in-edge task streams only the entries BEHIND its own: gm_tables.hip): every edge u -> v has
 // u < v AND the rows are ascending (the first entry of a row alone was tested, which says nothing about an unsorted row)
 int graph_is_topological(gm_graph *g, bool *out) {
-  if (g->topo_state == 0) {
-    bool sorted = false;
-    const int rc = graph_rows_sorted(g, &sorted);
+  bool sorted = false;
+  if (!g->facts.topological.known()) {
+    const int rc = graph_rows_sorted(g, &sorted);  // (takes the lock itself)
     if (rc) return rc;
+  }
+  const int rc = g->facts.topological.ensure(g->mu, [&](bool &topo) {
     HIP_TRY(hipSetDevice(g->device));
     DevBuf<int> flag;
     HIP_TRY(flag.alloc(1));
@@ -1182,10 +1181,11 @@ int graph_is_topological(gm_graph *g, bool *out) {
     if (g->nv > 0) hipLaunchKernelGGL(topo_check_kernel, dim3((unsigned)((g->nv + 255) / 256)), dim3(256), 0, 0, g->nv, g->d_rp, g->d_col, flag.p);
     int not_topo = 0;
     HIP_TRY(hipMemcpy(&not_topo, flag.p, sizeof(int), hipMemcpyDeviceToHost));
-    g->topo_state = (not_topo || !sorted) ? 2 : 1;
-  }
-  *out = g->topo_state == 1;
-  return GM_OK;
+    topo = !not_topo && sorted;
+    return kOnceBuilt;
+  });
+  *out = *g->facts.topological;
+  return rc;
 }
 
 // mode 0: ids ascending in degree, 1: descending, 2: ascending in (in-degree + out-degree) -- the topological numbering of an oriented
@@ -1299,7 +1299,7 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
   {
     int dup = 0;
     if ((e = hipMemcpy(&dup, dupflag.p, sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
-    r->sorted_state = dup ? 2 : 1;
+    (void)r->facts.rows_sorted.ensure(r->mu, [&](bool &sorted) { sorted = !dup; return kOnceBuilt; });  // (the copy's rows were just written: known)
   }
   int rc = finish_handle(r);
   if (rc) { gm_graph_free(r); return rc; }

@@ -13,11 +13,16 @@
 //   Graph::orientation                       src/common/graph.cc:233-279
 // None of that code is reused: tasks are described by a compact chunk table (16 B per ~256 edges)
 // instead of per-GPU COO copies, and the multi-GPU split is index arithmetic on chunk ids.
+// State of a handle (struct gm_graph, below): the graph itself; the structures built on first use, one struct each behind a Once<T>
+// (gm_once.h: built under g->mu in a local, published whole, read through the Once -- one protocol for "is it there yet"); the keyed
+// lists handed out under g->mu (tables, bitmap sets, clique plans); and the work buffers of the call families, which need no protocol
+// because one solver call at a time runs per handle (include/graphminer_amd.h).
 #pragma once
 #include "../../include/graphminer_amd.h"
 #include "gm_centre_plan.h"
 #include "gm_devown.h"
 #include "gm_mine.h"
+#include "gm_once.h"
 #include "gm_setops.h"
 
 #include <algorithm>
@@ -194,11 +199,9 @@ struct ChunkTable {
   // order (single rank); [1] all chunks by estimated cost, descending (rank r of n owns every n-th entry)
   DevOwn<int> d_order[2];
   std::vector<int> order[2];
-  // the views every reader uses; the arrays are a BitmapSet's of the graph (shared by its tables) or, built by the table itself, its own
+  // borrowed: the arrays of a BitmapSet of the graph (shared by its tables)
   unsigned *d_bitmaps = nullptr;         // n_bitmaps x bitmap_words
   int *d_row_slot = nullptr;             // per vertex: bitmap slot or -1
-  DevOwn<unsigned> d_bitmaps_mem;        // (empty when borrowed)
-  DevOwn<int> d_row_slot_mem;
   size_t n_bitmaps = 0;
   unsigned long long bitmap_words = 0;
   unsigned long long max_bit_words = 0;  // largest nel*stride over chunks that exceed bit_words
@@ -292,7 +295,181 @@ struct CentrePlan {             // once per graph, published whole
   DevOwn<int4> d_acc_tasks;     // the "cut" list: first n_cut tasks walk only ends below cut
   unsigned long long n_lds_tasks = 0, n_acc_tasks = 0, n_cut = 0;
   int cut = 0, bnd_stride = 0;
-  bool ready = false;
+};
+
+// ------------------------------------------------------------------------------------------------
+// The structures a handle builds on first use and keeps: one struct each, held by gm_graph as a Once<...> (gm_once.h).  The builder fills a
+// local value under g->mu and the whole value is published at once; readers go through the Once and never see a half-built group.  Every
+// comment says who builds the group and who reads it.
+// ------------------------------------------------------------------------------------------------
+// Task lists of the shorter-list-streams triangle count.  Built by ensure_tasklists (gm_tables.hip); read by plan_pattern / fill_mine_params
+// (gm_launch.hip), ensure_sup_corner / ensure_sup_masks, gm_sup_corner_info.
+struct TaskLists {
+  DevOwn<int> trp;      // row offsets (nv + 1)
+  DevOwn<int2> tdesc;   // per task {rp[partner], d(partner)}
+  DevOwn<int> tedge;    // the task's own DAG entry (the edge supports), always built with the lists
+  // TASK-MAJOR COPIES of the short lists (a handle that cannot have the key stream; build_inline_copies): colk = col followed by the keys
+  // of every list of <= GM_TC_INLINE_MAX entries in task order, tdesck = the descriptors pointing at the copies.  Consecutive tasks of a
+  // host then stream consecutive lines instead of one random 64-byte line (or two) each: what bounds the triangle count on
+  // LiveJournal-shaped graphs (mean list 9).  Empty when they did not fit: the kernels then stream the rows themselves
+  DevOwn<int> colk;
+  DevOwn<int2> tdesck;
+  unsigned long long n_copy_keys = 0;  // keys of the copies
+  // the hub corner the lists leave out (gm_ctc.hip): no task of a row >= skip_from; core_h = nv - skip_from vertices (0 / 0x7fffffff: none)
+  int core_h = 0;
+  int skip_from = 0x7fffffff;
+};
+// The symmetric bit matrix of the corner the task lists leave out (core_h / 32 words per row), and first[row][word] = position of the
+// word's first entry inside its row.  Built by ensure_sup_corner (gm_tables.hip); read by launch_pattern (core_tc_block_kernel<true>).
+struct SupCorner {
+  DevOwn<unsigned> csym;
+  DevOwn<unsigned short> cfirst;
+};
+// MATCH MASKS of the in-edge tasks with long tails: per DAG entry / per task the offset of the task's mask in the arena (64-bit words;
+// kNoMask: the task keeps its atomics), the arena itself (written and read by every launch).  Built by ensure_sup_masks (gm_tables.hip);
+// not applicable: DAG not topological, arena beyond 2^32 words, no room, GM_SUP_NO_MASKS.  Read by plan_pattern / fill_mine_params /
+// launch_pattern and gm_sup_mask_info.
+struct SupMasks {
+  DevOwn<unsigned> emoff, tmoff;
+  DevOwn<unsigned long long> smask;
+  unsigned long long words = 0;
+  DevOwn<int> far_rows;  // the rows with tails of more than 64 keys (masks of several words), widest ids first
+  int n_far_rows = 0;
+  int min_tail = 0;      // the shortest tail with a mask the offsets were laid out for (0: kSupMaskMinTail; sup_mask_min_tail)
+};
+// nv <= 2^24: instead of descriptors that point at copies, the copies ARE the task list of the short lists -- a key stream in host order,
+// every key tagged with its host's low 8 bits (GraphView::kst), offsets per host vertex, and the longer lists as their own task lists
+// (trpl / tdescl).  No descriptor, no row search, no flattening for the short lists: one coalesced load per 64 keys.
+// Built by ensure_keystream (gm_tables.hip), first set; not applicable: ids beyond 24 bits, keys beyond the 32-bit index, GM_TC_NO_KEY_STREAM.
+// Read by plan_pattern / fill_mine_params / launch_pattern, gm_tc_core_info / gm_tc_pairs_info.
+struct KeyStream {
+  DevOwn<unsigned> kst;  // the stream itself
+  DevOwn<int> rp;
+  DevOwn<int> trpl;
+  DevOwn<int2> tdescl;
+  unsigned long long n_keys = 0;  // keys of the stream
+  int n_long_tasks = 0;
+  int lmax = 0;                   // the limit of a "short" list the stream was built with
+  // built for the edge supports (the first caller was ensure_keystream(g, true)): per key {entry it was copied from, entry of its task's
+  // own edge}, per longer list the entry of its task's own edge.  Empty otherwise: KeyEntries below
+  DevOwn<int2> kst_et;
+  DevOwn<int> tedgel;
+  // triangle count: the out-edges of the last core_h vertices are counted on the matrix cores from the corner of the hub core (gm_ctc.hip)
+  // and the stream / the longer lists hold no task of a row >= skip_from; 0 / 0x7fffffff: no such corner.  With a choice of block pairs
+  // (pair_region > 0) the three keep NAMING the base corner of the density rule (gm_tc_core_info) but the stream leaves out the chosen
+  // pairs' edges instead, rows >= skip_from host tasks again: read skip_from < nv only as "this stream lacks edges that the product
+  // takes", never as a row bound
+  int core_h = 0;
+  int skip_from = 0x7fffffff;
+  long long core_edges = 0;  // entries of the rows >= skip_from
+  // ... chosen per PAIR of 256-row blocks (IB <= JB) of a region at the end of the core bitmap instead of as a full triangle of rows
+  // (tc_pairs_setup, inside the stream's build): the stream then leaves out exactly the edges u -> v, u >= pair_from, whose bit
+  // IB * nb + JB of pair_bits is set, and the product walks pair_tasks (CoreTcParams::tasks).  pair_region = 0: no selection
+  int pair_region = 0, pair_from = 0x7fffffff;
+  DevOwn<unsigned> pair_bits;
+  DevOwn<unsigned> pair_tasks;
+  int n_pair_tasks = 0;
+  long long pair_info[6] = {0, 0, 0, 0, 0, 0};  // gm_tc_pairs_info
+};
+// The entries of a key stream that was built WITHOUT them, for the edge supports: a second set kst2 / tdescl2 (same offsets, its own order
+// of arrival) with its kst_et / tedgel.  Built by ensure_keystream(g, true) (gm_tables.hip) after the first set; fill_mine_params reads
+// the second set where it exists, else the first set's own entries.
+struct KeyEntries {
+  DevOwn<int2> kst_et;
+  DevOwn<int> tedgel;
+  DevOwn<unsigned> kst2;
+  DevOwn<int2> tdescl2;
+};
+// The rows beyond the stage of the task-list kernels (> kTctStageMax entries): ids and the prefix of their lengths.  Built by
+// ensure_long_rows (gm_tables.hip); read by launch_pattern.
+struct LongRows {
+  DevOwn<int> rows;
+  DevOwn<long long> prefix;
+  int n = 0;
+  long long edges = 0;
+};
+// A topologically numbered DAG: dense adjacency bitmap of its LAST h vertices (the hubs, when the numbering is by degree) -- row v - base
+// holds bit w - base for every edge v -> w.  The rows of the wide vertices' 4-clique matrices whose first endpoint lies in this core are
+// GATHERED from it (gm_cgather.hip), the triangle count takes its corner (gm_ctc.hip).  Built by ensure_core_bitmap (gm_tables.hip); not
+// applicable: not topological, too small, no room, GM_CORE_H = 0.  Read by tc_core_size / tc_pairs_setup / ensure_core_tri /
+// get_clique_plan, launch_clique_wide / launch_pattern, gm_tc_core_info.
+struct HubCore {
+  DevOwn<unsigned> bits;
+  int h = 0, base = 0;
+};
+// ... and the same bits cut into BLOCKS of consecutive rows for the blocked gather (gm_cgather.hip cgatherb_kernel).  Built by
+// ensure_core_tri (gm_tables.hip); not applicable: no core bitmap, no room.  Read by build_gather_index, launch_clique_wide,
+// gm_clique4_gather_info.
+struct CoreBlocks {
+  DevOwn<unsigned> tri;     // block images: of every core row the words from its diagonal word on
+  DevOwn<int> rowbase;      // per core row: offset inside its block's image - first stored word
+  DevOwn<int> bid;          // per core row: its block
+  DevOwn<int4> blk;         // per block: {first row, rows, image offset, image words}
+  int n = 0;
+};
+// k-clique: the wide DAG vertices (clique_is_wide), longest rows first.  Built and read by get_clique_plan (gm_tables.hip).
+struct WideVerts {
+  DevOwn<int> sorted;
+  size_t n = 0;
+};
+// What is true of the graph itself, each found on first use (the slow path takes g->mu: no caller may hold it).
+struct GraphFacts {
+  Once<bool> rows_sorted;    // every row strictly ascending (graph_rows_sorted): the solvers refuse a handle that is not
+  Once<bool> topological;    // every edge goes to a larger id, rows sorted (graph_is_topological)
+  Once<unsigned long long> giant_edges;  // sum of the rows beyond kStageCapBig entries (giant_task_edges, gm_launch.hip)
+  Once<double> tri_per_edge;  // triangles per entry of this DAG, estimated from a sample (ensure_tri_per_edge: the edge supports' stream switch)
+  Once<double> mean_sq_deg;   // sum_v d(v)^2 / ne: the mean length of the row an entry sits in (ensure_mean_sq_deg: topo_view)
+  Once<unsigned long long> sum_c2;  // sum_v C(d(v),2) (gm_motif_formula)
+  Once<std::vector<int>> h_rp;  // host copy of the offsets (host_rp): download, k-clique tables, SgL renumbering, chunk dumps
+};
+// SgL (gm_solve_sgl.hip): what the map solvers index the graph by.  Each is built by the first call that needs it and read by the
+// launches of that solver.
+struct RectIdx {  // ensure_idx0: #neighbours below v
+  DevOwn<int> idx0;
+};
+struct WedgeBlocks {  // rectangle per wedge block (sgl_rect_wedges): the wedge-block prefix
+  DevOwn<unsigned long long> prefix;
+  unsigned long long n = 0;
+};
+struct CentreTaskList {  // rectangle / house by wedge accumulation without LDS maps (build_centre_tasks): the task list
+  DevOwn<int4> tasks;
+  unsigned long long n = 0;
+};
+struct HouseTables {  // ensure_edge_tables: the per-entry tables of the house
+  DevOwn<unsigned> t, tlt;
+};
+struct HouseBlocks {  // house per entry block: per-entry task-block prefix
+  DevOwn<unsigned long long> prefix;
+  unsigned long long n = 0;
+};
+// rectangle / house with the heavy centres' maps in LDS (round 6, gm_mine.hip rect_lds_kernel / house_lds_kernel): the id ranges and the
+// plan (ensure_rect_plan / ensure_house_plan)
+struct RectLdsPlan {
+  gm::RectLdsRanges ranges;
+  CentrePlan plan;
+};
+struct HouseLdsPlan {
+  gm::HouseLdsRanges ranges;
+  CentrePlan plan;
+};
+// the weighted 4-cycle kernel of the 6-vertex closed forms (gm_wrect.hip, gm_sgl6_raw), on the graph it walks (the copy numbered ascending
+// in degree, or the handle itself): ids per range (GM_WRECT_RANGE), ranges per bit of the row masks, the masks, the task list
+struct WrectPlan {
+  DevOwn<unsigned long long> mask;
+  DevOwn<int2> tasks;
+  unsigned long long n_tasks = 0;
+  int range = 0, grp = 1;
+};
+struct SymDegrees {  // the 5-vertex closed forms (gm_sgl5_raw): the symmetric degrees of the DAG's vertices
+  DevOwn<int> deg;
+};
+// local counts (gm_solve_local.hip), on the SYMMETRIC handle
+struct RevIndex {  // per entry (u, v): the entry (v, u) (gm_ktruss / gm_truss_decompose / gm_clique_local)
+  DevOwn<int> rev;
+};
+struct ListOffsets {  // triangle listing (gm_tc_list): the first slot of every batch of 64 entries of the oriented copy (batches + 1 values,
+  DevOwn<unsigned long long> off;  // the last one T), counted and scanned by the first call and kept for the windows that follow
+  unsigned long long total = 0;
 };
 
 struct gm_graph {
@@ -305,94 +482,93 @@ struct gm_graph {
   int *d_col = nullptr;  // col_idx: the view every reader uses -- d_col_mem's array, or the caller's (gm_graph_from_device: borrowed)
   DevOwn<int> d_col_mem;
   DevOwn<int> d_symdeg;  // a DAG made by gm_graph_orient: the degrees of the symmetric graph it came from (its topological numbering sorts by them)
-  DevOwn<int2> d_edesc;  // per CSR entry: {rp[col[e]], degree(col[e])}, built on first use (ensure_edesc)
-  DevOwn<int> d_trp;     // task lists of the shorter-list-streams triangle count (ensure_tasklists): row offsets (nv + 1)
-  int2 *d_tdesc = nullptr;  // ... and per task {rp[partner], d(partner)}: the view of d_tdesc_mem that ensure_tasklists publishes, read without the lock
-  DevOwn<int2> d_tdesc_mem;
-  DevOwn<int> d_tedge;   // ... and (edge supports only: ensure_tasklists(g, true)) the task's own DAG entry
-  // ... and TASK-MAJOR COPIES of the short lists (ensure_tasklists): d_colk = col followed by the keys of every list of <= GM_TC_INLINE_MAX
-  // entries in task order, d_tdesck = the descriptors pointing at the copies.  Consecutive tasks of a host then stream consecutive
-  // lines instead of one random 64-byte line (or two) each: what bounds the triangle count on LiveJournal-shaped graphs (mean list 9)
-  DevOwn<int> d_colk;
-  DevOwn<int2> d_tdesck;
-  unsigned long long n_inline_keys = 0;
-  // nv <= 2^24: instead of descriptors that point at the copies, the copies ARE the task list of the short lists -- a key stream in host
-  // order, every key tagged with its host's low 8 bits (GraphView::kst), offsets per host vertex, and the longer lists as their own
-  // task lists (d_trpl / d_tdescl).  No descriptor, no row search, no flattening for the short lists: one coalesced load per 64 keys.
-  DevOwn<unsigned> d_kst;  // the stream itself (ensure_keystream, gm_tables.hip)
-  int kst_state = 0;          // 2: this handle cannot have one (ids beyond 24 bits, GM_TC_NO_KEY_STREAM)
-  int n_long_tasks = 0;
-  DevOwn<int> d_kst_rp;
-  DevOwn<int> d_trpl;
-  DevOwn<int2> d_tdescl;
-  // the same for the edge supports (ensure_keystream(g, true)): per key the DAG entry it was copied from and the entry of its task's own
-  // edge, per longer list the entry of its task's own edge.  They belong to d_kst / d_tdescl when the stream was built with them, else to
-  // a second set d_kst2 / d_tdescl2 (same offsets, its own order of arrival).
-  DevOwn<int2> d_kst_et;  // per key: {entry it was copied from, entry of its task's own edge}
-  DevOwn<int> d_tedgel;
-  DevOwn<unsigned> d_kst2;
-  DevOwn<int2> d_tdescl2;
-  int kst_lmax = 0;  // the limit of a "short" list the stream was built with
-  // the rows beyond the stage of the task-list kernels (> 2048 entries; ensure_long_rows): ids and the prefix of their lengths
-  DevOwn<int> d_long_rows;
-  DevOwn<long long> d_long_prefix;
-  int n_long_rows = -1;               // -1: not looked for yet
-  long long long_edges = 0;
-  DevOwn<unsigned> d_sup;  // edge supports: one counter per DAG entry (gm_sup.hip)
-  // the 5-vertex closed forms (gm_wtri.hip, gm_sgl5_raw): a support array of their own (the diamond's d_sup is not touched), d(u) + d(v) per
-  // entry, the symmetric degrees (built once), 2 T_v per vertex, and the eight sums of one call
-  DevOwn<unsigned> d_w5sup, d_w5ed;
-  DevOwn<int> d_w5deg;
-  DevOwn<unsigned long long> d_w5tv2, d_w5out;
-  // the 6-vertex closed forms (gm_wrect.hip, gm_sgl6_raw).  On the DAG of the 5-vertex pass: e1 per vertex.  On the graph the weighted
-  // 4-cycle kernel walks (the copy numbered ascending in degree, or the handle itself): its plan, built once -- ids per range
-  // (GM_WRECT_RANGE), ranges per bit of the row masks, the masks, the task list
-  DevOwn<unsigned> d_s6e1;
-  DevOwn<unsigned long long> d_wrect_mask;
-  DevOwn<int2> d_wrect_tasks;
-  unsigned long long n_wrect_tasks = 0;
-  int wrect_range = 0, wrect_grp = 1;
-  bool wrect_ready = false;
-  // local counts and the k-truss (gm_local.hip, gm_tc_local / gm_ktruss / gm_truss_decompose).  A renumbered copy remembers its numbering;
-  // the DAG the triangle pass runs on has a support array of the local counts' own (d_sup and d_w5sup are not touched); the SYMMETRIC
-  // handle holds what lives in the caller's entry order: the supports / peeling state, the reverse-entry index (built once), the marks,
-  // the frontier list, the trussness, and the counters of a round
+  // ---- built on first use, published whole (the group structs above; gm_once.h) ------------------------------------------------------
+  Once<DevOwn<int2>> edesc;  // per CSR entry: {rp[col[e]], degree(col[e])} (ensure_edesc, gm_tables.hip; read by the table / task-list builds and fill_mine_params)
+  Once<TaskLists> tasklists;
+  Once<SupCorner> sup_corner;
+  Once<SupMasks> sup_masks;
+  Once<KeyStream> kst;
+  Once<KeyEntries> kst_entries;
+  Once<LongRows> long_rows;
+  Once<HubCore> core;
+  Once<CoreBlocks> core_blocks;
+  Once<WideVerts> wide;
+  GraphFacts facts;
+  Once<RectIdx> rect_idx;
+  Once<WedgeBlocks> wedge_blocks;
+  Once<CentreTaskList> rect_tasks, house_tasks;
+  Once<HouseTables> house_tables;
+  Once<HouseBlocks> house_blocks;
+  Once<RectLdsPlan> rect_lds;
+  Once<HouseLdsPlan> house_lds;
+  Once<WrectPlan> wrect;
+  Once<SymDegrees> w5deg;
+  Once<RevIndex> lrev;
+  Once<ListOffsets> list_off;
+  // gm_graph_sort_neighbors rewrites the rows: it refuses a handle on which one of these describes them already.  NOT checked (the list
+  // predates them): core, core_blocks, long_rows, sup_corner, sup_masks, kst_entries, facts other than sum_c2, rect_lds, house_lds, wrect,
+  // w5deg, lrev, list_off, relabel_cache[2], clique_plans -- most of them cannot exist without one that is
+  bool rows_in_use() const {
+    return !tables.empty() || edesc.built() || tasklists.built() || kst.built() || dag_cache || relabel_cache[0] || relabel_cache[1] || rect_idx.built() ||
+           wedge_blocks.built() || rect_tasks.built() || house_tables.built() || house_tasks.built() || house_blocks.built() || !bitmap_sets.empty() ||
+           wide.built() || facts.sum_c2.built();
+  }
+  // ---- keyed lists under g->mu, handed out whole ---------------------------------------------------------------------------------------
+  std::list<ChunkTable> tables;          // list: handed-out pointers stay valid (get_table)
+  std::list<BitmapSet> bitmap_sets;      // the hub rows' bitmaps, shared by the tables (get_table)
+  // k-clique: the per-(rank, world, policy) plans of the two phases of the wide vertices (row-group chunks of phase 1, count classes of
+  // phase 2, matrix offsets, arena rounds; get_clique_plan)
+  std::list<CliquePlan> clique_plans;
+  // ---- work buffers: grown on demand by the calls named, which is legal because one call at a time runs per handle; no protocol ---------
+  struct DiamondWork {  // gm_diamond_support_* / the diamond of gm_sgl (gm_sup.hip): one counter per DAG entry
+    DevOwn<unsigned> sup;
+  } diamond;
+  // gm_sgl5_raw / gm_sgl6_raw (gm_wtri.hip, gm_wrect.hip), on the DAG of the pass: a support array of their own (the diamond's is not
+  // touched), d(u) + d(v) per entry, 2 T_v per vertex, the eight sums of one call, e1 per vertex of the 6-vertex forms
+  struct ClosedFormWork {
+    DevOwn<unsigned> sup, ed;
+    DevOwn<unsigned long long> tv2, out;
+    DevOwn<unsigned> s6e1;
+  } w5;
+  // gm_tc_local / gm_ktruss / gm_truss_decompose / gm_clique_local (gm_local.hip, gm_kcl_local.hip).  The DAG the triangle pass runs on has
+  // a support array of the local counts' own (sup); the SYMMETRIC handle holds what lives in the caller's entry order: the supports /
+  // peeling state, the marks, the frontier list, the trussness, the counters of a round
+  struct LocalWork {
+    DevOwn<unsigned> sup;    // per DAG entry (diamond_support_entries)
+    DevOwn<unsigned> ent;    // per entry of the symmetric graph: the support of its edge; while peeling, exact at the canonical entries
+    DevOwn<unsigned char> mark;
+    DevOwn<int> front;       // ne / 2 + 1 canonical entries
+    DevOwn<unsigned> truss;
+    DevOwn<unsigned> cnt;    // 64 bytes: [0] frontier size, [1] 0xFFFFFFFF - smallest alive support
+    // local k-clique counts, on the DAG the kernels run on: the k-cliques of every entry, the list of the rows beyond the LDS matrix, the
+    // workgroups' scratch slots.  On the SYMMETRIC handle: the counts in the caller's entry order when the caller gives no array for them
+    DevOwn<unsigned long long> kcl;   // per DAG entry: the counts, then (ne further values) the undivided sums of the out-edges
+    DevOwn<int> kcl_heavy;            // ne / (kKclLocalLdsRow + 1) + 1 rows, then ne / (kKclLocalSplitRow + 1) + 1 split rows
+    DevOwn<unsigned> kcl_scratch;
+    size_t kcl_scratch_bytes = 0;
+    DevOwn<unsigned long long> ent64; // per entry of the symmetric graph
+  } local;
+  struct MapWork {  // the global counter maps of run_rect_acc / run_house_acc (rectangle, pentagon, house by wedge accumulation)
+    DevOwn<unsigned> rect_acc;
+    size_t rect_acc_bytes = 0;
+    DevOwn<unsigned long long> house_acc;  // 64-bit maps
+    size_t house_acc_bytes = 0;
+    DevOwn<int> house_touched;
+    DevOwn<int> pent_touched;              // touched-vertex lists (same shape as rect_acc)
+    size_t pent_touched_bytes = 0;
+  } maps;
+  struct CliqueArena {  // launch_clique_wide (gm_clique, k = 4)
+    DevOwn<unsigned> mat;      // matrix arena (largest round so far)
+    size_t mat_bytes = 0;
+    DevOwn<unsigned> queue;    // dequeue words of the wide launches of one call (zeroed per call)
+  } arena;
+  struct Scratch {  // the launch layer's per-call scratch (gm_launch.hip)
+    DevOwn<unsigned> p;
+    size_t bytes = 0;
+  } scratch;
+  // ---- the handle's own ---------------------------------------------------------------------------------------------------------------------
   DevOwn<int> d_newid;       // the topological copy made by get_relabeled (mode 2): id in the graph it was made from -> id here (nv)
-  DevOwn<unsigned> d_lsup;   // per DAG entry (diamond_support_entries)
-  DevOwn<unsigned> d_lent;   // per entry of the symmetric graph: the support of its edge; while peeling, exact at the canonical entries
-  DevOwn<int> d_lrev;        // per entry (u, v): the entry (v, u)
-  bool lrev_ready = false;
-  DevOwn<unsigned char> d_lmark;
-  DevOwn<int> d_lfront;      // ne / 2 + 1 canonical entries
-  DevOwn<unsigned> d_ltruss;
-  DevOwn<unsigned> d_lcnt;   // 64 bytes: [0] frontier size, [1] 0xFFFFFFFF - smallest alive support
-  // local k-clique counts (gm_kcl_local.hip, gm_clique_local).  On the DAG the kernels run on: the k-cliques of every entry, the list of
-  // the rows beyond the LDS matrix, the workgroups' scratch slots.  On the SYMMETRIC handle: the counts in the caller's entry order when
-  // the caller gives no array for them
-  DevOwn<unsigned long long> d_lkcl;   // per DAG entry: the counts, then (ne further values) the undivided sums of the out-edges
-  DevOwn<int> d_kcl_heavy;             // ne / (kKclLocalLdsRow + 1) + 1 rows, then ne / (kKclLocalSplitRow + 1) + 1 split rows
-  DevOwn<unsigned> d_kcl_scratch;
-  size_t kcl_scratch_bytes = 0;
-  DevOwn<unsigned long long> d_lent64; // per entry of the symmetric graph
-  // triangle listing (gm_list.hip, gm_tc_list), on the SYMMETRIC handle: the first slot of every batch of 64 entries of the oriented copy
-  // (batches + 1 values, the last one T), counted and scanned by the first call and kept for the windows that follow
-  DevOwn<unsigned long long> d_list_off;
-  unsigned long long list_total = 0;
-  bool list_ready = false;
-  // ... and the MATCH MASKS of the in-edge tasks with long tails (ensure_sup_masks, gm_tables.hip): per DAG entry / per task the offset of
-  // the task's mask in the arena (64-bit words; kNoMask: the task keeps its atomics), the arena itself (written and read by every launch)
-  DevOwn<unsigned> d_emoff, d_tmoff;
-  DevOwn<unsigned long long> d_smask;
-  unsigned long long smask_words = 0;
-  DevOwn<int> d_sup_far_rows;  // the rows with tails of more than 64 keys (masks of several words), widest ids first
-  int n_sup_far_rows = 0;
-  int smask_min_tail = 0;  // (0: kSupMaskMinTail)
-  int smask_state = 0;  // 0 unknown, 1 built, 2 not applicable (DAG not topological, arena beyond 2^32 words, GM_SUP_NO_MASKS)
-  std::vector<int> h_rp;  // host copy of the offsets, fetched on first use (host_rp): download, k-clique tables, SgL renumbering
-  std::list<ChunkTable> tables;  // list: handed-out pointers stay valid
   DevOwn<unsigned long long> d_counters;  // [4] + queue word, 64 B
-  DevOwn<unsigned> d_scratch;
-  size_t scratch_bytes = 0;
   static constexpr int kEvRing = 64;  // HIP-event pairs of the most recent launches
   hipEvent_t ev[kEvRing][4] = {};      // [0], [1]: around the launch; [2], [3]: around its hub-corner kernel (gm_ctc.hip) when it has one
   bool ev_corner[kEvRing] = {};
@@ -400,85 +576,9 @@ struct gm_graph {
   int cu_count = 256;
   gm_graph *dag_cache = nullptr;          // oriented copy, built on demand by gm_motif_formula
   gm_graph *relabel_cache[3] = {nullptr, nullptr, nullptr};  // renumbered copies: by degree ascending / descending, topological (get_relabeled)
-  int sorted_state = 0;              // 0 unknown, 1 every row strictly ascending, 2 not (graph_rows_sorted): the solvers refuse such a handle
-  int topo_state = 0;                // 0 unknown, 1 every edge goes to a larger id, 2 not (graph_is_topological)
-  unsigned long long giant_edges = ~0ull;  // sum of the rows beyond kStageCapBig entries (~0: not computed yet)
-  double tri_per_edge = -1.0;        // triangles per entry of this DAG, estimated from a sample (-1: not yet; the edge supports' stream switch)
-  double mean_sq_deg = -1.0;         // sum_v d(v)^2 / ne: the mean length of the row an entry sits in (-1: not computed yet; topo_view)
   bool topo_relabel_failed = false;  // the (degree, id) numbering is not topological for this DAG: it runs as given
-  const gm_graph *ring_alias = nullptr;
+  const gm_graph *ring_alias = nullptr;  // handle whose event ring holds this handle's most recent launch
   const gm_graph *ring_extra[2] = {nullptr, nullptr};  // 4-motif: the handles that ran the other sub-launches of the most recent calls (gm_kernel_times adds them)
-  DevOwn<int> d_idx0;                  // rectangle: #neighbours below v, and the wedge-block prefix
-  DevOwn<unsigned long long> d_wblock_prefix;
-  unsigned long long n_wblocks = 0;
-  DevOwn<int4> d_rect_tasks;          // rectangle by wedge accumulation: task list, counter maps
-  unsigned long long n_rect_tasks = 0;
-  // rectangle / house with the heavy centres' maps in LDS (round 6, gm_mine.hip rect_lds_kernel / house_lds_kernel): the id ranges, the plans
-  gm::RectLdsRanges rect_ranges;
-  gm::HouseLdsRanges house_ranges;
-  CentrePlan rect_plan, house_plan;
-  DevOwn<unsigned> d_rect_acc;
-  size_t rect_acc_bytes = 0;
-  DevOwn<unsigned> d_house_t;         // house by wedge accumulation: per-entry tables, task list, 64-bit maps
-  DevOwn<unsigned> d_house_tlt;
-  DevOwn<int4> d_house_tasks;
-  unsigned long long n_house_tasks = 0;
-  DevOwn<unsigned long long> d_house_acc;
-  size_t house_acc_bytes = 0;
-  DevOwn<int> d_house_touched;
-  DevOwn<int> d_pent_touched;         // pentagon by wedge accumulation: touched-vertex lists (same shape as d_rect_acc)
-  size_t pent_touched_bytes = 0;
-  DevOwn<unsigned long long> d_house_prefix;  // house: per-entry task-block prefix
-  unsigned long long n_house_blocks = 0;   // handle whose event ring holds this handle's most recent launch
-  unsigned long long sum_c2 = 0;          // sum_v C(d(v),2)
-  bool sum_c2_valid = false;
-  // k-clique: the wide DAG vertices (clique_is_wide), longest rows first, and the per-(rank, world, policy) plans of their two
-  // phases (row-group chunks of phase 1, count classes of phase 2, matrix offsets, arena rounds)
-  std::list<BitmapSet> bitmap_sets;
-  DevOwn<int> d_wide_sorted;
-  size_t n_wide = 0;
-  bool wide_valid = false;
-  std::list<CliquePlan> clique_plans;
-  DevOwn<unsigned> d_wide_mat;      // matrix arena (largest round so far)
-  size_t wide_mat_bytes = 0;
-  DevOwn<unsigned> d_wide_queue;    // dequeue words of the wide launches of one call (zeroed per call)
-  // k-clique on a topologically numbered DAG: dense adjacency bitmap of its LAST core_h vertices (the hubs, when the numbering is by
-  // degree) -- row v - core_base holds bit w - core_base for every edge v -> w; the rows of the wide vertices' matrices whose first
-  // endpoint lies in this core are GATHERED from it (gm_cgather.hip) instead of being built by streamed intersections
-  DevOwn<unsigned> d_core;
-  int core_h = 0, core_base = 0;       // core_h = 0: not built / not applicable (ensure_core_bitmap)
-  int core_state = 0;                  // 0 unknown, 1 built, 2 not applicable
-  // ... and the same bits cut into BLOCKS of consecutive rows for the blocked gather (gm_cgather.hip cgatherb_kernel; ensure_core_tri)
-  DevOwn<unsigned> d_cg_tri;        // block images: of every core row the words from its diagonal word on
-  DevOwn<int> d_cg_rowbase;         // per core row: offset inside its block's image - first stored word
-  DevOwn<int> d_cg_bid;             // per core row: its block
-  DevOwn<int4> d_cg_blk;            // per block: {first row, rows, image offset, image words}
-  int n_cg_blocks = 0;
-  int cg_tri_state = 0;                // 0 unknown, 1 built, 2 not applicable (no core bitmap, no room)
-  // triangle count: the out-edges of the last tc_core_h vertices are counted on the matrix cores from the corner of d_core (gm_ctc.hip) and
-  // the key stream / the longer lists of this handle hold no task of a row >= kst_skip_from (ensure_keystream); 0 / nv: no such corner.
-  // With a choice of block pairs (tc_pair_region > 0, below) the three keep NAMING the base corner of the density rule (gm_tc_core_info)
-  // but the stream leaves out the chosen pairs' edges instead, rows >= kst_skip_from host tasks again: read kst_skip_from < nv only as
-  // "this stream lacks edges that the product takes", never as a row bound
-  int tc_core_h = 0;
-  int kst_skip_from = 0x7fffffff;
-  long long tc_core_edges = 0;         // entries of the rows >= kst_skip_from
-  // ... chosen per PAIR of 256-row blocks (IB <= JB) of a region at the end of the core bitmap instead of as a full triangle of rows
-  // (tc_pairs_setup, gm_tables.hip): the stream then leaves out exactly the edges u -> v, u >= tc_pair_from, whose bit
-  // IB * nb + JB of d_tc_pair_bits is set, and the product walks d_tc_pair_tasks (CoreTcParams::tasks).  tc_core_h / kst_skip_from /
-  // tc_core_edges keep describing the base corner the density rule names (gm_tc_core_info).  tc_pair_region = 0: no selection
-  int tc_pair_region = 0, tc_pair_from = 0x7fffffff;
-  DevOwn<unsigned> d_tc_pair_bits;
-  DevOwn<unsigned> d_tc_pair_tasks;
-  int n_tc_pair_tasks = 0;
-  long long tc_pair_info[6] = {0, 0, 0, 0, 0, 0};  // gm_tc_pairs_info
-  // the same for the TASK LISTS (ensure_tasklists: the edge supports, the triangle count without a key stream): no task of a row >= tl_skip_from;
-  // the supports of the corner's edges come from the symmetric corner d_csym (tl_core_h / 32 words per row) with d_cfirst[row][word] = position
-  // of the word's first entry inside its row (ensure_sup_corner, gm_tables.hip; core_tc_block_kernel<true>, gm_ctc.hip)
-  int tl_core_h = 0;
-  int tl_skip_from = 0x7fffffff;
-  DevOwn<unsigned> d_csym;
-  DevOwn<unsigned short> d_cfirst;
   hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr};  // class kernels that cannot fill the chip run beside the others (run_pattern)
   hipEvent_t aux_done[3] = {nullptr, nullptr, nullptr};
   TempPool pool;  // temporaries of the setup paths (PoolScope)
@@ -618,17 +718,17 @@ int convert_offsets(const int64_t *rp64, int nv, long long ne, std::vector<int> 
 int get_relabeled(gm_graph *g, int mode, gm_graph **out);  // gm_graph.hip: cached renumbered copy (0 / 1 by degree, 2 topological)
 int graph_is_topological(gm_graph *g, bool *out);
 int graph_rows_sorted(gm_graph *g, bool *out);
-int ensure_long_rows(gm_graph *g);  // (gm_tables.hip) d_long_rows / d_long_prefix: the rows of more than kTctStageMax entries
-int ensure_core_tri(gm_graph *g);     // (gm_tables.hip) d_cg_* of a handle with a core bitmap; GM_OK also when not applicable
-int ensure_core_bitmap(gm_graph *g);  // (gm_tables.hip) d_core / core_h / core_base of a topologically numbered DAG; GM_OK also when not applicable
+int ensure_long_rows(gm_graph *g);  // (gm_tables.hip) g->long_rows: the rows of more than kTctStageMax entries
+int ensure_core_tri(gm_graph *g);     // (gm_tables.hip) g->core_blocks of a handle with a core bitmap; GM_OK also when not applicable
+int ensure_core_bitmap(gm_graph *g);  // (gm_tables.hip) g->core of a topologically numbered DAG; GM_OK also when not applicable
 int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned long long part_cap, int stage_cap, ChunkTable **out,
               const RowFilter &rf = RowFilter(), int bitmap_min_deg = kBitmapMinDeg);
 int ensure_edesc(gm_graph *g);
-int ensure_tasklists(gm_graph *g, bool with_edges = false);
+int ensure_tasklists(gm_graph *g);
 int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core = false);  // allow_core: the rows of the hub core may stay out (gm_ctc.hip)
 int sup_mask_min_tail(const gm_graph *g);  // (gm_tables.hip) kSupMaskMinTail or the option GM_SUP_MASK_MIN when the handle's masks were laid out
-int ensure_sup_corner(gm_graph *g);  // (gm_tables.hip) d_csym / d_cfirst of a handle whose task lists leave a hub corner out
-int ensure_sup_masks(gm_graph *g);  // (gm_tables.hip) d_emoff / d_tmoff / d_smask of a topologically numbered DAG with task lists; GM_OK also when not applicable
+int ensure_sup_corner(gm_graph *g);  // (gm_tables.hip) g->sup_corner of a handle whose task lists leave a hub corner out
+int ensure_sup_masks(gm_graph *g);  // (gm_tables.hip) g->sup_masks of a topologically numbered DAG with task lists; GM_OK also when not applicable
 int ensure_mean_sq_deg(gm_graph *g);
 int ensure_tri_per_edge(gm_graph *g);  // (gm_launch.hip) |N+(u) ^ N+(v)| averaged over a sample of the DAG's entries
 unsigned long long task_part_cap(gm_graph *g, int world);

@@ -91,7 +91,7 @@ inline void record_ran_on_dag(const gm_graph *sym, const gm_graph *run_on) {
 }
 
 // the in-edge tasks stream only the part of N+(u) beyond v: a topologically numbered DAG (GM_TC_NO_TRIM: A/B, whole lists)
-inline bool tails_trimmed(const gm_graph *g) { return g->topo_state == 1 && !gm_sweep_env("GM_TC_NO_TRIM"); }
+inline bool tails_trimmed(const gm_graph *g) { return *g->facts.topological && !gm_sweep_env("GM_TC_NO_TRIM"); }
 
 // workgroups of a launch: one per unit of work, at most per_cu on every CU, at least one
 inline int clamp_grid(long long want, long long cap) { return (int)std::max<long long>(1, std::min<long long>(want, cap)); }
@@ -106,7 +106,7 @@ int grow_dev(DevOwn<T> &buf, size_t *bytes, size_t need) {
   *bytes = need;
   return GM_OK;
 }
-inline int ensure_scratch(gm_graph *g, size_t need) { return grow_dev(g->d_scratch, &g->scratch_bytes, need); }
+inline int ensure_scratch(gm_graph *g, size_t need) { return grow_dev(g->scratch.p, &g->scratch.bytes, need); }
 
 // this rank's share of n units (gm_partition) as the first / step / count of a kernel's parameters; returns the count
 template <class P>

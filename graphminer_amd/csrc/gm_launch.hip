@@ -67,13 +67,11 @@ __global__ __launch_bounds__(256) void giant_edges_kernel(int nv, const int *__r
   if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
 }
 static int giant_task_edges(gm_graph *g, unsigned long long *out) {
-  if (g->giant_edges == ~0ull) {
-    unsigned long long s = 0;
-    if (int rc = reduce_to_u64(g, g->nv > 0, "giant_edges_kernel", &s, [&](unsigned long long *d_s) { hipLaunchKernelGGL(giant_edges_kernel, rows_grid(g), dim3(256), 0, 0, g->nv, g->d_rp, d_s); })) return rc;
-    g->giant_edges = s;
-  }
-  *out = g->giant_edges;
-  return GM_OK;
+  const int rc = g->facts.giant_edges.ensure(g->mu, [&](unsigned long long &s) {
+    return reduce_to_u64(g, g->nv > 0, "giant_edges_kernel", &s, [&](unsigned long long *d_s) { hipLaunchKernelGGL(giant_edges_kernel, rows_grid(g), dim3(256), 0, 0, g->nv, g->d_rp, d_s); });
+  });
+  *out = *g->facts.giant_edges;
+  return rc;
 }
 
 // ---- common launch prologue / epilogue of every mining entry point (LaunchCtx, the dequeue words: gm_launch.h) ----------------------
@@ -194,7 +192,7 @@ static int plan_pattern(const LaunchCtx &c, PatternPlan &pl) {
   // their vertices -- a hub hosts 10^5 in-edges -- so their cost is counted from the task lists and heavy chunks are cut into
   // parts of 1 M keys / world (>= 128 K): one-GPU simulation of an 8-rank share of R-MAT-22, parts of 8 M / 512 K / 128 K / 32 K keys:
   // 5.36 / 1.18 / 0.99 / 1.15 ms per rank (one GPU: 6.50 / 6.54 / 6.73 / 8.09 ms), profiles/r02/ab_tct_part_cap.log
-  pl.use_tct = pl.pat == PAT_TC && !(la->tune[6] & GM_T6_TC_CHUNKED) && la->tune[5] != 1 && g->ne > 0 && !gm_sweep_env("GM_HOST_TABLES");
+  pl.use_tct = pl.pat == PAT_TC && !(la->tune[6] & GM_T6_TC_CHUNKED) && la->tune[5] != 1 && g->ne > 0;
   // The 2048-entry stage costs occupancy (four instead of six workgroups per CU, R-MAT-22 on it: 3.04 vs 2.57 ms), and only the few hosts with
   // rows of 1025 .. 2048 entries need it: a graph that has such rows runs TWO tables -- hosts with rows <= 1024 on the 1024-entry kernel,
   // the others on the 2048-entry one (own dequeue word).  GM_TCT_STAGE_BIG: the 2048-entry stage for every host (A/B).
@@ -239,22 +237,22 @@ static int plan_pattern(const LaunchCtx &c, PatternPlan &pl) {
     bool sup_stream = false;
     if (pl.support && !pl.wtri && !(la->tune[6] & GM_T6_NO_KEYSTREAM)) {  // (the weighted pass reads the full task lists)
       if (const char *e = gm_opt("GM_SUP_STREAM")) sup_stream = atoi(e) != 0;
-      else sup_stream = ensure_mean_sq_deg(g) == GM_OK && g->mean_sq_deg < (double)kSupStreamMaxMeanRow && ensure_tri_per_edge(g) == GM_OK &&
-                        g->tri_per_edge < 0.5;
+      else sup_stream = ensure_mean_sq_deg(g) == GM_OK && *g->facts.mean_sq_deg < (double)kSupStreamMaxMeanRow && ensure_tri_per_edge(g) == GM_OK &&
+                        *g->facts.tri_per_edge < 0.5;
     }
     if ((sup_stream || !pl.support) && !(la->tune[6] & GM_T6_NO_KEYSTREAM)) {
       if (const int rc_k = ensure_keystream(g, pl.support, &pl.use_kst, !pl.support && !pl.tct_long)) return rc_k;  // (the triangle count: the hub corner may stay out, gm_ctc.hip)
     }
     if (!pl.use_kst) {
-      if (const int rc_t = ensure_tasklists(g, pl.support)) return rc_t;
+      if (const int rc_t = ensure_tasklists(g)) return rc_t;
     }
   }
-  if (pl.support && !pl.sup_part && !pl.wtri && !g->d_sup) HIP_TRY(g->d_sup.alloc(sizeof(unsigned) * (size_t)std::max<long long>(g->ne, 1)));
+  if (pl.support && !pl.sup_part && !pl.wtri && !g->diamond.sup) HIP_TRY(g->diamond.sup.alloc(sizeof(unsigned) * (size_t)std::max<long long>(g->ne, 1)));
   // match masks instead of one atomic per streamed edge (gm_sup.hip): one GPU, the task lists, a topologically numbered DAG
   // (tune[6] & GM_T6_SUP_ATOMICS: A/B switch, every streamed edge by an atomic)
   if (pl.support && !pl.sup_part && !pl.wtri && world == 1 && pl.use_tct && !pl.use_kst && !(la->tune[6] & GM_T6_SUP_ATOMICS)) {
     if (const int rc_m = ensure_sup_masks(g)) return rc_m;
-    pl.sup_masks = g->smask_state == 1;
+    pl.sup_masks = g->sup_masks.built();
   }
   setup_trace("run_pattern: task lists");
   // the hosts with rows of 1025 .. 2048 entries, on the 2048-entry kernel -- when a rank's share of them can fill the chip about twice: the two
@@ -263,7 +261,7 @@ static int plan_pattern(const LaunchCtx &c, PatternPlan &pl) {
   // edge supports - / 51.0 / 26.0 / 16.7 against - / 60.5 / 30.4 / 15.5 (profiles/r04/ab_split_stage.txt).  GM_TCT_SPLIT_ALWAYS: at every world.
   if (pl.split_stage) {
     RowFilter rb;
-    rb.tct = (pl.use_kst && !pl.support && g->kst_skip_from < g->nv) ? 2 : 1;  // (2: priced from the stream without the hub corner, gm_tables.hip)
+    rb.tct = (pl.use_kst && !pl.support && g->kst->skip_from < g->nv) ? 2 : 1;  // (2: priced from the stream without the hub corner, gm_tables.hip)
     rb.only_lo = kStageCap;
     rb.only_hi = kTctStageMax;
     if (const int rc_b = get_table(g, pl.target, true, 0, pl.part_cap, kTctStageMax, &pl.tab_big, rb, kBitmapMinDeg)) return rc_b;
@@ -274,7 +272,7 @@ static int plan_pattern(const LaunchCtx &c, PatternPlan &pl) {
     }
   }
   // the triangles of the hub corner on the matrix cores (gm_ctc.hip): this handle's key stream holds no task of the corner's rows
-  pl.corner_from = pl.use_kst ? g->kst_skip_from : (pl.use_tct ? g->tl_skip_from : 0x7fffffff);  // the rows the stream / the task lists in use leave out
+  pl.corner_from = pl.use_kst ? g->kst->skip_from : (pl.use_tct ? g->tasklists->skip_from : 0x7fffffff);  // the rows the stream / the task lists in use leave out
   pl.tc_core = pl.use_tct && !pl.support && pl.corner_from < g->nv;
   pl.sup_core = pl.support && !pl.wtri && !pl.use_kst && pl.corner_from < g->nv;  // (the weighted pass walks the corner's out-edges itself)
   if (pl.sup_core) {
@@ -410,32 +408,35 @@ static int fill_mine_params(PatternRun &r, int k) {
   memset(&p, 0, sizeof p);
   p.g = graph_view(g);
   if (int rc = ensure_edesc(g)) return rc;  // (the kernels read them unconditionally; -DGM_EDESC=0 builds gather rp[v] instead, for A/B runs)
-  p.g.edesc = g->d_edesc;
+  p.g.edesc = *g->edesc;
   if (pl.use_tct) {
-    p.g.trp = g->d_trp;
-    p.g.tdesc = g->d_tdesc;
-    p.g.tedge = pl.support ? g->d_tedge : nullptr;
+    const TaskLists &tl = *g->tasklists;
+    const KeyStream &ks = *g->kst;
+    p.g.trp = tl.trp;
+    p.g.tdesc = tl.tdesc;
+    p.g.tedge = pl.support ? tl.tedge.get() : nullptr;
     if (pl.sup_masks) {
-      p.g.tmoff = g->d_tmoff;
-      p.smask = g->d_smask;
+      p.g.tmoff = g->sup_masks->tmoff;
+      p.smask = g->sup_masks->smask;
     }
-    // the triangle count streams the short lists from their task-major copies (gm_host.h d_colk; tune[6] & GM_T6_NO_KEYSTREAM: from their rows);
+    // the triangle count streams the short lists from their task-major copies (gm_host.h TaskLists::colk; tune[6] & GM_T6_NO_KEYSTREAM: from their rows);
     // the edge supports need the entries of the streamed keys in col[] itself
     if (pl.use_kst && pl.support) {  // ... with the entries the supports need beside them (the second set when the stream was built without)
-      p.g.kst = g->d_kst2 ? g->d_kst2 : g->d_kst;
-      p.g.kst_rp = g->d_kst_rp;
-      p.g.kst_et = g->d_kst_et;
-      p.g.trp = g->d_trpl;
-      p.g.tdesc = g->d_tdescl2 ? g->d_tdescl2 : g->d_tdescl;
-      p.g.tedge = g->d_tedgel;
+      const KeyEntries &k2 = *g->kst_entries;
+      p.g.kst = k2.kst2 ? k2.kst2 : ks.kst;
+      p.g.kst_rp = ks.rp;
+      p.g.kst_et = k2.kst_et ? k2.kst_et : ks.kst_et;
+      p.g.trp = ks.trpl;
+      p.g.tdesc = k2.tdescl2 ? k2.tdescl2 : ks.tdescl;
+      p.g.tedge = k2.tedgel ? k2.tedgel : ks.tedgel;
     } else if (pl.use_kst) {  // short lists as one tagged key stream, the longer ones as tasks
-      p.g.kst = g->d_kst;
-      p.g.kst_rp = g->d_kst_rp;
-      p.g.trp = g->d_trpl;
-      p.g.tdesc = g->d_tdescl;
-    } else if (!pl.support && g->d_colk && g->d_tdesck && !(la->tune[6] & GM_T6_NO_KEYSTREAM)) {
-      p.g.col = g->d_colk;
-      p.g.tdesc = g->d_tdesck;
+      p.g.kst = ks.kst;
+      p.g.kst_rp = ks.rp;
+      p.g.trp = ks.trpl;
+      p.g.tdesc = ks.tdescl;
+    } else if (!pl.support && tl.colk && tl.tdesck && !(la->tune[6] & GM_T6_NO_KEYSTREAM)) {
+      p.g.col = tl.colk;
+      p.g.tdesc = tl.tdesck;
     }
   }
   if (int rc = take_share(r, pl.tab, p)) return rc;
@@ -487,7 +488,7 @@ static int prepare_scratch(PatternRun &r, int k) {
     {  // a slot per workgroup: with very long rows fewer workgroups, so that the arena stays within half of the free memory
       size_t free_b = 0, total_b = 0;
       (void)hipMemGetInfo(&free_b, &total_b);
-      const unsigned long long budget = (unsigned long long)(free_b + g->scratch_bytes) / 2ull;
+      const unsigned long long budget = (unsigned long long)(free_b + g->scratch.bytes) / 2ull;
       const unsigned long long fit = budget / std::max<unsigned long long>(slot_words * sizeof(unsigned), 1ull);
       if (fit == 0) {
         g_last_error = "k-clique: the bit-matrix of the longest DAG row (" + std::to_string(g->max_deg) + " entries) does not fit the device memory";
@@ -497,7 +498,7 @@ static int prepare_scratch(PatternRun &r, int k) {
     }
     const size_t need = (size_t)slot_words * sizeof(unsigned) * (size_t)r.grid;
     if (int rc = ensure_scratch(g, need)) return rc;
-    p.scratch = g->d_scratch;
+    p.scratch = g->scratch.p;
     p.scratch_words = slot_words;
   }
   // (a side stream is a hardware queue: ~17 ms each to create -- GM_SETUP_TRACE, the first 4-clique call spent 35 ms here for a variant that is off)
@@ -544,6 +545,9 @@ static int debug_chunks_dump(PatternRun &run) {
   std::vector<ChunkRec> recs(tab->n);
   HIP_TRY(hipMemcpy(recs.data(), tab->d, sizeof(ChunkRec) * tab->n, hipMemcpyDeviceToHost));
   if (int rcv = table_host_views(g, tab)) return rcv;
+  const std::vector<int> *h_rp_p = nullptr;
+  if (int rcv = host_rp(g, &h_rp_p)) return rcv;
+  const std::vector<int> &h_rp = *h_rp_p;
   std::vector<size_t> idx(tab->n);
   for (size_t i = 0; i < tab->n; ++i) idx[i] = i;
   std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return ticks[a] > ticks[b]; });
@@ -558,9 +562,9 @@ static int debug_chunks_dump(PatternRun &run) {
       for (size_t pos = 0; pos < tab->n; ++pos) {
         const size_t cid = p.order ? (size_t)(p.order == tab->d_order[0] ? tab->order[0][pos] : tab->order[1][pos]) : pos;
         const ChunkRec &r = recs[cid];
-        const bool whole = r.e_begin == g->h_rp[r.u_begin] && r.e_end == g->h_rp[r.u_end];
+        const bool whole = r.e_begin == h_rp[r.u_begin] && r.e_end == h_rp[r.u_end];
         fprintf(f, "%zu,%zu,%d,%d,%d,%d,%d,%d,%llu,%.1f\n", pos, cid, r.u_end - r.u_begin, r.e_end - r.e_begin,
-                g->h_rp[r.u_begin + 1] - g->h_rp[r.u_begin], (int)whole, r.part, r.nparts, tab->cost[cid], ticks[pos] / 100.0);
+                h_rp[r.u_begin + 1] - h_rp[r.u_begin], (int)whole, r.part, r.nparts, tab->cost[cid], ticks[pos] / 100.0);
       }
       fclose(f);
     }
@@ -571,7 +575,7 @@ static int debug_chunks_dump(PatternRun &run) {
     const size_t cid = p.order ? (size_t)(p.order == tab->d_order[0] ? tab->order[0][pos] : tab->order[1][pos]) : pos;
     const ChunkRec &r = recs[cid];
     fprintf(stderr, "[chunks] #%zu pos %zu: %.1f us  rows [%d,%d) entries [%d,%d) n=%d part %d/%d rowlen %d\n", k, pos, ticks[pos] / 100.0,
-            r.u_begin, r.u_end, r.e_begin, r.e_end, r.e_end - r.e_begin, r.part, r.nparts, g->h_rp[r.u_begin + 1] - g->h_rp[r.u_begin]);
+            r.u_begin, r.u_end, r.e_begin, r.e_end, r.e_end - r.e_begin, r.part, r.nparts, h_rp[r.u_begin + 1] - h_rp[r.u_begin]);
   }
   return GM_OK;
 }
@@ -599,7 +603,7 @@ static int launch_clique4_rounds(PatternRun &r) {
     }
     r.my_edges += plan->wide_edges;
   }
-  HIP_TRY(hipMemsetAsync(g->d_wide_queue, 0, 65536, stream));
+  HIP_TRY(hipMemsetAsync(g->arena.queue, 0, 65536, stream));
   setup_trace("launch: clique prologue");
   const bool prof = gm_sweep_env("GM_WIDE_PROFILE") != nullptr;
   int qword = 0;
@@ -612,16 +616,16 @@ static int launch_clique4_rounds(PatternRun &r) {
     if (blocked) {
       CGatherBParams cb;
       memset(&cb, 0, sizeof cb);
-      cb.mat = g->d_wide_mat;
-      cb.tri = g->d_cg_tri;
-      cb.rowbase = g->d_cg_rowbase;
-      cb.blk = g->d_cg_blk;
+      cb.mat = g->arena.mat;
+      cb.tri = g->core_blocks->tri;
+      cb.rowbase = g->core_blocks->rowbase;
+      cb.blk = g->core_blocks->blk;
       cb.tab = rd.d_gtab;
       cb.units = rd.d_gunits;
       cb.items = rd.d_gitems;
-      cb.delta = g->core_base & 31;
+      cb.delta = g->core->base & 31;
       cb.count = (int)rd.n_gitems;
-      cb.queue = g->d_wide_queue + qword++;
+      cb.queue = g->arena.queue + qword++;
       const int ggrid = grid_for(cb.count, g->cu_count, cgatherb_per_cu());
       HIP_TRY(launch_cgatherb(cb, ggrid, stream));
       setup_trace("launch: core gather (blocked)");
@@ -632,14 +636,14 @@ static int launch_clique4_rounds(PatternRun &r) {
       cg.col = g->d_col;
       cg.verts = plan->d_verts;
       cg.base = plan->d_slot_base;
-      cg.mat = g->d_wide_mat;
-      cg.core = g->d_core;
-      cg.core_base = g->core_base;
-      cg.core_words = (g->core_h + 31) / 32;
-      cg.core_bytes = (unsigned long long)g->core_h * (unsigned long long)cg.core_words * 4ull;
+      cg.mat = g->arena.mat;
+      cg.core = g->core->bits;
+      cg.core_base = g->core->base;
+      cg.core_words = (g->core->h + 31) / 32;
+      cg.core_bytes = (unsigned long long)g->core->h * (unsigned long long)cg.core_words * 4ull;
       cg.first_slot = (int)rd.w0;
       cg.count = (int)(rd.w1 - rd.w0);
-      cg.queue = g->d_wide_queue + qword++;
+      cg.queue = g->arena.queue + qword++;
       const int ggrid = grid_for(cg.count, g->cu_count, cgather_per_cu());
       // (GM_CLIQUE_SIDE_STREAM=1: on a side stream beside the streamed build and the counts of the narrow vertices -- they touch other rows
       // of the arena.  Measured and not taken: the gathers want all 32 waves of a CU -- 4 / 3 / 2 / 1 workgroups per CU beside the streamed
@@ -668,8 +672,8 @@ static int launch_clique4_rounds(PatternRun &r) {
       pw.count = (int)std::min(rd.host_tab.n, rd.host_tab.n_with_cost);
       pw.trp = rd.d_trp;
       pw.tasks = rd.d_tasks;
-      pw.queue = g->d_wide_queue + qword++;
-      pw.mat = g->d_wide_mat;
+      pw.queue = g->arena.queue + qword++;
+      pw.mat = g->arena.mat;
       pw.flags = p.flags;
       const int bgrid = grid_for(pw.count, g->cu_count, cbuild_per_cu(plan->stage));
       if (pw.count > 0) HIP_TRY(launch_cbuild(pw, plan->stage, bgrid, stream));
@@ -686,8 +690,8 @@ static int launch_clique4_rounds(PatternRun &r) {
       cs.step = (int)plan->n_step;
       cs.count = (int)rd.n_count;
       cs.base = rd.d_base;
-      cs.mat = g->d_wide_mat;
-      cs.queue = g->d_wide_queue + qword++;
+      cs.mat = g->arena.mat;
+      cs.queue = g->arena.queue + qword++;
       cs.counters = g->d_counters;
       cs.topo = plan->topo ? 1 : 0;
       const int sgrid = grid_for(cs.count, g->cu_count, 8);
@@ -703,11 +707,11 @@ static int launch_clique4_rounds(PatternRun &r) {
       c.rp = g->d_rp;
       c.verts = plan->d_verts;
       c.base = plan->d_slot_base;
-      c.mat = g->d_wide_mat;
+      c.mat = g->arena.mat;
       c.slots = plan->d_mcls_slots + rd.mcls_begin[cls];
       c.qrec = plan->d_mcls_rec + rd.mcls_begin[cls];
       c.count = (int)(rd.mcls_begin[cls + 1] - rd.mcls_begin[cls]);
-      c.queue = g->d_wide_queue + qword++;
+      c.queue = g->arena.queue + qword++;
       c.counters = g->d_counters;
       c.topo = plan->topo ? 1 : 0;
       if (c.count == 0) continue;
@@ -722,7 +726,7 @@ static int launch_clique4_rounds(PatternRun &r) {
     size_t nt = 0, nh = 0;
     for (const auto &rd : plan->rounds) { nt += rd.n_tasks; nh += rd.host_tab.n; }
     fprintf(stderr, "[clique plan] %zu wide vertices, %lld narrow chunks, %zu tasks in %zu host chunks, %zu round(s), arena %.1f MB, stage %d, %s numbering\n",
-            plan->verts.size(), plan->n_count, nt, nh, plan->rounds.size(), g->wide_mat_bytes / 1048576.0, plan->stage, plan->topo ? "topological" : "arbitrary");
+            plan->verts.size(), plan->n_count, nt, nh, plan->rounds.size(), g->arena.mat_bytes / 1048576.0, plan->stage, plan->topo ? "topological" : "arbitrary");
   }
   return GM_OK;
 }
@@ -771,7 +775,7 @@ static int launch_classes(PatternRun &r) {
     const int per_cu_w = giant ? giant_per_cu() : hrow ? hrow_per_cu(cls) : (int)std::max<size_t>(1, (160 * 1024) / mine_wide_lds_bytes(cls));
     const int wgrid = grid_for(q.count, g->cu_count, per_cu_w);
     if (giant) {
-      q.scratch = g->d_scratch;  // (allocated before the timer started)
+      q.scratch = g->scratch.p;  // (allocated before the timer started)
       q.scratch_words = giant_scratch_words(g->max_deg);
     }
     hipStream_t ws;
@@ -792,7 +796,7 @@ static int launch_task_tables(PatternRun &r, int kind) {
   hipStream_t stream = r.ctx.stream;
   const PatternPlan &pl = r.pl;
   const MineParams &p = r.p;
-  const WtriParams wp = {g->d_w5sup, g->d_w5ed, g->d_w5deg};
+  const WtriParams wp = {g->w5.sup, g->w5.ed, g->w5deg->deg};
   auto launch = [&](const MineParams &q, int stage, long long dequeues) {
     const int grid = grid_for(dequeues, g->cu_count, kind == TK_WTRI ? wtri_per_cu(stage) : kind == TK_SUPPORT ? sup_per_cu(stage) : tch_per_cu(stage));
     return kind == TK_WTRI ? launch_wtri(q, wp, stage, grid, stream) : kind == TK_SUPPORT ? launch_sup(q, stage, grid, stream) : launch_tch(q, stage, grid, stream);
@@ -847,18 +851,18 @@ static int launch_tc(PatternRun &r) {
   if (pl.tc_core) {  // the out-edges of the hub corner: one masked bit-matrix product; a rank takes every world-th block
     CoreTcParams cp;
     memset(&cp, 0, sizeof cp);
-    cp.core = g->d_core;
-    cp.row_words = (g->core_h + 31) / 32;
+    cp.core = g->core->bits;
+    cp.row_words = (g->core->h + 31) / 32;
     // (a stream built with a choice of block pairs, tc_pairs_setup: the region they lie in and the list of their pieces)
-    const bool pairs = pl.use_kst && g->tc_pair_region > 0;
-    const int from = pairs ? g->tc_pair_from : pl.corner_from;
-    cp.row0 = from - g->core_base;
+    const bool pairs = pl.use_kst && g->kst->pair_region > 0;
+    const int from = pairs ? g->kst->pair_from : pl.corner_from;
+    cp.row0 = from - g->core->base;
     cp.word0 = cp.row0 >> 5;
     cp.h = g->nv - from;
     cp.ntasks = 0;
     if (pairs) {
-      cp.tasks = g->d_tc_pair_tasks;
-      cp.n_list = g->n_tc_pair_tasks;
+      cp.tasks = g->kst->pair_tasks;
+      cp.n_list = g->kst->n_pair_tasks;
     }
     if (int rc = launch_corner(r, cp, false)) return rc;
     // (gm_stats.tasks: a table's task edges are its rows' entries -- the corner's rows are chunks of the table like any other)
@@ -872,35 +876,35 @@ static int launch_supports(PatternRun &r) {
   hipStream_t stream = r.ctx.stream;
   const PatternPlan &pl = r.pl;
   const int world = r.ctx.world, rank = r.ctx.rank;
-  unsigned *sup = pl.sup_part ? r.rq.sup_out : g->d_sup;
+  unsigned *sup = pl.sup_part ? r.rq.sup_out : g->diamond.sup;
   HIP_TRY(hipMemsetAsync(sup, 0, sizeof(unsigned) * (size_t)(pl.sup_part ? diamond_support_entries(g->ne, world) : g->ne), stream));
   r.p.scratch = sup;
   if (int rc = launch_task_tables(r, TK_SUPPORT)) return rc;
-  if (pl.tct_long && g->n_long_rows > 0) {
+  if (pl.tct_long && g->long_rows->n > 0) {
     SupLongParams sl;
     memset(&sl, 0, sizeof sl);
     sl.rp = g->d_rp;
     sl.col = g->d_col;
-    sl.rows = g->d_long_rows;
-    sl.prefix = g->d_long_prefix;
-    sl.nrows = g->n_long_rows;
-    sl.total = g->long_edges;
+    sl.rows = g->long_rows->rows;
+    sl.prefix = g->long_rows->prefix;
+    sl.nrows = g->long_rows->n;
+    sl.total = g->long_rows->edges;
     sl.sup = sup;
     sl.topo = tails_trimmed(g) ? 1 : 0;
     sl.rank = rank;
     sl.world = world;
     HIP_TRY(launch_sup_long(sl, g->cu_count, stream));
-    r.my_edges += (unsigned long long)((g->long_edges - rank + world - 1) / world);
+    r.my_edges += (unsigned long long)((g->long_rows->edges - rank + world - 1) / world);
   }
   if (pl.sup_core) {  // the supports of the hub corner's edges: (A A)_ij on the matrix cores (gm_ctc.hip); a rank takes every world-th block
     CoreTcParams cp;
     memset(&cp, 0, sizeof cp);
-    cp.core = g->d_csym;
-    cp.h = g->tl_core_h;
+    cp.core = g->sup_corner->csym;
+    cp.h = g->tasklists->core_h;
     cp.row_words = cp.h / 32;
     cp.rp = g->d_rp;
     cp.base = pl.corner_from;
-    cp.first_pos = g->d_cfirst;
+    cp.first_pos = g->sup_corner->cfirst;
     cp.sup = sup;
     if (int rc = launch_corner(r, cp, true)) return rc;
   }
@@ -911,48 +915,48 @@ static int launch_supports(PatternRun &r) {
     sc.ne = g->ne;
     sc.lmin = sup_mask_min_tail(g);
     sc.rp = g->d_rp;
-    sc.emoff = g->d_emoff;
-    sc.smask = g->d_smask;
+    sc.emoff = g->sup_masks->emoff;
+    sc.smask = g->sup_masks->smask;
     sc.sup = sup;
-    sc.far_rows = g->d_sup_far_rows;
-    sc.n_far_rows = g->n_sup_far_rows;
+    sc.far_rows = g->sup_masks->far_rows;
+    sc.n_far_rows = g->sup_masks->n_far_rows;
     HIP_TRY(launch_sup_cols(sc, g->cu_count, stream));
   }
   if (!pl.sup_part) HIP_TRY(launch_sup_pairs(sup, 0, g->ne, g->d_counters, g->cu_count, stream));
   return GM_OK;
 }
 
-// The 5-vertex closed forms on the DAG (gm_wtri.hip; gm_sgl5_raw filled g->d_w5sup and says what it wants, rq.wtri_*): the per-entry sums and the
+// The 5-vertex closed forms on the DAG (gm_wtri.hip; gm_sgl5_raw filled g->w5.sup and says what it wants, rq.wtri_*): the per-entry sums and the
 // scatter into 2 T_v, the support-weighted second pass over the triangles (A, B -> counters[0], [1]) -- the task tables, then the out-edges
 // no task list holds: the rows beyond the stage or the rows of the hub corner -- and the per-vertex sums.  All inside the timed region.
 static int launch_weighted(PatternRun &r) {
   gm_graph *g = r.ctx.g;
   hipStream_t stream = r.ctx.stream;
   const PatternPlan &pl = r.pl;
-  HIP_TRY(hipMemsetAsync(g->d_w5out, 0, 64, stream));
-  HIP_TRY(hipMemsetAsync(g->d_w5tv2, 0, sizeof(unsigned long long) * (size_t)std::max(g->nv, 1), stream));
+  HIP_TRY(hipMemsetAsync(g->w5.out, 0, 64, stream));
+  HIP_TRY(hipMemsetAsync(g->w5.tv2, 0, sizeof(unsigned long long) * (size_t)std::max(g->nv, 1), stream));
   WtriEntryParams ep;
   memset(&ep, 0, sizeof ep);
-  ep.nv = g->nv; ep.ne = g->ne; ep.rp = g->d_rp; ep.col = g->d_col; ep.sup = g->d_w5sup; ep.deg = g->d_w5deg;
-  ep.ed = g->d_w5ed; ep.tv2 = g->d_w5tv2; ep.out = g->d_w5out;
+  ep.nv = g->nv; ep.ne = g->ne; ep.rp = g->d_rp; ep.col = g->d_col; ep.sup = g->w5.sup; ep.deg = g->w5deg->deg;
+  ep.ed = g->w5.ed; ep.tv2 = g->w5.tv2; ep.out = g->w5.out;
   HIP_TRY(launch_wtri_entries(ep, g->cu_count, stream));
   if (r.rq.wtri_tri) {
     if (int rc = launch_task_tables(r, TK_WTRI)) return rc;
-    const WtriParams wp = {g->d_w5sup, g->d_w5ed, g->d_w5deg};
+    const WtriParams wp = {g->w5.sup, g->w5.ed, g->w5deg->deg};
     WtriEdgeParams we;
     memset(&we, 0, sizeof we);
     we.rp = g->d_rp; we.col = g->d_col; we.nv = g->nv; we.ne = g->ne;
     we.topo = tails_trimmed(g) ? 1 : 0;
     we.counters = g->d_counters;
-    if (pl.tct_long && g->n_long_rows > 0) {
-      we.rows = g->d_long_rows; we.prefix = g->d_long_prefix; we.nrows = g->n_long_rows; we.total = g->long_edges;
+    if (pl.tct_long && g->long_rows->n > 0) {
+      we.rows = g->long_rows->rows; we.prefix = g->long_rows->prefix; we.nrows = g->long_rows->n; we.total = g->long_rows->edges;
       HIP_TRY(launch_wtri_edges(we, wp, g->cu_count, stream));
     } else if (pl.corner_from < g->nv) {
       we.v0 = pl.corner_from; we.total = g->ne;
       HIP_TRY(launch_wtri_edges(we, wp, g->cu_count, stream));
     }
   }
-  if (r.rq.wtri_vert) HIP_TRY(launch_wtri_vertices(g->nv, g->d_w5tv2, g->d_w5deg, g->d_w5out, g->cu_count, stream));
+  if (r.rq.wtri_vert) HIP_TRY(launch_wtri_vertices(g->nv, g->w5.tv2, g->w5deg->deg, g->w5.out, g->cu_count, stream));
   return GM_OK;
 }
 
@@ -1071,12 +1075,12 @@ __global__ __launch_bounds__(256) void sum_sq_deg_kernel(int nv, const int *__re
 
 // sum d^2 / ne of a handle's rows = the mean length of the row an entry sits in (cached)
 int ensure_mean_sq_deg(gm_graph *self) {
-  if (self->mean_sq_deg < 0) {
+  return self->facts.mean_sq_deg.ensure(self->mu, [&](double &mean) {
     unsigned long long s2 = 0;
     if (int rc = reduce_to_u64(self, self->nv > 0, "sum_sq_deg_kernel", &s2, [&](unsigned long long *d_s) { hipLaunchKernelGGL(sum_sq_deg_kernel, rows_grid(self), dim3(256), 0, 0, self->nv, self->d_rp, d_s); })) return rc;
-    self->mean_sq_deg = self->ne > 0 ? (double)s2 / (double)self->ne : 0.0;
-  }
-  return GM_OK;
+    mean = self->ne > 0 ? (double)s2 / (double)self->ne : 0.0;
+    return kOnceBuilt;
+  });
 }
 
 // Triangles per DAG entry, ESTIMATED: every stride-th entry (u -> v), |N+(u) ^ N+(v)| by a merge of the two sorted rows (at most 512 steps:
@@ -1108,7 +1112,7 @@ __global__ __launch_bounds__(256) void tri_sample_kernel(int nv, long long ne, c
 }
 
 int ensure_tri_per_edge(gm_graph *self) {
-  if (self->tri_per_edge < 0) {
+  return self->facts.tri_per_edge.ensure(self->mu, [&](double &tri) {
     const int nsamples = (int)std::min<long long>(1 << 16, std::max<long long>(self->ne, 1));
     const long long stride = std::max<long long>(1, self->ne / nsamples);
     unsigned long long s = 0;
@@ -1116,9 +1120,9 @@ int ensure_tri_per_edge(gm_graph *self) {
           hipLaunchKernelGGL(tri_sample_kernel, dim3((unsigned)((nsamples + 255) / 256)), dim3(256), 0, 0, self->nv, (long long)self->ne, self->d_rp, self->d_col, stride,
                              nsamples, d_s);
         })) return rc;
-    self->tri_per_edge = (double)s / (double)nsamples;
-  }
-  return GM_OK;
+    tri = (double)s / (double)nsamples;
+    return kOnceBuilt;
+  });
 }
 
 // Heavy chunks of the task-list kernels (a hub hosts 10^5 in-edges) are cut into PARTS that share the chunk's batches -- and every part
@@ -1130,7 +1134,7 @@ int ensure_tri_per_edge(gm_graph *self) {
 unsigned long long task_part_cap(gm_graph *g, int world) {
   if (const char *e = gm_sweep_env("GM_TCT_PART_KKEYS")) return (unsigned long long)std::max(4, atoi(e)) << 10;  // (sweeps)
   double keys = 0.0;
-  if (ensure_mean_sq_deg(g) == GM_OK) keys = (double)g->ne * g->mean_sq_deg * 0.5;
+  if (ensure_mean_sq_deg(g) == GM_OK) keys = (double)g->ne * *g->facts.mean_sq_deg * 0.5;
   const double cap = keys / (3000.0 * (double)std::max(world, 1));
   return (unsigned long long)std::min(std::max(cap, (double)(128 << 10)), (double)(4 << 20));
 }
@@ -1148,8 +1152,8 @@ int topo_view(const gm_graph *dag, const gm_launch *la, gm_graph **run_on) {
   if (rc) return rc;
   double min_row = (double)kTopoMinMeanRow;
   if (const char *e = gm_opt("GM_TOPO_MIN_ROW")) min_row = atof(e);
-  if (gm_sweep_env("GM_TABLE_INFO")) fprintf(stderr, "[topo view] sum d+^2 / |E+| = %.1f (switch at %.1f)\n", self->mean_sq_deg, min_row);
-  if (self->mean_sq_deg < min_row) return GM_OK;  // short lists: as numbered
+  if (gm_sweep_env("GM_TABLE_INFO")) fprintf(stderr, "[topo view] sum d+^2 / |E+| = %.1f (switch at %.1f)\n", *self->facts.mean_sq_deg, min_row);
+  if (*self->facts.mean_sq_deg < min_row) return GM_OK;  // short lists: as numbered
   return get_relabeled(self, 2, run_on);
 }
 
@@ -1170,12 +1174,12 @@ extern "C" int gm_tc_core_info(const gm_graph *dag, int64_t info[4]) {
   // (a symmetric handle: the oriented copy its formula 3-motif counts the triangles of)
   const int rc = topo_view(dag->dag_cache ? dag->dag_cache : dag, nullptr, &run_on);
   if (rc) return rc;
-  const bool on = run_on->kst_skip_from < run_on->nv;
-  const long long nJ = on ? (run_on->tc_core_h + 63) >> 6 : 0;
-  info[0] = on ? run_on->tc_core_h : 0;           // vertices of the corner (0: every edge is a task of the key stream)
-  info[1] = on ? run_on->tc_core_edges : 0;       // DAG entries inside it
+  const bool on = run_on->kst->skip_from < run_on->nv;
+  const long long nJ = on ? (run_on->kst->core_h + 63) >> 6 : 0;
+  info[0] = on ? run_on->kst->core_h : 0;           // vertices of the corner (0: every edge is a task of the key stream)
+  info[1] = on ? run_on->kst->core_edges : 0;       // DAG entries inside it
   info[2] = nJ * (nJ + 1) / 2;                    // 64 x 64 blocks of the masked product
-  info[3] = on ? run_on->core_h : 0;              // vertices of the core bitmap the corner is a part of
+  info[3] = on ? run_on->core->h : 0;              // vertices of the core bitmap the corner is a part of
   return GM_OK;
 }
 
@@ -1187,8 +1191,8 @@ extern "C" int gm_tc_pairs_info(const gm_graph *dag, int64_t info[6]) {
   gm_graph *run_on = nullptr;
   const int rc = topo_view(dag->dag_cache ? dag->dag_cache : dag, nullptr, &run_on);
   if (rc) return rc;
-  const bool on = run_on->kst_skip_from < run_on->nv && run_on->tc_pair_region > 0;
-  for (int i = 0; i < 6; ++i) info[i] = on ? run_on->tc_pair_info[i] : 0;
+  const bool on = run_on->kst->skip_from < run_on->nv && run_on->kst->pair_region > 0;
+  for (int i = 0; i < 6; ++i) info[i] = on ? run_on->kst->pair_info[i] : 0;
   return GM_OK;
 }
 
@@ -1374,17 +1378,15 @@ extern "C" int gm_motif_formula(const gm_graph *sym, int k, const gm_launch *la,
   if (ncounts < 2) return GM_ERR_INVALID;
   gm_graph *g = const_cast<gm_graph *>(sym);
   if (const int rc_dag = ensure_dag_cache(g)) return rc_dag;  // (the oriented copy, cached on the handle)
-  if (!g->sum_c2_valid) {  // sum_v C(d(v),2): one reduction kernel over the offsets
-    unsigned long long s2 = 0;
-    if (int rc = reduce_to_u64(g, true, "sum_c2_kernel", &s2, [&](unsigned long long *acc) {
+  // sum_v C(d(v),2): one reduction kernel over the offsets
+  if (const int rc_s = g->facts.sum_c2.ensure(g->mu, [&](unsigned long long &s2) {
+        return reduce_to_u64(g, true, "sum_c2_kernel", &s2, [&](unsigned long long *acc) {
           if (g->d_rp64) hipLaunchKernelGGL((sum_c2_kernel<long long>), rows_grid(g), dim3(256), 0, 0, g->nv, (const long long *)g->d_rp64, acc);
           else hipLaunchKernelGGL((sum_c2_kernel<int>), rows_grid(g), dim3(256), 0, 0, g->nv, (const int *)g->d_rp, acc);
-        })) return rc;
-    g->sum_c2 = s2;
-    g->sum_c2_valid = true;
-  }
+        });
+      })) return rc_s;
   const int rank = la ? la->rank : 0;
-  const int rc = run_tc(g->dag_cache, la, counts, ncounts, st, FIN_MOTIF3_FORMULA, rank == 0 ? g->sum_c2 : 0ull);
+  const int rc = run_tc(g->dag_cache, la, counts, ncounts, st, FIN_MOTIF3_FORMULA, rank == 0 ? *g->facts.sum_c2 : 0ull);
   record_ran_on(g, g->dag_cache);  // (whatever rc; run_tc has recorded the handle the oriented copy ran on)
   return rc;
 }
@@ -1419,7 +1421,7 @@ extern "C" int gm_clique4_gather_info(const gm_graph *dag, int64_t info[4]) {
       info[1] += (int64_t)rd.gather_table_bytes;   // bytes they read by construction: 16 B record + 4 B per row + their table dwords
       info[2] += (int64_t)rd.n_gitems;             // work items (each loads one block image of <= 64 KB unless it shares it with its predecessor)
     }
-    info[3] = g->n_cg_blocks;
+    info[3] = g->core_blocks->n;
     break;
   }
   return GM_OK;

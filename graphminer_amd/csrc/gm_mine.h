@@ -409,7 +409,7 @@ constexpr int kCgbWords = 16384;   // LDS words of a block image (64 KB: two wor
 constexpr int kCgbMaxRows = 1024;  // rows of a block (their LDS offsets: 4 KB)
 struct CGatherBParams {
   unsigned *mat;          // matrix arena of the round
-  const unsigned *tri;    // the block images one after the other: of every core row the words from its diagonal word on (gm_host.h d_cg_tri)
+  const unsigned *tri;    // the block images one after the other: of every core row the words from its diagonal word on (gm_host.h CoreBlocks)
   const int *rowbase;     // per core row: (word offset of the row inside its block's image) - (index of its first stored word)
   const int4 *blk;        // per block: {first core row, rows, image offset in tri (words, a multiple of 4), image words}
   const unsigned *tab;    // column tables: per vertex, dword 64 T + l = q(128 T + l) | q(128 T + 64 + l) << 16, q = id - (core_base & ~31)
@@ -433,7 +433,7 @@ constexpr int kCtcWaves = 4;
 constexpr int kCtcMaxH = 32768;        // f32 accumulators stay exact; the core bitmap (kCoreHDefault) is no larger
 constexpr int kTcCoreHDefault = 32768; // the largest corner considered (tc_core_size, gm_tables.hip: by density); GM_TC_CORE_H overrides
 struct CoreTcParams {
-  const unsigned *core;      // the core bitmap (gm_host.h d_core): row_words words per row
+  const unsigned *core;      // the core bitmap (gm_host.h HubCore): row_words words per row
   int row_words;
   int row0, word0;           // the corner: first row of the bitmap, first word of its rows
   int h;                     // vertices of the corner

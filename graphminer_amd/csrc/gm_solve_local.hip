@@ -9,14 +9,13 @@ static int ensure_local_buffers(gm_graph *g, bool peel, bool truss) {
   std::lock_guard<std::mutex> lk(g->mu);
   HIP_TRY(hipSetDevice(g->device));
   const size_t ne = (size_t)std::max<long long>(g->ne, 1);
-  if (!g->d_lent) HIP_TRY(g->d_lent.alloc(sizeof(unsigned) * ne));
+  if (!g->local.ent) HIP_TRY(g->local.ent.alloc(sizeof(unsigned) * ne));
   if (peel) {
-    if (!g->d_lrev) HIP_TRY(g->d_lrev.alloc(sizeof(int) * ne));
-    if (!g->d_lmark) HIP_TRY(g->d_lmark.alloc(ne));
-    if (!g->d_lfront) HIP_TRY(g->d_lfront.alloc(sizeof(int) * (ne / 2 + 1)));
-    if (!g->d_lcnt) HIP_TRY(g->d_lcnt.alloc(64));
+    if (!g->local.mark) HIP_TRY(g->local.mark.alloc(ne));
+    if (!g->local.front) HIP_TRY(g->local.front.alloc(sizeof(int) * (ne / 2 + 1)));
+    if (!g->local.cnt) HIP_TRY(g->local.cnt.alloc(64));
   }
-  if (truss && !g->d_ltruss) HIP_TRY(g->d_ltruss.alloc(sizeof(unsigned) * ne));
+  if (truss && !g->local.truss) HIP_TRY(g->local.truss.alloc(sizeof(unsigned) * ne));
   return GM_OK;
 }
 
@@ -28,7 +27,7 @@ static int local_refusals(const gm_graph *sym, const gm_launch *la) {
   return GM_OK;
 }
 
-// The supports of every entry of the oriented copy -- one rank's PAT_SUPPORT_PART into run_on->d_lsup, every path of the triangle pass --
+// The supports of every entry of the oriented copy -- one rank's PAT_SUPPORT_PART into run_on->local.sup, every path of the triangle pass --
 // and their way back: `c` is the open launch on the SYMMETRIC handle, the mapping kernel writes `out` (caller's entry order) and adds the
 // sum of the supports to its counters[0].
 static int local_supports(gm_graph *g, const gm_launch *l2, SubLaunches &sub, gm_graph **run_on_out) {
@@ -36,10 +35,10 @@ static int local_supports(gm_graph *g, const gm_launch *l2, SubLaunches &sub, gm
   if (int rc = diamond_run_on(g, l2, &run_on)) return rc;
   {
     std::lock_guard<std::mutex> lk(run_on->mu);
-    if (!run_on->d_lsup) HIP_TRY(run_on->d_lsup.alloc(sizeof(unsigned) * (size_t)diamond_support_entries(run_on->ne, 1)));
+    if (!run_on->local.sup) HIP_TRY(run_on->local.sup.alloc(sizeof(unsigned) * (size_t)diamond_support_entries(run_on->ne, 1)));
   }
   uint64_t dummy = 0;
-  if (int rc = sub.run([&](gm_stats *s) { return run_pattern({PAT_SUPPORT_PART, 3, -1, 0, run_on->d_lsup}, run_on, l2, &dummy, 1, s); })) return rc;
+  if (int rc = sub.run([&](gm_stats *s) { return run_pattern({PAT_SUPPORT_PART, 3, -1, 0, run_on->local.sup}, run_on, l2, &dummy, 1, s); })) return rc;
   *run_on_out = run_on;
   return GM_OK;
 }
@@ -51,8 +50,8 @@ static int local_map(LaunchCtx &c, gm_graph *run_on, unsigned *out) {
   memset(&mp, 0, sizeof mp);
   mp.nv = g->nv; mp.ne = g->ne; mp.rp = g->d_rp; mp.col = g->d_col;
   mp.newid = run_on != dag ? run_on->d_newid : nullptr;  // (the oriented copy keeps the symmetric graph's ids: one level of numbering)
-  mp.drp = run_on->d_rp; mp.dcol = run_on->d_col; mp.dsup = run_on->d_lsup;
-  mp.topo = run_on->topo_state == 1 ? 1 : 0;
+  mp.drp = run_on->d_rp; mp.dcol = run_on->d_col; mp.dsup = run_on->local.sup;
+  mp.topo = *run_on->facts.topological ? 1 : 0;
   mp.out = out; mp.sum = g->d_counters;
   HIP_TRY(launch_local_map(mp, g->cu_count, c.stream));
   return GM_OK;
@@ -78,7 +77,7 @@ extern "C" int gm_tc_local(const gm_graph *sym, const gm_launch *la, uint64_t *d
   if (int rc = local_supports(g, &l2, sub, &run_on)) return rc;
   HIP_TRY(hipMemsetAsync(g->d_counters, 0, kCounterBlockBytes, ctx.stream));  // (a first call oriented the graph since begin_launch)
   if (int rc = start_timer(ctx)) return rc;
-  unsigned *ent = d_entry_sup ? d_entry_sup : g->d_lent;
+  unsigned *ent = d_entry_sup ? d_entry_sup : g->local.ent;
   if (int rc = local_map(ctx, run_on, ent)) return rc;
   if (d_vertex_tri) HIP_TRY(launch_local_vertices(g->nv, g->d_rp, ent, (unsigned long long *)d_vertex_tri, g->cu_count, ctx.stream));
   if (int rc = sub.run([&](gm_stats *s) { return end_launch(ctx, FIN_COPY, 0, &sum, 1, s); })) return rc;
@@ -88,7 +87,7 @@ extern "C" int gm_tc_local(const gm_graph *sym, const gm_launch *la, uint64_t *d
 }
 
 // ---- local k-clique counts (gm_kcl_local.hip; DESIGN.md "Local k-clique counts") -----------------------------------------------------------
-// The k-cliques of every entry of the DAG (the oriented copy, or its topological copy: topo_view) into run_on->d_lkcl, then the way back
+// The k-cliques of every entry of the DAG (the oriented copy, or its topological copy: topo_view) into run_on->local.kcl, then the way back
 // the supports take: the 64-bit mapping kernel into the caller's entry order, the row sums / (k - 1) per vertex.
 constexpr size_t kKclScratchBudget = (size_t)1 << 30;  // bytes of scratch slots the wide kernel's grid is cut to (at least one slot)
 extern "C" int gm_clique_local(const gm_graph *sym, int k, const gm_launch *la, uint64_t *d_vertex_cnt, uint64_t *d_entry_cnt, uint64_t *total,
@@ -124,27 +123,27 @@ extern "C" int gm_clique_local(const gm_graph *sym, int k, const gm_launch *la, 
   {
     std::lock_guard<std::mutex> lk(run_on->mu);
     HIP_TRY(hipSetDevice(run_on->device));
-    if (!run_on->d_lkcl) HIP_TRY(run_on->d_lkcl.alloc(sizeof(unsigned long long) * 2 * dne));
-    if (!run_on->d_kcl_heavy) HIP_TRY(run_on->d_kcl_heavy.alloc(sizeof(int) * (heavy_cap + mid_cap)));
+    if (!run_on->local.kcl) HIP_TRY(run_on->local.kcl.alloc(sizeof(unsigned long long) * 2 * dne));
+    if (!run_on->local.kcl_heavy) HIP_TRY(run_on->local.kcl_heavy.alloc(sizeof(int) * (heavy_cap + mid_cap)));
     if (wide)
-      if (int rc = grow_dev(run_on->d_kcl_scratch, &run_on->kcl_scratch_bytes, slot_bytes * (size_t)grid_wide)) return rc;
+      if (int rc = grow_dev(run_on->local.kcl_scratch, &run_on->local.kcl_scratch_bytes, slot_bytes * (size_t)grid_wide)) return rc;
   }
   if (!d_entry_cnt) {
     std::lock_guard<std::mutex> lk(g->mu);
-    if (!g->d_lent64) HIP_TRY(g->d_lent64.alloc(sizeof(unsigned long long) * (size_t)g->ne));
+    if (!g->local.ent64) HIP_TRY(g->local.ent64.alloc(sizeof(unsigned long long) * (size_t)g->ne));
   }
   HIP_TRY(hipMemsetAsync(g->d_counters, 0, kCounterBlockBytes, ctx.stream));  // (a first call oriented the graph since begin_launch)
   if (int rc = start_timer(ctx)) return rc;
-  HIP_TRY(hipMemsetAsync(run_on->d_lkcl, 0, sizeof(unsigned long long) * 2 * dne, ctx.stream));
+  HIP_TRY(hipMemsetAsync(run_on->local.kcl, 0, sizeof(unsigned long long) * 2 * dne, ctx.stream));
   KclLocalParams kp;
   memset(&kp, 0, sizeof kp);
   kp.nv = run_on->nv; kp.ne = run_on->ne; kp.k = k; kp.max_deg = std::max(run_on->max_deg, 1);
-  kp.rp = run_on->d_rp; kp.col = run_on->d_col; kp.cnt = run_on->d_lkcl; kp.spk = run_on->d_lkcl + dne;
-  kp.heavy = run_on->d_kcl_heavy; kp.heavy_cap = (unsigned)heavy_cap;
-  kp.mid = run_on->d_kcl_heavy + heavy_cap; kp.mid_cap = (unsigned)mid_cap;
+  kp.rp = run_on->d_rp; kp.col = run_on->d_col; kp.cnt = run_on->local.kcl; kp.spk = run_on->local.kcl + dne;
+  kp.heavy = run_on->local.kcl_heavy; kp.heavy_cap = (unsigned)heavy_cap;
+  kp.mid = run_on->local.kcl_heavy + heavy_cap; kp.mid_cap = (unsigned)mid_cap;
   kp.queue = queue_word(g, QW_MAIN); kp.queue_wide = queue_word(g, QW_CLASS1); kp.n_heavy = queue_word(g, QW_CLASS2);
   kp.queue_mid = queue_word(g, QW_CLASS3); kp.n_mid = queue_word(g, QW_CORNER);
-  kp.scratch = run_on->d_kcl_scratch; kp.scratch_words = kcl_local_scratch_words(run_on->max_deg);
+  kp.scratch = run_on->local.kcl_scratch; kp.scratch_words = kcl_local_scratch_words(run_on->max_deg);
   kp.err = g->d_counters + 1;
   HIP_TRY(launch_kcl_local(kp, KCL_STAGE_ROOTS, grid, ctx.stream));
   if (k >= 5 && run_on->max_deg > kKclLocalSplitRow) HIP_TRY(launch_kcl_local(kp, KCL_STAGE_SPLIT, grid, ctx.stream));
@@ -154,9 +153,9 @@ extern "C" int gm_clique_local(const gm_graph *sym, int k, const gm_launch *la, 
   memset(&mp, 0, sizeof mp);
   mp.nv = g->nv; mp.ne = g->ne; mp.rp = g->d_rp; mp.col = g->d_col;
   mp.newid = run_on != dag ? run_on->d_newid : nullptr;
-  mp.drp = run_on->d_rp; mp.dcol = run_on->d_col; mp.dsup = run_on->d_lkcl;
-  mp.topo = run_on->topo_state == 1 ? 1 : 0;
-  unsigned long long *ent = d_entry_cnt ? (unsigned long long *)d_entry_cnt : g->d_lent64.get();
+  mp.drp = run_on->d_rp; mp.dcol = run_on->d_col; mp.dsup = run_on->local.kcl;
+  mp.topo = *run_on->facts.topological ? 1 : 0;
+  unsigned long long *ent = d_entry_cnt ? (unsigned long long *)d_entry_cnt : g->local.ent64.get();
   mp.out = ent; mp.sum = g->d_counters;
   HIP_TRY(launch_local_map(mp, g->cu_count, ctx.stream));
   if (d_vertex_cnt) HIP_TRY(launch_local_vertices(g->nv, g->d_rp, ent, (unsigned)(k - 1), (unsigned long long *)d_vertex_cnt, g->cu_count, ctx.stream));
@@ -195,17 +194,19 @@ static int run_truss(const gm_graph *sym, bool decompose, int k_in, const gm_lau
   if (int rc = local_supports(g, &l2, sub, &run_on)) return rc;
   if (int rc = start_timer(ctx)) return rc;
   hipStream_t stream = ctx.stream;
-  if (int rc = local_map(ctx, run_on, g->d_lent)) return rc;
-  if (!g->lrev_ready) {  // (once per handle)
-    HIP_TRY(launch_local_rev(g->nv, g->ne, g->d_rp, g->d_col, g->d_lrev, g->cu_count, stream));
-    g->lrev_ready = true;
-  }
-  HIP_TRY(launch_local_peel_init(g->ne, g->d_lrev, g->d_lmark, g->cu_count, stream));
+  if (int rc = local_map(ctx, run_on, g->local.ent)) return rc;
+  // (once per handle; filled on this call's stream, in front of its first reader: the header allows one call at a time per handle)
+  if (int rc = g->lrev.ensure(g->mu, [&](RevIndex &ri) {
+        HIP_TRY(ri.rev.alloc(sizeof(int) * (size_t)std::max<long long>(g->ne, 1)));
+        HIP_TRY(launch_local_rev(g->nv, g->ne, g->d_rp, g->d_col, ri.rev, g->cu_count, stream));
+        return kOnceBuilt;
+      })) return rc;
+  HIP_TRY(launch_local_peel_init(g->ne, g->lrev->rev, g->local.mark, g->cu_count, stream));
   LocalPeelParams pp;
   memset(&pp, 0, sizeof pp);
-  pp.nv = g->nv; pp.ne = g->ne; pp.rp = g->d_rp; pp.col = g->d_col; pp.rev = g->d_lrev;
-  pp.sup = g->d_lent; pp.mark = g->d_lmark; pp.front = g->d_lfront; pp.cnt = g->d_lcnt;
-  pp.truss = decompose ? g->d_ltruss : nullptr;
+  pp.nv = g->nv; pp.ne = g->ne; pp.rp = g->d_rp; pp.col = g->d_col; pp.rev = g->lrev->rev;
+  pp.sup = g->local.ent; pp.mark = g->local.mark; pp.front = g->local.front; pp.cnt = g->local.cnt;
+  pp.truss = decompose ? g->local.truss : nullptr;
   long long k = decompose ? 3 : k_in, kmax = 0;
   int rounds = 0;
   for (;;) {
@@ -213,9 +214,9 @@ static int run_truss(const gm_graph *sym, bool decompose, int k_in, const gm_lau
     for (;;) {  // the rounds of level k: threshold k - 2
       pp.thr = (unsigned)(k - 2);
       pp.level = (unsigned)(k - 1);
-      HIP_TRY(hipMemsetAsync(g->d_lcnt, 0, 8, stream));
+      HIP_TRY(hipMemsetAsync(g->local.cnt, 0, 8, stream));
       HIP_TRY(launch_local_mark(pp, g->cu_count, stream));
-      HIP_TRY(hipMemcpyAsync(word, g->d_lcnt, sizeof word, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(word, g->local.cnt, sizeof word, hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));
       ++rounds;
       if (word[0] == 0u) break;
@@ -270,24 +271,21 @@ extern "C" int gm_tc_list(const gm_graph *sym, const gm_launch *la, uint64_t fir
   memset(&lp, 0, sizeof lp);
   lp.nv = dag->nv; lp.ne = dag->ne; lp.rp = dag->d_rp; lp.col = dag->d_col;
   if (int rc = start_timer(ctx)) return rc;
-  if (!g->list_ready) {  // (once per handle)
-    if (dag->ne > 0) {
-      const size_t nb = (size_t)((dag->ne + GM_WAVE - 1) / GM_WAVE);
-      {
-        std::lock_guard<std::mutex> lk(g->mu);
-        if (!g->d_list_off) HIP_TRY(g->d_list_off.alloc(sizeof(unsigned long long) * (nb + 1)));
-      }
-      lp.off = g->d_list_off;
-      HIP_TRY(list_count_scan(lp, g->cu_count, ctx.stream));
-      HIP_TRY(hipMemcpyAsync(&g->list_total, g->d_list_off + nb, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx.stream));
-      HIP_TRY(hipStreamSynchronize(ctx.stream));
-    }
-    g->list_ready = true;
-  }
-  const uint64_t T = g->list_total;
+  if (int rc = g->list_off.ensure(g->mu, [&](ListOffsets &lo) {  // (once per handle)
+        if (dag->ne > 0) {
+          const size_t nb = (size_t)((dag->ne + GM_WAVE - 1) / GM_WAVE);
+          HIP_TRY(lo.off.alloc(sizeof(unsigned long long) * (nb + 1)));
+          lp.off = lo.off;
+          HIP_TRY(list_count_scan(lp, g->cu_count, ctx.stream));
+          HIP_TRY(hipMemcpyAsync(&lo.total, lo.off + nb, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx.stream));
+          HIP_TRY(hipStreamSynchronize(ctx.stream));
+        }
+        return kOnceBuilt;
+      })) return rc;
+  const uint64_t T = g->list_off->total;
   const uint64_t nw = (d_tri && first < T) ? std::min<uint64_t>(cap, T - first) : 0;
   if (nw > 0) {
-    lp.off = g->d_list_off; lp.first = first; lp.nw = nw; lp.tri = d_tri;
+    lp.off = g->list_off->off; lp.first = first; lp.nw = nw; lp.tri = d_tri;
     HIP_TRY(launch_list_fill(lp, g->cu_count, ctx.stream));
   }
   gm_stats s;

@@ -24,35 +24,33 @@ static int centre_estimates(size_t nv, int parts, Launch launch, const char *wha
 // Every centre with work, by its 2-path estimate (work_launch: the kernel that writes it per centre), as one task list on the device, once
 // per graph (the form with every end in the global maps): heavy first, then light by 4
 template <class WorkLaunch>
-static int build_centre_tasks(gm_graph *g, WorkLaunch work_launch, const char *what, DevOwn<int4> &d_tasks, unsigned long long *n_tasks) {
-  if (d_tasks) return GM_OK;
-  OtherSetupScope scope(g);
-  const size_t nv = (size_t)g->nv;
-  std::vector<unsigned long long> work;
-  if (int rc = centre_estimates(nv, 1, work_launch, what, work)) return rc;
-  std::vector<int> vs;
-  vs.reserve(nv);
-  for (size_t v = 0; v < nv; ++v)
-    if (work[v] > 0) vs.push_back((int)v);
-  std::stable_sort(vs.begin(), vs.end(), [&](int a, int b) { return work[(size_t)a] > work[(size_t)b]; });
-  std::vector<int4> tasks;
-  emit_centre_tasks(vs, work.data(), kHeavyCentre, tasks);
-  DevOwn<int4> d;
-  if (int rc = upload(d, tasks)) return rc;
-  *n_tasks = tasks.size();
-  d_tasks = std::move(d);  // (the list is what says "built": handed over whole)
-  return GM_OK;
+static int build_centre_tasks(gm_graph *g, WorkLaunch work_launch, const char *what, Once<CentreTaskList> &list) {
+  return list.ensure(g->mu, [&](CentreTaskList &out) {
+    OtherSetupScope scope(g);
+    const size_t nv = (size_t)g->nv;
+    std::vector<unsigned long long> work;
+    if (int rc = centre_estimates(nv, 1, work_launch, what, work)) return rc;
+    std::vector<int> vs;
+    vs.reserve(nv);
+    for (size_t v = 0; v < nv; ++v)
+      if (work[v] > 0) vs.push_back((int)v);
+    std::stable_sort(vs.begin(), vs.end(), [&](int a, int b) { return work[(size_t)a] > work[(size_t)b]; });
+    std::vector<int4> tasks;
+    emit_centre_tasks(vs, work.data(), kHeavyCentre, tasks);
+    if (int rc = upload(out.tasks, tasks)) return rc;
+    out.n = tasks.size();
+    return kOnceBuilt;
+  });
 }
 
 // rectangle, flattened over wedges (rect_flat_kernel in gm_mine.hip)
 static int ensure_idx0(gm_graph *g, const GraphView &gv) {
-  if (g->d_idx0) return GM_OK;
-  OtherSetupScope scope(g);
-  DevOwn<int> idx0;
-  HIP_TRY(idx0.alloc(sizeof(int) * (size_t)std::max(g->nv, 1)));
-  HIP_TRY(launch_idx0(gv, idx0, 0));
-  g->d_idx0 = std::move(idx0);
-  return GM_OK;
+  return g->rect_idx.ensure(g->mu, [&](RectIdx &ri) {
+    OtherSetupScope scope(g);
+    HIP_TRY(ri.idx0.alloc(sizeof(int) * (size_t)std::max(g->nv, 1)));
+    HIP_TRY(launch_idx0(gv, ri.idx0, 0));
+    return kOnceBuilt;
+  });
 }
 
 int run_rect_flat(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm_stats *st, bool pentagon) {
@@ -62,12 +60,12 @@ int run_rect_flat(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, g
   gm_graph *g = ctx.g;
   const gm_launch *la = &ctx.la;
   const GraphView gv = graph_view(g);
-  if (!g->d_wblock_prefix) {  // once per graph: idx0[v] on the device, wedge-block prefix on the host
+  rc = ensure_idx0(g, gv);  // (takes the lock itself)
+  if (rc) return rc;
+  rc = g->wedge_blocks.ensure(g->mu, [&](WedgeBlocks &wb) {  // once per graph: idx0[v] on the device, wedge-block prefix on the host
     OtherSetupScope scope(g);
-    rc = ensure_idx0(g, gv);
-    if (rc) return rc;
     std::vector<int> idx0((size_t)std::max(g->nv, 1));
-    HIP_TRY(hipMemcpy(idx0.data(), g->d_idx0, sizeof(int) * (size_t)g->nv, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(idx0.data(), g->rect_idx->idx0, sizeof(int) * (size_t)g->nv, hipMemcpyDeviceToHost));
     std::vector<unsigned long long> pre((size_t)g->nv + 1);
     unsigned long long acc = 0;
     for (int v = 0; v < g->nv; ++v) {
@@ -76,18 +74,18 @@ int run_rect_flat(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, g
       acc += (n * (n - (n ? 1ull : 0ull)) / 2ull + 63ull) / 64ull;
     }
     pre[g->nv] = acc;
-    g->n_wblocks = acc;
-    DevOwn<unsigned long long> d_pre;
-    HIP_TRY(d_pre.alloc(sizeof(unsigned long long) * ((size_t)g->nv + 1)));
-    HIP_TRY(hipMemcpy(d_pre, pre.data(), sizeof(unsigned long long) * ((size_t)g->nv + 1), hipMemcpyHostToDevice));
-    g->d_wblock_prefix = std::move(d_pre);
-  }
+    wb.n = acc;
+    HIP_TRY(wb.prefix.alloc(sizeof(unsigned long long) * ((size_t)g->nv + 1)));
+    HIP_TRY(hipMemcpy(wb.prefix, pre.data(), sizeof(unsigned long long) * ((size_t)g->nv + 1), hipMemcpyHostToDevice));
+    return kOnceBuilt;
+  });
+  if (rc) return rc;
   RectParams p;
   memset(&p, 0, sizeof p);
   p.g = gv;
-  p.idx0 = g->d_idx0;
-  p.block_prefix = g->d_wblock_prefix;
-  p.nblocks = g->n_wblocks;
+  p.idx0 = g->rect_idx->idx0;
+  p.block_prefix = g->wedge_blocks->prefix;
+  p.nblocks = g->wedge_blocks->n;
   p.group = la->chunk > 0 ? la->chunk : (pentagon ? 2 : 16);
   const long long ngroups = (long long)((p.nblocks + (unsigned long long)p.group - 1) / (unsigned long long)p.group);
   const int64_t count = take_range(ctx, ngroups, p);
@@ -109,7 +107,6 @@ static int upload_centre_tasks(const CentreTasks &t, CentrePlan &pl) {
   pl.n_acc_tasks = t.acc_tasks.size();
   pl.n_lds_tasks = t.lds_tasks.size();
   pl.n_cut = t.n_cut;
-  pl.ready = true;
   return GM_OK;
 }
 static int max_lds_ranges(int limit) {
@@ -118,66 +115,67 @@ static int max_lds_ranges(int limit) {
 }
 // rectangle: the 2-path ends in the last ranges of ids (at most kRectLdsRanges) of the centres with >= GM_RECT_LDS_MIN 2-paths are counted in
 // LDS maps (rect_lds_kernel): the ranges, the row bounds, the (centre, range) tasks, rect_acc_kernel's list with those centres in front
-static int ensure_rect_plan(gm_graph *g, const GraphView &gv) {
-  if (g->rect_plan.ready) return GM_OK;
-  OtherSetupScope scope(g);
-  const size_t nv = (size_t)g->nv;
-  unsigned long long lds_min = 4096;
-  if (const char *e = gm_opt("GM_RECT_LDS_MIN")) lds_min = std::strtoull(e, nullptr, 10);
-  const int nblk = (int)((nv + kRectLdsWords - 1) / kRectLdsWords);
-  std::vector<int> bmax((size_t)std::max(nblk, 1), 0);
-  if (nv) {
-    DevOwn<int> d_bmax;
-    HIP_TRY(d_bmax.alloc(sizeof(int) * (size_t)nblk));
-    hipError_t e0 = hipMemset(d_bmax, 0, sizeof(int) * (size_t)nblk);
-    if (e0 == hipSuccess) e0 = launch_rect_blockmax(gv, d_bmax, 0);
-    if (e0 == hipSuccess) e0 = hipMemcpy(bmax.data(), d_bmax, sizeof(int) * (size_t)nblk, hipMemcpyDeviceToHost);
-    if (e0 != hipSuccess) return hip_fail(e0, "rect_blockmax_kernel", __FILE__, __LINE__);
-  }
-  RectLdsRanges rr{};  // (whatever the numbering: tune[6] & GM_T6_AS_NUMBERED runs on the graph as given)
-  rr.n = rect_lds_ranges((long long)g->nv, bmax, kRectLdsWords, max_lds_ranges(kRectLdsRanges), rr.rb, rr.lb);
-  setup_trace("rect: ranges");
-  CentrePlan pl;
-  pl.cut = rr.rb[0];
-  pl.bnd_stride = rr.n + 1;
-  HIP_TRY(pl.d_bnd.alloc(sizeof(int) * (size_t)pl.bnd_stride * std::max<size_t>(nv, 1)));
-  std::vector<unsigned long long> est;  // (both estimates: [0, nv) all ends, [nv, 2 nv) the ends below the cut)
-  if (nv) HIP_TRY(launch_rect_bounds(gv, rr, pl.d_bnd, 0));
-  if (int rc = centre_estimates(nv, 2, [&](unsigned long long *d_work) { return launch_rect_work_cut(gv, g->d_idx0, pl.d_bnd, pl.bnd_stride, d_work, 0); }, "rect_work_cut_kernel", est)) return rc;
-  setup_trace("rect: bounds + work estimates");
-  std::vector<int> idx0h(std::max<size_t>(nv, 1));
-  if (nv) HIP_TRY(hipMemcpy(idx0h.data(), g->d_idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
-  const CentreTasks tasks = plan_rect_tasks(nv, est.data(), est.data() + nv, idx0h.data(), rr.rb, rr.n, lds_min, kRectLdsWaves * GM_WAVE, kHeavyCentre);
-  if (int rc = upload_centre_tasks(tasks, pl)) return rc;
-  g->rect_ranges = rr, g->rect_plan = std::move(pl);
-  setup_trace("rect: task lists");
-  return GM_OK;
+static int ensure_rect_plan(gm_graph *g, const GraphView &gv) {  // (after ensure_idx0)
+  const int *d_idx0 = g->rect_idx->idx0;
+  return g->rect_lds.ensure(g->mu, [&](RectLdsPlan &out) {
+    OtherSetupScope scope(g);
+    const size_t nv = (size_t)g->nv;
+    unsigned long long lds_min = 4096;
+    if (const char *e = gm_opt("GM_RECT_LDS_MIN")) lds_min = std::strtoull(e, nullptr, 10);
+    const int nblk = (int)((nv + kRectLdsWords - 1) / kRectLdsWords);
+    std::vector<int> bmax((size_t)std::max(nblk, 1), 0);
+    if (nv) {
+      DevOwn<int> d_bmax;
+      HIP_TRY(d_bmax.alloc(sizeof(int) * (size_t)nblk));
+      hipError_t e0 = hipMemset(d_bmax, 0, sizeof(int) * (size_t)nblk);
+      if (e0 == hipSuccess) e0 = launch_rect_blockmax(gv, d_bmax, 0);
+      if (e0 == hipSuccess) e0 = hipMemcpy(bmax.data(), d_bmax, sizeof(int) * (size_t)nblk, hipMemcpyDeviceToHost);
+      if (e0 != hipSuccess) return hip_fail(e0, "rect_blockmax_kernel", __FILE__, __LINE__);
+    }
+    RectLdsRanges &rr = out.ranges = RectLdsRanges{};  // (whatever the numbering: tune[6] & GM_T6_AS_NUMBERED runs on the graph as given)
+    rr.n = rect_lds_ranges((long long)g->nv, bmax, kRectLdsWords, max_lds_ranges(kRectLdsRanges), rr.rb, rr.lb);
+    setup_trace("rect: ranges");
+    CentrePlan &pl = out.plan;
+    pl.cut = rr.rb[0];
+    pl.bnd_stride = rr.n + 1;
+    HIP_TRY(pl.d_bnd.alloc(sizeof(int) * (size_t)pl.bnd_stride * std::max<size_t>(nv, 1)));
+    std::vector<unsigned long long> est;  // (both estimates: [0, nv) all ends, [nv, 2 nv) the ends below the cut)
+    if (nv) HIP_TRY(launch_rect_bounds(gv, rr, pl.d_bnd, 0));
+    if (int rc = centre_estimates(nv, 2, [&](unsigned long long *d_work) { return launch_rect_work_cut(gv, d_idx0, pl.d_bnd, pl.bnd_stride, d_work, 0); }, "rect_work_cut_kernel", est)) return rc;
+    setup_trace("rect: bounds + work estimates");
+    std::vector<int> idx0h(std::max<size_t>(nv, 1));
+    if (nv) HIP_TRY(hipMemcpy(idx0h.data(), d_idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
+    const CentreTasks tasks = plan_rect_tasks(nv, est.data(), est.data() + nv, idx0h.data(), rr.rb, rr.n, lds_min, kRectLdsWaves * GM_WAVE, kHeavyCentre);
+    if (int rc = upload_centre_tasks(tasks, pl)) return rc;
+    setup_trace("rect: task lists");
+    return kOnceBuilt;
+  });
 }
 // house: the same with ranges of kHouseLdsIds ids (at most kHouseLdsRanges) and plan_house_tasks' policy (GM_HOUSE_WALK_MIN: its 2-paths per walk)
 static int ensure_house_plan(gm_graph *g, const GraphView &gv) {
-  if (g->house_plan.ready) return GM_OK;
-  OtherSetupScope scope(g);
-  const size_t nv = (size_t)g->nv;
-  const char *lds_min_given = gm_opt("GM_RECT_LDS_MIN");
-  const unsigned long long lds_min = lds_min_given ? std::strtoull(lds_min_given, nullptr, 10) : 4096;
-  HouseLdsRanges rr = {0, 0, g->nv};
-  rr.n = house_lds_ranges((long long)g->nv, kHouseLdsIds, max_lds_ranges(kHouseLdsRanges), &rr.cut);
-  CentrePlan pl;
-  pl.cut = rr.cut;
-  pl.bnd_stride = rr.n + 1;
-  HIP_TRY(pl.d_bnd.alloc(sizeof(int) * (size_t)pl.bnd_stride * std::max<size_t>(nv, 1)));
-  std::vector<unsigned long long> est;
-  if (nv) HIP_TRY(launch_house_bounds(gv, rr, pl.d_bnd, 0));
-  if (int rc = centre_estimates(nv, 2, [&](unsigned long long *d_work) { return launch_house_work_cut(gv, pl.d_bnd, pl.bnd_stride, d_work, 0); }, "house_work_cut_kernel", est)) return rc;
-  std::vector<int> deg(nv + 1, 0);  // (the offsets, then their differences)
-  if (nv) HIP_TRY(hipMemcpy(deg.data(), g->d_rp, sizeof(int) * (nv + 1), hipMemcpyDeviceToHost));
-  for (size_t v = 0; v < nv; ++v) deg[v] = deg[v + 1] - deg[v];
-  unsigned long long per_walk = 200;
-  if (const char *e = gm_sweep_env("GM_HOUSE_WALK_MIN")) per_walk = std::strtoull(e, nullptr, 10);
-  const CentreTasks tasks = plan_house_tasks(nv, est.data(), est.data() + nv, deg.data(), rr.n, lds_min, lds_min_given != nullptr, per_walk, kRectLdsWaves * GM_WAVE, kHeavyCentre);
-  if (int rc = upload_centre_tasks(tasks, pl)) return rc;
-  g->house_ranges = rr, g->house_plan = std::move(pl);
-  return GM_OK;
+  return g->house_lds.ensure(g->mu, [&](HouseLdsPlan &out) {
+    OtherSetupScope scope(g);
+    const size_t nv = (size_t)g->nv;
+    const char *lds_min_given = gm_opt("GM_RECT_LDS_MIN");
+    const unsigned long long lds_min = lds_min_given ? std::strtoull(lds_min_given, nullptr, 10) : 4096;
+    HouseLdsRanges &rr = out.ranges = HouseLdsRanges{0, 0, g->nv};
+    rr.n = house_lds_ranges((long long)g->nv, kHouseLdsIds, max_lds_ranges(kHouseLdsRanges), &rr.cut);
+    CentrePlan &pl = out.plan;
+    pl.cut = rr.cut;
+    pl.bnd_stride = rr.n + 1;
+    HIP_TRY(pl.d_bnd.alloc(sizeof(int) * (size_t)pl.bnd_stride * std::max<size_t>(nv, 1)));
+    std::vector<unsigned long long> est;
+    if (nv) HIP_TRY(launch_house_bounds(gv, rr, pl.d_bnd, 0));
+    if (int rc = centre_estimates(nv, 2, [&](unsigned long long *d_work) { return launch_house_work_cut(gv, pl.d_bnd, pl.bnd_stride, d_work, 0); }, "house_work_cut_kernel", est)) return rc;
+    std::vector<int> deg(nv + 1, 0);  // (the offsets, then their differences)
+    if (nv) HIP_TRY(hipMemcpy(deg.data(), g->d_rp, sizeof(int) * (nv + 1), hipMemcpyDeviceToHost));
+    for (size_t v = 0; v < nv; ++v) deg[v] = deg[v + 1] - deg[v];
+    unsigned long long per_walk = 200;
+    if (const char *e = gm_sweep_env("GM_HOUSE_WALK_MIN")) per_walk = std::strtoull(e, nullptr, 10);
+    const CentreTasks tasks = plan_house_tasks(nv, est.data(), est.data() + nv, deg.data(), rr.n, lds_min, lds_min_given != nullptr, per_walk, kRectLdsWaves * GM_WAVE, kHeavyCentre);
+    if (int rc = upload_centre_tasks(tasks, pl)) return rc;
+    return kOnceBuilt;
+  });
 }
 // what the acc / LDS kernel reads of the plan (the two patterns' parameter structs name these members alike); returns the LDS kernel's share of the tasks
 template <class P>
@@ -224,17 +222,17 @@ int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm
   rc = ensure_idx0(g, gv);
   if (rc) return rc;
   const bool lds_maps = !pentagon && !(la->tune[6] & GM_T6_GLOBAL_MAPS);
-  if (!lds_maps) rc = build_centre_tasks(g, [&](unsigned long long *d_work) { return launch_rect_work(gv, g->d_idx0, d_work, 0); }, "rect_work_kernel", g->d_rect_tasks, &g->n_rect_tasks);
+  if (!lds_maps) rc = build_centre_tasks(g, [&](unsigned long long *d_work) { return launch_rect_work(gv, g->rect_idx->idx0, d_work, 0); }, "rect_work_kernel", g->rect_tasks);
   if (rc) return rc;
   setup_trace("rect: idx0 / old tasks");
   if (lds_maps && (rc = ensure_rect_plan(g, gv))) return rc;
   RectAccParams p;
   memset(&p, 0, sizeof p);
   p.g = gv;
-  p.idx0 = g->d_idx0;
-  p.tasks = g->d_rect_tasks;
-  if (lds_maps) acc_params_from_plan(p, g->rect_plan);
-  const int64_t count = take_range(ctx, (int64_t)(lds_maps ? g->rect_plan.n_acc_tasks : g->n_rect_tasks), p);
+  p.idx0 = g->rect_idx->idx0;
+  p.tasks = g->rect_tasks->tasks;
+  if (lds_maps) acc_params_from_plan(p, g->rect_lds->plan);
+  const int64_t count = take_range(ctx, (int64_t)(lds_maps ? g->rect_lds->plan.n_acc_tasks : g->rect_tasks->n), p);
   p.counters = g->d_counters;
   p.queue = queue_word64(g, QW64_MAIN);
   // (with the heavy centres in LDS what is left for the global maps is light: 1 / 2 / 4 / 8 workgroups per CU measured 11.15 / 10.95 /
@@ -242,15 +240,15 @@ int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm
   int acc_wgs_per_cu = lds_maps ? 2 : 8;
   if (const char *e = gm_sweep_env("GM_RECT_ACC_WGS")) acc_wgs_per_cu = std::max(1, std::atoi(e));
   size_t need = 0;
-  const int grid = map_grid(g, count, p, 4, 4, acc_wgs_per_cu, g->rect_acc_bytes, &need);
-  if (need > g->rect_acc_bytes) {
-    if (int rc_a = grow_dev(g->d_rect_acc, &g->rect_acc_bytes, need)) return rc_a;
-    HIP_TRY(hipMemset(g->d_rect_acc, 0, need));  // every launch leaves the maps zeroed again
+  const int grid = map_grid(g, count, p, 4, 4, acc_wgs_per_cu, g->maps.rect_acc_bytes, &need);
+  if (need > g->maps.rect_acc_bytes) {
+    if (int rc_a = grow_dev(g->maps.rect_acc, &g->maps.rect_acc_bytes, need)) return rc_a;
+    HIP_TRY(hipMemset(g->maps.rect_acc, 0, need));  // every launch leaves the maps zeroed again
   }
-  p.acc = g->d_rect_acc;
+  p.acc = g->maps.rect_acc;
   // touched-vertex lists: same shape as the maps (one int list of up to nv entries per wave)
-  if (int rc_t = grow_dev(g->d_pent_touched, &g->pent_touched_bytes, need)) return rc_t;
-  p.touched = g->d_pent_touched;
+  if (int rc_t = grow_dev(g->maps.pent_touched, &g->maps.pent_touched_bytes, need)) return rc_t;
+  p.touched = g->maps.pent_touched;
   setup_trace("rect: global maps");
   if (pentagon) {
     rc = ensure_edge_tables(g, gv);
@@ -258,14 +256,14 @@ int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm
     PentAccParams q;
     memset(&q, 0, sizeof q);
     q.g = gv;
-    q.idx0 = g->d_idx0;
-    q.tlt = g->d_house_tlt;
+    q.idx0 = g->rect_idx->idx0;
+    q.tlt = g->house_tables->tlt;
     q.tasks = p.tasks;
     q.first = p.first;
     q.step = p.step;
     q.count = p.count;
     q.acc = p.acc;
-    q.touched = g->d_pent_touched;
+    q.touched = g->maps.pent_touched;
     q.acc_stride = p.acc_stride;
     q.queue = p.queue;
     q.counters = p.counters;
@@ -275,8 +273,8 @@ int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm
     return end_launch(ctx, FIN_HALF_SIGNED, 0, h_out, 1, st);
   }
   RectLdsParams lp{};
-  lp.idx0 = g->d_idx0;
-  const int64_t lcount = lds_maps ? lds_params_from_plan(lp, ctx, gv, g->rect_plan, g->rect_ranges) : 0;
+  lp.idx0 = g->rect_idx->idx0;
+  const int64_t lcount = lds_maps ? lds_params_from_plan(lp, ctx, gv, g->rect_lds->plan, g->rect_lds->ranges) : 0;
   if (int rc_t = start_timer(ctx)) return rc_t;
   // (workgroups per CU: what its LDS -- the map + 1.5 KB of scratch per wave -- lets run together)
   const int lds_wgs = std::max(1, (int)((160 * 1024) / (kRectLdsWords * 4 + kRectLdsWaves * 1536 + 1024)));
@@ -291,22 +289,23 @@ int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm
 // per-entry triangle tables t / tlt (edge_tab_kernel), once per graph; every rank builds the whole tables: they are inputs of
 // every centre of the house / pentagon map kernels
 static int ensure_edge_tables(gm_graph *g, const GraphView &gv) {
-  if (g->d_house_t && g->d_house_tlt) return GM_OK;
-  OtherSetupScope scope(g);
-  const size_t ne1 = (size_t)std::max<long long>(g->ne, 1);
-  DevBuf<unsigned> t, tlt;
-  HIP_TRY(t.alloc(ne1, true));  // (handed to the handle below)
-  HIP_TRY(tlt.alloc(ne1, true));
-  if (g->ne > 0) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(g->d_counters, 0, kCounterBlockBytes));
-    HIP_TRY(launch_edge_tab(gv, t.p, tlt.p, queue_word64(g, QW64_MAIN), g->cu_count * 8, 0));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(g->d_counters, 0, kCounterBlockBytes));  // (the table kernel used the dequeue head)
-  }
-  g->d_house_t.take(t);  // (published only after the build kernel has succeeded; the buffers free themselves on the error paths)
-  g->d_house_tlt.take(tlt);
-  return GM_OK;
+  return g->house_tables.ensure(g->mu, [&](HouseTables &ht) {
+    OtherSetupScope scope(g);
+    const size_t ne1 = (size_t)std::max<long long>(g->ne, 1);
+    DevBuf<unsigned> t, tlt;
+    HIP_TRY(t.alloc(ne1, true));  // (handed to the handle below)
+    HIP_TRY(tlt.alloc(ne1, true));
+    if (g->ne > 0) {
+      HIP_TRY(hipDeviceSynchronize());
+      HIP_TRY(hipMemset(g->d_counters, 0, kCounterBlockBytes));
+      HIP_TRY(launch_edge_tab(gv, t.p, tlt.p, queue_word64(g, QW64_MAIN), g->cu_count * 8, 0));
+      HIP_TRY(hipDeviceSynchronize());
+      HIP_TRY(hipMemset(g->d_counters, 0, kCounterBlockBytes));  // (the table kernel used the dequeue head)
+    }
+    ht.t.take(t);  // (only after the build kernel has succeeded; the buffers free themselves on the error paths)
+    ht.tlt.take(tlt);
+    return kOnceBuilt;
+  });
 }
 
 // house by wedge accumulation (edge_tab_kernel + house_acc_kernel + house_lds_kernel in gm_mine.hip); tune[6] & GM_T6_GLOBAL_MAPS: every end in
@@ -321,32 +320,32 @@ static int run_house_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h
   rc = ensure_edge_tables(g, gv);
   if (rc) return rc;
   const bool lds_maps = !(la->tune[6] & GM_T6_GLOBAL_MAPS);
-  rc = lds_maps ? ensure_house_plan(g, gv) : build_centre_tasks(g, [&](unsigned long long *d_work) { return launch_house_work(gv, d_work, 0); }, "house_work_kernel", g->d_house_tasks, &g->n_house_tasks);
+  rc = lds_maps ? ensure_house_plan(g, gv) : build_centre_tasks(g, [&](unsigned long long *d_work) { return launch_house_work(gv, d_work, 0); }, "house_work_kernel", g->house_tasks);
   if (rc) return rc;
   HouseAccParams p;
   memset(&p, 0, sizeof p);
   p.g = gv;
-  p.t = g->d_house_t;
-  p.tlt = g->d_house_tlt;
-  p.tasks = g->d_house_tasks;
-  if (lds_maps) acc_params_from_plan(p, g->house_plan);
-  const int64_t count = take_range(ctx, (int64_t)(lds_maps ? g->house_plan.n_acc_tasks : g->n_house_tasks), p);
+  p.t = g->house_tables->t;
+  p.tlt = g->house_tables->tlt;
+  p.tasks = g->house_tasks->tasks;
+  if (lds_maps) acc_params_from_plan(p, g->house_lds->plan);
+  const int64_t count = take_range(ctx, (int64_t)(lds_maps ? g->house_lds->plan.n_acc_tasks : g->house_tasks->n), p);
   p.counters = g->d_counters;
   p.queue = queue_word64(g, QW64_MAIN);
   size_t need = 0;
-  const int grid = map_grid(g, count, p, 8, 3, lds_maps ? 4 : 8, g->house_acc_bytes, &need);
-  if (need > g->house_acc_bytes) {
-    g->house_acc_bytes = 0;
-    HIP_TRY(g->d_house_acc.alloc(need));
-    HIP_TRY(hipMemset(g->d_house_acc, 0, need));  // every launch leaves the maps zeroed again
-    HIP_TRY(g->d_house_touched.alloc(need / 2));  // one int list per map
-    g->house_acc_bytes = need;
+  const int grid = map_grid(g, count, p, 8, 3, lds_maps ? 4 : 8, g->maps.house_acc_bytes, &need);
+  if (need > g->maps.house_acc_bytes) {
+    g->maps.house_acc_bytes = 0;
+    HIP_TRY(g->maps.house_acc.alloc(need));
+    HIP_TRY(hipMemset(g->maps.house_acc, 0, need));  // every launch leaves the maps zeroed again
+    HIP_TRY(g->maps.house_touched.alloc(need / 2));  // one int list per map
+    g->maps.house_acc_bytes = need;
   }
-  p.acc = g->d_house_acc;
-  p.touched = g->d_house_touched;
+  p.acc = g->maps.house_acc;
+  p.touched = g->maps.house_touched;
   HouseLdsParams lp{};
-  lp.t = g->d_house_t;
-  const int64_t lcount = lds_maps ? lds_params_from_plan(lp, ctx, gv, g->house_plan, g->house_ranges) : 0;
+  lp.t = g->house_tables->t;
+  const int64_t lcount = lds_maps ? lds_params_from_plan(lp, ctx, gv, g->house_lds->plan, g->house_lds->ranges) : 0;
   if (int rc_t = start_timer(ctx)) return rc_t;
   if (lcount > 0) HIP_TRY(launch_house_lds(lp, (int)std::min<long long>((long long)g->cu_count, (long long)lcount), ctx.stream));
   if (count > 0) HIP_TRY(launch_house_acc(p, grid, ctx.stream));
@@ -362,7 +361,7 @@ static int run_house_flat(const gm_graph *cg, const gm_launch *la_in, uint64_t *
   gm_graph *g = ctx.g;
   const gm_launch *la = &ctx.la;
   const GraphView gv = graph_view(g);
-  if (!g->d_house_prefix) {  // once per graph: blocks per entry on the device, prefix on the host
+  rc = g->house_blocks.ensure(g->mu, [&](HouseBlocks &hb) {  // once per graph: blocks per entry on the device, prefix on the host
     OtherSetupScope scope(g);
     const size_t ne = (size_t)g->ne;
     DevOwn<unsigned> d_nblk;
@@ -376,17 +375,17 @@ static int run_house_flat(const gm_graph *cg, const gm_launch *la_in, uint64_t *
     unsigned long long acc = 0;
     for (size_t i = 0; i < ne; ++i) { pre[i] = acc; acc += nblk[i]; }
     pre[ne] = acc;
-    g->n_house_blocks = acc;
-    DevOwn<unsigned long long> d_pre;
-    HIP_TRY(d_pre.alloc(sizeof(unsigned long long) * (ne + 1)));
-    HIP_TRY(hipMemcpy(d_pre, pre.data(), sizeof(unsigned long long) * (ne + 1), hipMemcpyHostToDevice));
-    g->d_house_prefix = std::move(d_pre);
-  }
+    hb.n = acc;
+    HIP_TRY(hb.prefix.alloc(sizeof(unsigned long long) * (ne + 1)));
+    HIP_TRY(hipMemcpy(hb.prefix, pre.data(), sizeof(unsigned long long) * (ne + 1), hipMemcpyHostToDevice));
+    return kOnceBuilt;
+  });
+  if (rc) return rc;
   HouseParams p;
   memset(&p, 0, sizeof p);
   p.g = gv;
-  p.entry_prefix = g->d_house_prefix;
-  p.nblocks = g->n_house_blocks;
+  p.entry_prefix = g->house_blocks->prefix;
+  p.nblocks = g->house_blocks->n;
   p.group = la->chunk > 0 ? la->chunk : 8;
   p.no_bits = (la->tune[6] & GM_T6_HOUSE_NO_BITMAP) ? 1 : 0;
   const long long ngroups = (long long)((p.nblocks + (unsigned long long)p.group - 1) / (unsigned long long)p.group);
@@ -421,7 +420,7 @@ static int run_sgl_nested(int pat, const gm_graph *cg, const gm_launch *la_in, u
     const size_t need = (size_t)grid * 4 * (size_t)p.max_deg * sizeof(int);
     rc = ensure_scratch(g, need);
     if (rc) return rc;
-    p.scratch = reinterpret_cast<int *>(g->d_scratch.get());
+    p.scratch = reinterpret_cast<int *>(g->scratch.p.get());
   }
   if (int rc_t = start_timer(ctx)) return rc_t;
   if (count > 0) HIP_TRY(launch_sgl_nested(pat, p, grid, ctx.stream));
@@ -474,9 +473,9 @@ extern "C" int gm_diamond_support_info(const gm_graph *sym, int64_t info[4]) {
   HIP_TRY(hipDeviceSynchronize());
   unsigned long long at = 0;
   HIP_TRY(hipMemcpy(&at, run_on->d_counters + 2, sizeof at, hipMemcpyDeviceToHost));
-  info[0] = run_on->smask_state == 1 ? (int64_t)run_on->smask_words : 0;  // 64-bit words of the match-mask arena (0: no masks)
+  info[0] = run_on->sup_masks.built() ? (int64_t)run_on->sup_masks->words : 0;  // 64-bit words of the match-mask arena (0: no masks)
   info[1] = (int64_t)at;                                                  // increments issued as global atomics from the waves' queues
-  info[2] = run_on->smask_state == 1 ? (int64_t)run_on->n_sup_far_rows : 0;
+  info[2] = run_on->sup_masks.built() ? (int64_t)run_on->sup_masks->n_far_rows : 0;
   info[3] = (int64_t)sup_mask_min_tail(run_on);
   return GM_OK;
 }
@@ -486,18 +485,18 @@ extern "C" int gm_sup_core_info(const gm_graph *sym, int64_t info[4]) {
   gm_graph *run_on = nullptr;
   const int rc = diamond_run_on(sym, nullptr, &run_on);
   if (rc) return rc;
-  const bool on = run_on->tl_skip_from < run_on->nv;
-  const long long nb = on ? run_on->tl_core_h >> 8 : 0;
-  info[0] = on ? run_on->tl_core_h : 0;  // vertices of the corner (0: every edge's support comes from the triangle pass)
+  const bool on = run_on->tasklists->skip_from < run_on->nv;
+  const long long nb = on ? run_on->tasklists->core_h >> 8 : 0;
+  info[0] = on ? run_on->tasklists->core_h : 0;  // vertices of the corner (0: every edge's support comes from the triangle pass)
   info[1] = 0;
   if (on) {
     int e0 = 0;
     HIP_TRY(hipSetDevice(run_on->device));
-    HIP_TRY(hipMemcpy(&e0, run_on->d_rp + run_on->tl_skip_from, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&e0, run_on->d_rp + run_on->tasklists->skip_from, sizeof(int), hipMemcpyDeviceToHost));
     info[1] = run_on->ne - (long long)e0;  // DAG entries inside it
   }
   info[2] = nb * (nb + 1) / 2;           // pairs of 256-row blocks of the product
-  info[3] = on ? (run_on->tl_core_h >> 9) : 0;  // 512-column chunks of a row
+  info[3] = on ? (run_on->tasklists->core_h >> 9) : 0;  // 512-column chunks of a row
   return GM_OK;
 }
 extern "C" int gm_diamond_support_partial(const gm_graph *sym, const gm_launch *la, uint32_t *d_support, int64_t n_entries, gm_stats *st) {
@@ -583,19 +582,20 @@ extern "C" int gm_sgl5_finish(const char *pattern, const uint64_t raw[GM_SGL5_NR
 
 // the per-handle arrays of the weighted pass on the DAG it runs on; the symmetric degrees are built once
 static int ensure_w5_buffers(gm_graph *g) {
-  std::lock_guard<std::mutex> lk(g->mu);
-  if (g->d_w5out) return GM_OK;
   HIP_TRY(hipSetDevice(g->device));
   const size_t ne = (size_t)std::max<long long>(g->ne, 1), nv = (size_t)std::max(g->nv, 1);
-  if (!g->d_w5sup) HIP_TRY(g->d_w5sup.alloc(sizeof(unsigned) * (size_t)diamond_support_entries(g->ne, 1)));
-  if (!g->d_w5ed) HIP_TRY(g->d_w5ed.alloc(sizeof(unsigned) * ne));
-  if (!g->d_w5tv2) HIP_TRY(g->d_w5tv2.alloc(sizeof(unsigned long long) * nv));
-  if (!g->d_w5deg) {
-    HIP_TRY(g->d_w5deg.alloc(sizeof(int) * nv));
-    HIP_TRY(launch_wtri_degrees(g->nv, g->ne, g->d_rp, g->d_col, g->d_w5deg, g->cu_count, 0));
-    HIP_TRY(hipDeviceSynchronize());
-  }
-  HIP_TRY(g->d_w5out.alloc(64));
+  if (const int rc = g->w5deg.ensure(g->mu, [&](SymDegrees &sd) {
+        HIP_TRY(sd.deg.alloc(sizeof(int) * nv));
+        HIP_TRY(launch_wtri_degrees(g->nv, g->ne, g->d_rp, g->d_col, sd.deg, g->cu_count, 0));
+        HIP_TRY(hipDeviceSynchronize());
+        return kOnceBuilt;
+      })) return rc;
+  std::lock_guard<std::mutex> lk(g->mu);
+  if (g->w5.out) return GM_OK;
+  if (!g->w5.sup) HIP_TRY(g->w5.sup.alloc(sizeof(unsigned) * (size_t)diamond_support_entries(g->ne, 1)));
+  if (!g->w5.ed) HIP_TRY(g->w5.ed.alloc(sizeof(unsigned) * ne));
+  if (!g->w5.tv2) HIP_TRY(g->w5.tv2.alloc(sizeof(unsigned long long) * nv));
+  HIP_TRY(g->w5.out.alloc(64));
   return GM_OK;
 }
 
@@ -629,13 +629,13 @@ static int sgl5_raw_needs(const gm_graph *sym, unsigned needs, const gm_launch *
     if (int rc = diamond_run_on(sym, &l2, &run_on)) return rc;
     if (int rc = ensure_w5_buffers(run_on)) return rc;
     uint64_t dummy = 0, ab[4] = {0, 0, 0, 0};
-    if (int rc = sub.run([&](gm_stats *s) { return run_pattern({PAT_SUPPORT_PART, 3, -1, 0, run_on->d_w5sup}, run_on, &l2, &dummy, 1, s); })) return rc;
+    if (int rc = sub.run([&](gm_stats *s) { return run_pattern({PAT_SUPPORT_PART, 3, -1, 0, run_on->w5.sup}, run_on, &l2, &dummy, 1, s); })) return rc;
     PatternReq weighted{PAT_WTRI, 3, FIN_RAW4};
     weighted.wtri_tri = need(R5_A) || need(R5_B);
     weighted.wtri_vert = need(R5_H) || need(R5_S);
     if (int rc = sub.run([&](gm_stats *s) { return run_pattern(weighted, run_on, &l2, ab, 4, s); })) return rc;
     unsigned long long o[5] = {0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpy(o, run_on->d_w5out, sizeof o, hipMemcpyDeviceToHost));  // (run_pattern has synchronised the stream)
+    HIP_TRY(hipMemcpy(o, run_on->w5.out, sizeof o, hipMemcpyDeviceToHost));  // (run_pattern has synchronised the stream)
     const uint64_t v[7] = {o[0] / 3ull, o[1], o[2], ab[0], ab[1], o[3], o[4]};
     const int at[7] = {R5_T, R5_D, R5_W, R5_A, R5_B, R5_H, R5_S};
     for (int i = 0; i < 7; ++i)
@@ -661,7 +661,7 @@ static int sgl5_raw_needs(const gm_graph *sym, unsigned needs, const gm_launch *
           ChouseParams cp;
           memset(&cp, 0, sizeof cp);
           cp.nv = g->nv; cp.ne = g->ne; cp.rp = g->d_rp; cp.col = g->d_col;
-          cp.scratch = reinterpret_cast<int *>(g->d_scratch.get()); cp.max_deg = std::max(g->max_deg, 1); cp.out = g->d_counters;
+          cp.scratch = reinterpret_cast<int *>(g->scratch.p.get()); cp.max_deg = std::max(g->max_deg, 1); cp.out = g->d_counters;
           HIP_TRY(launch_chouse(cp, grid, c.stream));
           return (int)GM_OK;
         })) return rc;
@@ -801,30 +801,30 @@ static int run_wrect(const gm_graph *sym, const gm_launch *la_in, uint64_t out[2
   gm_graph *g = ctx.g;
   const GraphView gv = graph_view(g);
   if (int rc = ensure_idx0(g, gv)) return rc;
-  if (std::lock_guard<std::mutex> lk(g->mu); !g->wrect_ready) {  // (two first calls on one handle: one builds, the other waits)
+  if (const int rc = g->wrect.ensure(g->mu, [&](WrectPlan &wp) {  // (two first calls on one handle: one builds, the other waits)
     OtherSetupScope scope(g);
     const size_t nv = (size_t)g->nv;
     int range = kWrectRange;
     if (const char *e = gm_opt("GM_WRECT_RANGE")) range = std::max(16, std::min(kWrectRange, std::atoi(e)));
     const long long nranges = std::max<long long>(1, ((long long)g->nv + range - 1) / range);
-    g->wrect_range = range;
-    g->wrect_grp = (int)((nranges + 63) / 64);
-    HIP_TRY(g->d_wrect_mask.alloc(sizeof(unsigned long long) * std::max<size_t>(nv, 1)));
-    HIP_TRY(launch_wrect_mask(g->nv, g->d_rp, g->d_col, range, g->wrect_grp, g->d_wrect_mask, g->cu_count, 0));
+    wp.range = range;
+    wp.grp = (int)((nranges + 63) / 64);
+    HIP_TRY(wp.mask.alloc(sizeof(unsigned long long) * std::max<size_t>(nv, 1)));
+    HIP_TRY(launch_wrect_mask(g->nv, g->d_rp, g->d_col, range, wp.grp, wp.mask, g->cu_count, 0));
     std::vector<int> idx0h(std::max<size_t>(nv, 1));
-    if (nv) HIP_TRY(hipMemcpy(idx0h.data(), g->d_idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
+    if (nv) HIP_TRY(hipMemcpy(idx0h.data(), g->rect_idx->idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
     const std::vector<int2> tasks = wrect_tasks(idx0h.data(), nv, range, kWrectThreads);  // (the hubs' per-range tasks first)
-    g->n_wrect_tasks = tasks.size();
-    HIP_TRY(g->d_wrect_tasks.alloc(sizeof(int2) * std::max<size_t>(tasks.size(), 1)));
-    if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_wrect_tasks, tasks.data(), sizeof(int2) * tasks.size(), hipMemcpyHostToDevice));
+    wp.n_tasks = tasks.size();
+    HIP_TRY(wp.tasks.alloc(sizeof(int2) * std::max<size_t>(tasks.size(), 1)));
+    if (!tasks.empty()) HIP_TRY(hipMemcpy(wp.tasks, tasks.data(), sizeof(int2) * tasks.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());
-    g->wrect_ready = true;
-  }
+    return kOnceBuilt;
+  })) return rc;
   WrectParams p;
   memset(&p, 0, sizeof p);
-  p.rp = g->d_rp; p.col = g->d_col; p.idx0 = g->d_idx0;
-  p.rmask = g->d_wrect_mask; p.range = g->wrect_range; p.grp = g->wrect_grp;
-  p.tasks = g->d_wrect_tasks; p.count = g->n_wrect_tasks;
+  p.rp = g->d_rp; p.col = g->d_col; p.idx0 = g->rect_idx->idx0;
+  p.rmask = g->wrect->mask; p.range = g->wrect->range; p.grp = g->wrect->grp;
+  p.tasks = g->wrect->tasks; p.count = g->wrect->n_tasks;
   p.queue = queue_word64(g, QW64_MAIN);
   p.counters = g->d_counters;
   if (int rc = start_timer(ctx)) return rc;
@@ -866,20 +866,20 @@ extern "C" int gm_sgl6_raw(const gm_graph *sym, uint32_t need, const gm_launch *
   if (entry_sums) {
     gm_graph *run_on = nullptr;
     if (int rc = diamond_run_on(sym, &l2, &run_on)) return rc;  // (the handle the pass above ran on)
-    if (!run_on->d_w5sup || !run_on->d_w5tv2 || !run_on->d_w5deg) return GM_ERR_INVALID;
+    if (!run_on->w5.sup || !run_on->w5.tv2 || !run_on->w5deg->deg) return GM_ERR_INVALID;
     {
       std::lock_guard<std::mutex> lk(run_on->mu);
-      if (!run_on->d_s6e1) HIP_TRY(run_on->d_s6e1.alloc(sizeof(unsigned) * (size_t)std::max(run_on->nv, 1)));
+      if (!run_on->w5.s6e1) HIP_TRY(run_on->w5.s6e1.alloc(sizeof(unsigned) * (size_t)std::max(run_on->nv, 1)));
     }
     uint64_t v[4] = {0, 0, 0, 0};
     LaunchCtx ctx;
     if (int rc = begin_launch(run_on, &l2, v, ctx)) return rc;
-    HIP_TRY(hipMemsetAsync(run_on->d_s6e1, 0, sizeof(unsigned) * (size_t)std::max(run_on->nv, 1), ctx.stream));
+    HIP_TRY(hipMemsetAsync(run_on->w5.s6e1, 0, sizeof(unsigned) * (size_t)std::max(run_on->nv, 1), ctx.stream));
     if (int rc = start_timer(ctx)) return rc;
     Sgl6EntryParams ep;
     memset(&ep, 0, sizeof ep);
     ep.nv = run_on->nv; ep.ne = run_on->ne; ep.rp = run_on->d_rp; ep.col = run_on->d_col;
-    ep.sup = run_on->d_w5sup; ep.deg = run_on->d_w5deg; ep.tv2 = run_on->d_w5tv2; ep.e1 = run_on->d_s6e1; ep.out = run_on->d_counters;
+    ep.sup = run_on->w5.sup; ep.deg = run_on->w5deg->deg; ep.tv2 = run_on->w5.tv2; ep.e1 = run_on->w5.s6e1; ep.out = run_on->d_counters;
     HIP_TRY(launch_sgl6_sums(ep, run_on->cu_count, ctx.stream));
     if (int rc = sub.run([&](gm_stats *s) { return end_launch(ctx, FIN_RAW4, 0, v, 4, s); })) return rc;
     raw[R6_X] = want(R6_X) ? v[0] : 0;

@@ -11,7 +11,7 @@ using namespace gm;
 // The greedy chunk walk over the vertices [v0, v1): a contiguous run of whole rows is closed when it reaches `target` entries,
 // would exceed the LDS stage (or, k-clique, the bit-matrix budget), spans kMaxChunkVerts rows, or meets a row that is left out /
 // too long for the stage; rows longer than the stage are SPLIT into `target`-entry chunks (allow_split) or chunks of their
-// own. Runs on the host (gm_chunk_table, GM_HOST_TABLES) and, one thread per block of kTableBlock vertices, on the device:
+// own. Runs on the host (gm_chunk_table) and, one thread per block of kTableBlock vertices, on the device:
 // the walk restarts at every block boundary, so a table is the same whichever side built it.
 constexpr int kTableBlock = 512;  // (2048 until round 3: four times fewer walkers, each four times as long -- the walk is a serial chain)
 struct ChunkWalk {
@@ -130,16 +130,6 @@ __global__ __launch_bounds__(256) void chunk_cost_kernel(const int *__restrict__
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(&cost[blockIdx.x], c);
 }
 
-// edges per batch of a chunk: 64, or kSplitBatch in the SPLIT chunks of the symmetric-graph patterns whose task edges stream
-// long lists (estimated keys per entry >= kSplitBatchMinKeys)
-static int batch_edges(const ChunkRec &r, const std::vector<int> &rp, int stage_cap, unsigned long long cost) {
-  const bool whole = r.e_begin == rp[(size_t)r.u_begin] && r.e_end == rp[(size_t)r.u_end];
-  const unsigned long long nel = (unsigned long long)std::max(r.e_end - r.e_begin, 1);
-  // (the one-row chunks of the big-LDS classes are in the same situation as SPLIT chunks: every task edge streams a long list)
-  const bool long_lists = cost / nel >= (unsigned long long)kSplitBatchMinKeys;
-  return ((stage_cap == kStageCapWide && !whole && long_lists) || (stage_cap > kStageCapWide && long_lists)) ? kSplitBatch : GM_WAVE;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Task-chunk table, built on the device. The reference builds its COO task list with a serial host loop
 // (Graph::init_edgelist, src/common/graph.cc:297-326) and round 1 of this library walked the vertices on the host too
@@ -188,7 +178,8 @@ struct TableDevParams {
   RowFilter rf;
 };
 __device__ __forceinline__ bool rf_skips(const RowFilter &rf, int d) { return rf.skips(d); }
-// parts and batch sizes per chunk (batch_edges + the part rule of the host path)
+// parts and batch sizes per chunk: 64 edges per batch, or kSplitBatch in the SPLIT chunks of the symmetric-graph patterns whose task
+// edges stream long lists (estimated keys per entry >= kSplitBatchMinKeys)
 __global__ __launch_bounds__(256) void tab_parts_kernel(int n0, const ChunkRec *__restrict__ recs, const int *__restrict__ rp,
                                                         const unsigned long long *__restrict__ cost, int stage_cap, unsigned long long cap,
                                                         int cut, int *__restrict__ np_out, int *__restrict__ bsz_out) {
@@ -296,15 +287,17 @@ static int build_table_device(gm_graph *g, ChunkTable &t, bool sym_table, double
   const int *kst_rp = nullptr;
   // (a stream without the rows of the hub core, gm_ctc.hip, prices the triangle count's own tables -- rf.tct == 2 -- only: the edge supports
   // walk every task)
-  const bool kst_costs = g->d_kst_rp && (g->kst_skip_from >= g->nv ? t.rf.tct != 2 : (t.rf.tct == 2 || !g->d_trp));
+  const KeyStream &ks = *g->kst;
+  const TaskLists &tl = *g->tasklists;
+  const bool kst_costs = ks.rp && (ks.skip_from >= g->nv ? t.rf.tct != 2 : (t.rf.tct == 2 || !tl.trp));
   if (!trp && kst_costs) {  // the costs of the triangle count's tables: the key stream + the longer lists
-    trp = g->d_trpl;
-    tlen = &g->d_tdescl[0].y;
+    trp = ks.trpl;
+    tlen = &ks.tdescl[0].y;
     tstride = 2;
-    kst_rp = g->d_kst_rp;
+    kst_rp = ks.rp;
   } else if (!trp) {
-    trp = g->d_trp;
-    tlen = g->d_tdesc ? &g->d_tdesc[0].y : nullptr;
+    trp = tl.trp;
+    tlen = tl.tdesc ? &tl.tdesc[0].y : nullptr;
     tstride = 2;
   }
   const int nv = g->nv;
@@ -386,7 +379,7 @@ static int build_table_device(gm_graph *g, ChunkTable &t, bool sym_table, double
     HIP_TRY(key1.alloc((size_t)n));
     HIP_TRY(keyo.alloc((size_t)n));
     HIP_TRY(iota.alloc((size_t)n));
-    hipLaunchKernelGGL(tab_orderkeys_kernel, blocks(n), dim3(256), 0, 0, n, cost_p, heavy, sym_table ? 1 : 0, (!sym_table && g->topo_state == 1) ? 1 : 0,
+    hipLaunchKernelGGL(tab_orderkeys_kernel, blocks(n), dim3(256), 0, 0, n, cost_p, heavy, sym_table ? 1 : 0, (!sym_table && *g->facts.topological) ? 1 : 0,
                        key0.p, key1.p, iota.p);
     for (int m = 0; m < 2; ++m) {
       HIP_TRY(t.d_order[m].alloc(sizeof(int) * (size_t)n));
@@ -533,7 +526,6 @@ int get_share_order(gm_graph *g, ChunkTable *t, int world, int rank, int policy,
   std::lock_guard<std::mutex> lk(g->mu);
   for (const auto &sh : t->shares)
     if (sh.world == world && sh.rank == rank && sh.policy == policy && sh.which == which) { *out = &sh; return GM_OK; }
-  if (!t->d_edges) return GM_ERR_UNSUPPORTED;  // (a host-built table: GM_HOST_TABLES devel builds)
   SetupTimer timer;
   HIP_TRY(hipSetDevice(g->device));
   const int n = (int)t->n;
@@ -587,7 +579,6 @@ int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned
   SetupTimer timer;
   double bitmap_ms = 0;
   const bool sym_table = stage_cap >= kStageCapWide;  // a table of the symmetric-graph patterns (general, mid or big class)
-  std::vector<ChunkRec> recs;
   ChunkTable t;
   t.target = target;
   t.allow_split = allow_split;
@@ -596,166 +587,13 @@ int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned
   t.stage_cap = stage_cap;
   t.rf = rf;
   t.bitmap_min_deg = bitmap_min_deg;
-  if (!gm_sweep_env("GM_HOST_TABLES")) {  // (GM_HOST_TABLES: the same walk in a host loop over the vertices, kept for A/B)
-    HIP_TRY(hipSetDevice(g->device));
-    PoolScope pool(g);
-    int rc = build_table_device(g, t, sym_table, bitmap_ms);
-    if (rc) return rc;  // (what a partially built table owns goes back with `t`)
-    if (gm_sweep_env("GM_TABLE_INFO"))
-      fprintf(stderr, "[table/device] stage_cap %d rows (%d,%d] skip (%d,%d]: %zu chunks, est. keys %.3e, %zu bitmaps, edges %llu, %.2f ms\n",
-              stage_cap, rf.only_lo, rf.only_hi, rf.skip_lo, rf.skip_hi, t.n, (double)t.total_cost, t.n_bitmaps, t.total_edges, timer.ms());
-    g->setup.bitmap_ms += bitmap_ms;
-    g->setup.table_ms += timer.ms() - bitmap_ms;
-    g->tables.push_back(std::move(t));
-    *out = &g->tables.back();
-    return GM_OK;
-  }
-  {
-    int rc = host_rp(g, nullptr);
-    if (rc) return rc;
-  }
-  build_chunks(g->h_rp, g->nv, target, allow_split, bit_words, stage_cap, recs, t.max_bit_words, rf);
-  // estimated work per chunk (device), then: cut the heavy ones into parts, and fix the dequeue orders
-  std::vector<unsigned long long> cost(recs.size());
-  if (!recs.empty()) {
-    DevOwn<ChunkRec> d_tmp;
-    DevOwn<unsigned long long> d_cost;
-    hipError_t e = d_tmp.alloc(sizeof(ChunkRec) * recs.size());
-    if (e == hipSuccess) e = d_cost.alloc(sizeof(unsigned long long) * recs.size());
-    if (e == hipSuccess) e = hipMemcpy(d_tmp, recs.data(), sizeof(ChunkRec) * recs.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_cost, 0, sizeof(unsigned long long) * recs.size());
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(chunk_cost_kernel, dim3((unsigned)recs.size()), dim3(256), 0, 0, g->d_rp, g->d_col, d_tmp.get(), d_cost.get(),
-                         sym_table ? 1 : 0, kStageCapWide);
-      e = hipMemcpy(cost.data(), d_cost, sizeof(unsigned long long) * recs.size(), hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess) return hip_fail(e, "chunk_cost_kernel", __FILE__, __LINE__);
-  }
-  if ((allow_split || sym_table) && part_cap != 0) {  // (clique chunks are never cut: their second phase needs the whole bit-matrix; part_cap 0: never)
-    const unsigned long long cap = std::max<unsigned long long>(part_cap, 1);
-    std::vector<ChunkRec> cut;
-    std::vector<unsigned long long> cut_cost;
-    cut.reserve(recs.size());
-    cut_cost.reserve(recs.size());
-    for (size_t i = 0; i < recs.size(); ++i) {
-      const int bsz = batch_edges(recs[i], g->h_rp, stage_cap, cost[i]);
-      const int batches = (recs[i].e_end - recs[i].e_begin + bsz - 1) / bsz;
-      // a part must keep every wave of its workgroup busy for several batches: the 16-wave class takes batches of 4 edges
-      // (its rows' partners are thousands of keys long) and parts of >= 64 batches, the 4-wave classes parts of >= 16
-      const int min_batches = stage_cap == kStageCapBig ? 64 : (stage_cap == kStageCapMid ? 32 : 1);
-      const int np = (int)std::max<unsigned long long>(1, std::min<unsigned long long>((unsigned long long)std::max(batches / min_batches, 1), cost[i] / cap + (cost[i] % cap != 0)));
-      for (int q = 0; q < np; ++q) {
-        ChunkRec r = recs[i];
-        r.part = q;
-        r.nparts = np;
-        r.batch = bsz;
-        cut.push_back(r);
-        cut_cost.push_back(cost[i] / (unsigned long long)np);
-      }
-    }
-    recs.swap(cut);
-    cost.swap(cut_cost);
-  }
-  t.cost = cost;
-  t.n = recs.size();
-  t.first_vertex.resize(t.n);
-  for (size_t i = 0; i < t.n; ++i) t.first_vertex[i] = recs[i].u_begin;
-  t.edge_prefix.resize(t.n + 1);
-  t.edge_prefix[0] = 0;
-  for (size_t i = 0; i < t.n; ++i) {  // task edges of a part = the entries of its batches
-    const int nel = recs[i].e_end - recs[i].e_begin, np = recs[i].nparts;
-    unsigned long long mine = 0;
-    const int bsz = recs[i].batch;
-    for (int b = recs[i].part; b * bsz < nel; b += np) mine += (unsigned long long)std::min(bsz, nel - b * bsz);
-    t.edge_prefix[i + 1] = t.edge_prefix[i] + mine;
-  }
-  t.total_edges = t.edge_prefix.back();
-  t.total_cost = 0;
-  for (auto c : t.cost) t.total_cost += c;
-  t.host_ready = true;
-  HIP_TRY(t.d.alloc(sizeof(ChunkRec) * std::max<size_t>(t.n, 1)));
-  if (t.n) HIP_TRY(hipMemcpy(t.d, recs.data(), sizeof(ChunkRec) * t.n, hipMemcpyHostToDevice));
-  if (t.n) {
-    // Longest-processing-time-first dequeue order: the dynamic queue then ends on light chunks, so the tail of a launch
-    // (which does not shrink with the number of ranks) stays short; rank r of n owns every n-th entry of this order.
-    unsigned long long total_cost = 0;
-    for (size_t i = 0; i < t.n; ++i) total_cost += cost[i];
-    const unsigned long long heavy = 2ull * (total_cost / t.n) + 1ull;
-    for (int m = 0; m < 2; ++m) {
-      std::vector<int> &o = t.order[m];
-      o.resize(t.n);
-      for (size_t i = 0; i < t.n; ++i) o[i] = (int)i;
-      // order 0 of the symmetric-graph tables keeps chunk-id order INSIDE the heavy class as well: the heavy chunks are the
-      // SPLIT chunks of the hub rows, and consecutive chunks of one row probe the same bitmap -- run together they keep it
-      // in L2 (R-MAT-22 diamond: by cost 47.8 ms, by id 39.5 ms)
-      const bool classes_only = (m == 0) && sym_table;
-      std::stable_sort(o.begin(), o.end(), [&](int a, int b) {
-        unsigned long long ca = cost[(size_t)a], cb = cost[(size_t)b];
-        if (m == 0) { ca = ca >= heavy ? (classes_only ? 1ull : ca) : 0ull; cb = cb >= heavy ? (classes_only ? 1ull : cb) : 0ull; }
-        return ca > cb;
-      });
-      HIP_TRY(t.d_order[m].alloc(sizeof(int) * t.n));
-      HIP_TRY(hipMemcpy(t.d_order[m], o.data(), sizeof(int) * t.n, hipMemcpyHostToDevice));
-    }
-  }
-  if (allow_split) {
-    SetupTimer bm_timer;
-    // Hub rows (longer than the LDS stage, cut into SPLIT chunks) get a dense bitmap over the vertex ids, the
-    // longest rows first, within a memory budget: one probe then replaces a ~17-step bisection in HBM.
-    const unsigned long long words = ((unsigned long long)g->nv + 31ull) / 32ull;
-    const unsigned long long budget_bytes = kBitmapBudget;
-    std::vector<std::pair<int, int>> big;  // (degree, vertex)
-    for (int v = 0; v < g->nv; ++v) {
-      const int d = g->h_rp[v + 1] - g->h_rp[v];
-      if (d > bitmap_min_deg && !rf.skips(d)) big.push_back({d, v});
-    }
-    std::sort(big.begin(), big.end(), [](const std::pair<int, int> &x, const std::pair<int, int> &y) { return x.first > y.first; });
-    const size_t nb = words ? std::min<size_t>(big.size(), (size_t)(budget_bytes / (words * 4ull))) : 0;
-    if (nb > 0) {
-      std::vector<int> slot_of_row;  // sparse map through a sorted vector
-      std::vector<std::pair<int, int>> row_slot(nb);
-      std::vector<int> rows(nb);
-      for (size_t i = 0; i < nb; ++i) { row_slot[i] = {big[i].second, (int)i}; rows[i] = big[i].second; }
-      std::sort(row_slot.begin(), row_slot.end());
-      std::vector<int> slots(t.n, -1);
-      for (size_t c = 0; c < t.n; ++c) {
-        const ChunkRec &r = recs[c];
-        if (r.u_end == r.u_begin + 1 && (g->h_rp[r.u_begin + 1] - g->h_rp[r.u_begin]) > stage_cap) {
-          auto it = std::lower_bound(row_slot.begin(), row_slot.end(), std::make_pair(r.u_begin, -1));
-          if (it != row_slot.end() && it->first == r.u_begin) slots[c] = it->second;
-        }
-      }
-      HIP_TRY(t.d_slot.alloc(sizeof(int) * t.n));
-      HIP_TRY(hipMemcpy(t.d_slot, slots.data(), sizeof(int) * t.n, hipMemcpyHostToDevice));
-      {
-        std::vector<int> by_vertex((size_t)g->nv, -1);
-        for (size_t i = 0; i < nb; ++i) by_vertex[(size_t)rows[i]] = (int)i;
-        HIP_TRY(t.d_row_slot_mem.alloc(sizeof(int) * (size_t)g->nv));
-        t.d_row_slot = t.d_row_slot_mem;
-        HIP_TRY(hipMemcpy(t.d_row_slot, by_vertex.data(), sizeof(int) * (size_t)g->nv, hipMemcpyHostToDevice));
-      }
-      HIP_TRY(t.d_bitmaps_mem.alloc((size_t)nb * (size_t)words * 4));
-      t.d_bitmaps = t.d_bitmaps_mem;
-      HIP_TRY(hipMemset(t.d_bitmaps, 0, (size_t)nb * (size_t)words * 4));
-      DevOwn<int> d_rows;
-      HIP_TRY(d_rows.alloc(sizeof(int) * nb));
-      HIP_TRY(hipMemcpy(d_rows, rows.data(), sizeof(int) * nb, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(bitmap_build_kernel, dim3((unsigned)nb), dim3(256), 0, 0, g->d_rp, g->d_col, d_rows.get(), t.d_bitmaps, words);
-      hipError_t e = hipDeviceSynchronize();
-      d_rows.reset();
-      if (e != hipSuccess) return hip_fail(e, "bitmap_build_kernel", __FILE__, __LINE__);
-      t.n_bitmaps = nb;
-      t.bitmap_words = words;
-    }
-    bitmap_ms = bm_timer.ms();
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  if (gm_sweep_env("GM_TABLE_INFO")) {  // diagnostics
-    unsigned long long tc = 0, mx = 0;
-    for (auto c : t.cost) { tc += c; mx = std::max(mx, c); }
-    fprintf(stderr, "[table] stage_cap %d rows (%d,%d] skip (%d,%d]: %zu chunks, est. keys %.3e (max chunk %.3e), %zu bitmaps, edges %llu\n", stage_cap,
-            rf.only_lo, rf.only_hi, rf.skip_lo, rf.skip_hi, t.n, (double)tc, (double)mx, t.n_bitmaps, t.edge_prefix.empty() ? 0ull : t.edge_prefix.back());
-  }
+  HIP_TRY(hipSetDevice(g->device));
+  PoolScope pool(g);
+  int rc = build_table_device(g, t, sym_table, bitmap_ms);
+  if (rc) return rc;  // (what a partially built table owns goes back with `t`)
+  if (gm_sweep_env("GM_TABLE_INFO"))
+    fprintf(stderr, "[table/device] stage_cap %d rows (%d,%d] skip (%d,%d]: %zu chunks, est. keys %.3e, %zu bitmaps, edges %llu, %.2f ms\n",
+            stage_cap, rf.only_lo, rf.only_hi, rf.skip_lo, rf.skip_hi, t.n, (double)t.total_cost, t.n_bitmaps, t.total_edges, timer.ms());
   g->setup.bitmap_ms += bitmap_ms;
   g->setup.table_ms += timer.ms() - bitmap_ms;
   g->tables.push_back(std::move(t));
@@ -775,7 +613,7 @@ __global__ __launch_bounds__(256) void edesc_kernel(long long ne, const int *__r
 }
 
 // ---- task lists of gm_tch.hip / gm_tch.hip: every edge u -> v of the DAG is a task of ONE of its endpoints (ensure_tasklists, below) ------
-// ---- task-major copies of the short lists (gm_host.h: d_colk / d_tdesck) -- for the handles that cannot have the key stream -----------
+// ---- task-major copies of the short lists (gm_host.h: TaskLists::colk / tdesck) -- for the handles that cannot have the key stream -----------
 #ifndef GM_TC_INLINE_MAX_DEFAULT
 #define GM_TC_INLINE_MAX_DEFAULT 32
 #endif
@@ -803,11 +641,11 @@ __global__ __launch_bounds__(256) void inl_copy_kernel(long long nt, const int2 
     }
   }
 }
-// after d_tdesc: failures here leave the handle without copies (the kernels then stream the rows themselves)
-static void build_inline_copies(gm_graph *g, ScanTemp &tmp) {
+// after the lists, into the same local of ensure_tasklists: failures here leave the handle without copies (the kernels then stream the rows themselves)
+static void build_inline_copies(gm_graph *g, TaskLists &tl, ScanTemp &tmp) {
   int lmax = GM_TC_INLINE_MAX_DEFAULT;
   if (const char *e = gm_sweep_env("GM_TC_INLINE_MAX")) lmax = atoi(e);  // (sweeps; 0: no copies)
-  if (lmax <= 0 || g->ne <= 0 || g->d_tdesc == nullptr) return;
+  if (lmax <= 0 || g->ne <= 0 || tl.tdesc == nullptr) return;
   const long long nt = g->ne;
   DevOwn<unsigned long long> off;  // (lengths in, offsets out: the scan runs in place)
   DevOwn<int> colk;
@@ -817,7 +655,7 @@ static void build_inline_copies(gm_graph *g, ScanTemp &tmp) {
   const long long blocks = std::min<long long>((nt + 256) / 256, (long long)g->cu_count * 32);
   unsigned long long total = 0;
   for (;;) {  // the copies share the 32-bit index space of col[]: halve the limit until they fit
-    hipLaunchKernelGGL(inl_len_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, nt, g->d_tdesc, lmax, off.get());
+    hipLaunchKernelGGL(inl_len_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, nt, tl.tdesc.get(), lmax, off.get());
     if (dev_exclusive_sum(tmp, off.get(), off.get(), (size_t)nt + 1) != hipSuccess) return fail();
     if (hipMemcpy(&total, off + nt, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail();
     if ((unsigned long long)nt + total < 0x7fffff00ull) break;
@@ -829,12 +667,12 @@ static void build_inline_copies(gm_graph *g, ScanTemp &tmp) {
   if (colk.alloc(4 * ((size_t)nt + (size_t)total)) != hipSuccess) return fail();
   if (hipMemcpyAsync(colk, g->d_col, 4 * (size_t)nt, hipMemcpyDeviceToDevice, 0) != hipSuccess) return fail();
   const long long cblocks = std::min<long long>((nt * 8 + 255) / 256, (long long)g->cu_count * 64);
-  hipLaunchKernelGGL(inl_copy_kernel, dim3((unsigned)cblocks), dim3(256), 0, 0, nt, g->d_tdesc, off.get(), lmax, nt, colk.get(), tdk.get());
+  hipLaunchKernelGGL(inl_copy_kernel, dim3((unsigned)cblocks), dim3(256), 0, 0, nt, tl.tdesc.get(), off.get(), lmax, nt, colk.get(), tdk.get());
   if (hipDeviceSynchronize() != hipSuccess) return fail();
   off.reset();
-  g->d_colk = std::move(colk);
-  g->d_tdesck = std::move(tdk);
-  g->n_inline_keys = total;
+  tl.colk = std::move(colk);
+  tl.tdesck = std::move(tdk);
+  tl.n_copy_keys = total;
 }
 
 // The task lists by COUNTING PLACEMENT (round 4; until then: one (host, entry) key per edge found by a bisection of the offsets, a radix
@@ -1067,10 +905,6 @@ __global__ __launch_bounds__(256) void kst_narrow_kernel(int nv, const unsigned 
   if (v <= nv) out[v] = (int)in[v];
 }
 
-// d_kst / d_kst_rp / d_trpl / d_tdescl of a handle (gm_host.h): GM_OK also when the handle cannot have them (ids beyond 24 bits, keys
-// beyond the 32-bit index space at every list limit) -- *built says which
-// edges: with the entries the edge supports need (gm_host.h KeyStream): a handle whose stream was built without them gets a SECOND set of
-// keys / longer lists with them -- same offsets (the counts per host do not depend on the order of arrival), its own order.
 // the hub corner the triangle count takes on the matrix cores (gm_ctc.hip): its size on this handle -- the last h vertices, word-aligned in the
 // core bitmap -- or 0.  The masked product costs h^3 / 6 bit-products whatever the corner holds, the streamed kernel ~rho^2 h^3 / 8 keys for
 // a corner of density rho (|E| = rho h^2 / 2 edges, lists of rho h / 2 keys, half of a list streamed), so the corner pays from a density
@@ -1083,11 +917,12 @@ static int tc_core_size(gm_graph *g, const char *env = "GM_TC_CORE_H", bool bloc
   bool forced = false;
   if (const char *e = gm_opt(env)) { want = atoll(e); forced = true; }
   if (want <= 0 || g->nv < 64) return 0;
-  if (ensure_core_bitmap(g) != GM_OK || g->core_state != 1) return 0;  // (not topologically numbered, no room: everything through the stream)
-  const long long cap = std::min<long long>((long long)g->core_h, (long long)kCtcMaxH);
+  if (ensure_core_bitmap(g) != GM_OK || !g->core.built()) return 0;  // (not topologically numbered, no room: everything through the stream)
+  const long long core_h = g->core->h;
+  const long long cap = std::min<long long>(core_h, (long long)kCtcMaxH);
   auto aligned = [&](long long h) {  // the corner starts at a word of the bitmap's rows
-    const long long off = ((long long)g->core_h - h + 31) / 32 * 32;
-    return off >= g->core_h ? 0ll : (long long)g->core_h - off;
+    const long long off = (core_h - h + 31) / 32 * 32;
+    return off >= core_h ? 0ll : core_h - off;
   };
   if (forced) {
     const long long h = aligned(std::min(want, cap));
@@ -1177,13 +1012,13 @@ __global__ __launch_bounds__(256) void tc_pair_select_kernel(const int nb, const
   atomicAdd(&sums[2], (unsigned long long)edges[b]);
   atomicAdd(&sums[3], (unsigned long long)k);
 }
-// Decides the pairs of this handle (under g->mu, before the stream's count pass): tc_h = the base corner of the density rule (0: none).
-// Leaves g->tc_pair_region = 0 -- the full triangle of tc_h, as before -- when the corner is forced (GM_TC_CORE_H), switched off
+// Decides the pairs of the key stream `ks` being built (under g->mu, before the stream's count pass): tc_h = the base corner of the density rule (0: none).
+// Leaves ks.pair_region = 0 -- the full triangle of tc_h, as before -- when the corner is forced (GM_TC_CORE_H), switched off
 // (GM_TC_PAIRS=off), there is no base corner and no forced region, or the region cannot run on the block kernel.
 // GM_TC_PAIRS = rule | off | all | none | checker ((IB + JB) odd) | diag | offdiag (tests: the last five); GM_TC_PAIR_R = R of the rule;
 // GM_TC_PAIR_REGION = rows of the region whatever the density rule says (tests: small graphs)
-static int tc_pairs_setup(gm_graph *g, const TaskWalk &tw, const int tc_h) {
-  g->tc_pair_region = 0;
+static int tc_pairs_setup(gm_graph *g, KeyStream &ks, const TaskWalk &tw, const int tc_h) {
+  ks.pair_region = 0;
   const char *mode = gm_opt("GM_TC_PAIRS");
   if (!mode || !*mode) mode = "rule";
   const char *forced_region = gm_opt("GM_TC_PAIR_REGION");
@@ -1201,18 +1036,19 @@ static int tc_pairs_setup(gm_graph *g, const TaskWalk &tw, const int tc_h) {
     if (strtoll(e, &end, 10) < 0 || end == e || *end != '\0') return GM_ERR_INVALID;
   }
   if (kind == 6 || gm_opt("GM_TC_CORE_H") || (tc_h <= 0 && !forced_region)) return GM_OK;
-  if (g->core_state != 1 || g->d_core == nullptr || !tw.topo) return GM_OK;
+  if (!g->core.built() || !tw.topo) return GM_OK;
+  const int core_h = g->core->h;
   // the region: the largest multiple of 512 rows at the end of the core bitmap, at most a quarter of the vertices, starting where the block
   // kernel's 16-byte loads can (core_tc_fast_path)
-  long long region = std::min<long long>(std::min<long long>(g->core_h, kCtcMaxH), (long long)g->nv / 4) / 512 * 512;
+  long long region = std::min<long long>(std::min<long long>(core_h, kCtcMaxH), (long long)g->nv / 4) / 512 * 512;
   if (forced_region) region = region_want;
-  else while (region >= 512 && (g->core_h - region) % 128 != 0) region -= 512;
-  if (region < 512 || region % 512 != 0 || region > g->core_h || region > kCtcMaxH || region < tc_h) return GM_OK;
+  else while (region >= 512 && (core_h - region) % 128 != 0) region -= 512;
+  if (region < 512 || region % 512 != 0 || region > core_h || region > kCtcMaxH || region < tc_h) return GM_OK;
   CoreTcParams cp;
   memset(&cp, 0, sizeof cp);
-  cp.core = g->d_core;
-  cp.row_words = (g->core_h + 31) / 32;
-  cp.row0 = g->core_h - (int)region;
+  cp.core = g->core->bits;
+  cp.row_words = (core_h + 31) / 32;
+  cp.row0 = core_h - (int)region;
   cp.word0 = cp.row0 >> 5;
   cp.h = (int)region;
   if (cp.row0 % 32 != 0 || !core_tc_fast_path(cp)) return GM_OK;
@@ -1246,54 +1082,35 @@ static int tc_pairs_setup(gm_graph *g, const TaskWalk &tw, const int tc_h) {
     return std::min(cb + kCtcBPiece, nc) - cb;
   };
   std::stable_sort(tasks.begin(), tasks.end(), [&](const unsigned a, const unsigned b) { return chunks_of(a) > chunks_of(b); });
-  HIP_TRY(g->d_tc_pair_bits.alloc(sizeof(unsigned) * (size_t)nwords));
-  HIP_TRY(g->d_tc_pair_tasks.alloc(sizeof(unsigned) * std::max<size_t>(tasks.size(), 1)));
-  HIP_TRY(hipMemcpy(g->d_tc_pair_bits, bits, sizeof(unsigned) * (size_t)nwords, hipMemcpyHostToDevice));
-  if (!tasks.empty()) HIP_TRY(hipMemcpy(g->d_tc_pair_tasks, tasks.data(), sizeof(unsigned) * tasks.size(), hipMemcpyHostToDevice));
-  g->n_tc_pair_tasks = (int)tasks.size();
-  g->tc_pair_from = region_from;
+  HIP_TRY(ks.pair_bits.alloc(sizeof(unsigned) * (size_t)nwords));
+  HIP_TRY(ks.pair_tasks.alloc(sizeof(unsigned) * std::max<size_t>(tasks.size(), 1)));
+  HIP_TRY(hipMemcpy(ks.pair_bits, bits, sizeof(unsigned) * (size_t)nwords, hipMemcpyHostToDevice));
+  if (!tasks.empty()) HIP_TRY(hipMemcpy(ks.pair_tasks, tasks.data(), sizeof(unsigned) * tasks.size(), hipMemcpyHostToDevice));
+  ks.n_pair_tasks = (int)tasks.size();
+  ks.pair_from = region_from;
   const long long info[6] = {region, taken, possible, p_edges, p_keys, (long long)R};
-  for (int i = 0; i < 6; ++i) g->tc_pair_info[i] = info[i];
-  g->tc_pair_region = (int)region;
+  for (int i = 0; i < 6; ++i) ks.pair_info[i] = info[i];
+  ks.pair_region = (int)region;
   setup_trace("key stream: tasks of the product, uploads");
   return GM_OK;
 }
 
-int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
-  auto have = [&]() { return g->d_kst_rp != nullptr && (!edges || g->d_kst_et != nullptr); };
-  *built = have();
-  if (*built || g->kst_state == 2 || g->ne == 0) return GM_OK;
-  // (a stream without the hub corner's rows cannot carry the edge supports: they take the task lists)
-  if (edges && g->d_kst_rp != nullptr && g->kst_skip_from < g->nv) return GM_OK;
-  {
-    const int rc = ensure_edesc(g);  // (takes the lock itself)
-    if (rc) return rc;
-  }
-  const int tc_h = (allow_core && !edges && g->d_kst_rp == nullptr) ? tc_core_size(g) : 0;  // (takes the lock itself)
-  std::lock_guard<std::mutex> lk(g->mu);
-  *built = have();
-  if (*built || g->kst_state == 2) return GM_OK;
-  if (edges && g->d_kst_rp != nullptr && g->kst_skip_from < g->nv) return GM_OK;
-  const bool second = g->d_kst_rp != nullptr;  // the offsets exist: only the place pass, into the second set
-  int lmax = second ? g->kst_lmax : GM_TC_INLINE_MAX_DEFAULT;
+// One build of the key stream.  first == nullptr: the FIRST set into `ks` -- offsets, stream, longer lists, with the entries when `edges`,
+// with the hub corner / the block pairs when allow_core.  Else only the place pass over the offsets of *first, into the second set `ke`.
+// kOnceBuilt, kOnceNotApplicable (first set: this handle cannot have a stream) or an error code.  Under g->mu; `topo` from the caller.
+static int build_keystream(gm_graph *g, const bool edges, const bool allow_core, const int tc_h, bool topo, const KeyStream *first, KeyStream &ks, KeyEntries &ke) {
+  const bool second = first != nullptr;  // the offsets exist: only the place pass, into the second set
+  int lmax = second ? first->lmax : GM_TC_INLINE_MAX_DEFAULT;
   if (!second) {
     if (const char *e = gm_sweep_env("GM_TC_INLINE_MAX")) lmax = atoi(e);  // (sweeps)
-    if (!keystream_possible(g) || lmax < 4) {
-      g->kst_state = 2;
-      return GM_OK;
-    }
+    if (!keystream_possible(g) || lmax < 4) return kOnceNotApplicable;
   }
   SetupTimer timer;
   HIP_TRY(hipSetDevice(g->device));
   const size_t nv1 = (size_t)g->nv + 1;
   PoolScope pool(g);
   ScanTemp tmp;
-  bool topo = false;
-  {
-    const int rc = graph_is_topological(g, &topo);
-    if (rc) return rc;
-    if (gm_sweep_env("GM_TC_NO_TRIM")) topo = false;  // (A/B: whole lists streamed on a topologically numbered DAG too)
-  }
+  if (gm_sweep_env("GM_TC_NO_TRIM")) topo = false;  // (A/B: whole lists streamed on a topologically numbered DAG too)
   DevBuf<unsigned long long> cnt, keys, keyoff;
   DevBuf<int> longs;
   HIP_TRY(cnt.alloc(nv1));
@@ -1312,18 +1129,18 @@ int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
   const long long blocks_place = std::min<long long>(((long long)g->nv * 8 + 255) / 256, (long long)g->cu_count * per_cu_place);
   TaskWalk tw;
   tw.nv = g->nv; tw.stage_max = kTctStageMax; tw.topo = topo ? 1 : 0;
-  tw.rp = g->d_rp; tw.col = g->d_col; tw.edesc = g->d_edesc;
+  tw.rp = g->d_rp; tw.col = g->d_col; tw.edesc = *g->edesc;
   int skip_from = (!second && topo && tc_h > 0) ? g->nv - tc_h : 0x7fffffff;
   if (!second && allow_core && !edges) {  // the corner per pair of blocks: the stream leaves out the chosen pairs' edges instead of whole rows
-    if (const int rc = tc_pairs_setup(g, tw, skip_from < g->nv ? tc_h : 0)) return rc;
-    if (g->tc_pair_region > 0) {
-      tw.region_from = g->tc_pair_from;
-      tw.pair_nb = g->tc_pair_region / 256;
-      tw.pair_bits = g->d_tc_pair_bits;
-      if (skip_from >= g->nv) skip_from = g->tc_pair_from;  // (a forced region on a graph without a base corner: gm_tc_core_info names the region)
+    if (const int rc = tc_pairs_setup(g, ks, tw, skip_from < g->nv ? tc_h : 0)) return rc;
+    if (ks.pair_region > 0) {
+      tw.region_from = ks.pair_from;
+      tw.pair_nb = ks.pair_region / 256;
+      tw.pair_bits = ks.pair_bits;
+      if (skip_from >= g->nv) skip_from = ks.pair_from;  // (a forced region on a graph without a base corner: gm_tc_core_info names the region)
     }
   }
-  tw.skip_from = g->tc_pair_region > 0 ? 0x7fffffff : skip_from;
+  tw.skip_from = ks.pair_region > 0 ? 0x7fffffff : skip_from;
   long long core_edges = 0;
   if (skip_from < g->nv) {
     int e0 = 0;
@@ -1333,17 +1150,17 @@ int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
   TaskWalk tw_count = tw, tw_place = tw;
   tw_count.hub0 = topo ? std::max(0, g->nv - win_count) : g->nv;
   tw_place.hub0 = topo ? std::max(0, g->nv - win_place) : g->nv;
-  DevOwn<int> krp_new, trpl_new, tedgel;  // (what this call builds: handed to the handle at the end, given back on every other return)
+  DevOwn<int> krp_new, trpl_new, tedgel;  // (what this call builds: moved into ks / ke at the end, given back on every other return)
   DevOwn<unsigned> kst;
   DevOwn<int2> tdl, kst_et;
   auto fail = [](hipError_t e, const char *what) { return hip_fail(e, what, __FILE__, __LINE__); };
   hipError_t e = hipSuccess;
   if (!second && ((e = krp_new.alloc(sizeof(int) * nv1)) != hipSuccess || (e = trpl_new.alloc(sizeof(int) * nv1)) != hipSuccess)) return fail(e, "hipMalloc(key stream offsets)");
-  int *const krp = second ? g->d_kst_rp.get() : krp_new.get(), *const trpl = second ? g->d_trpl.get() : trpl_new.get();
+  int *const krp = second ? first->rp.get() : krp_new.get(), *const trpl = second ? first->trpl.get() : trpl_new.get();
   KstEdges ed{nullptr, nullptr};
-  unsigned long long total = second ? g->n_inline_keys : 0, key_limit = 0x7fffff00ull;
+  unsigned long long total = second ? first->n_keys : 0, key_limit = 0x7fffff00ull;
   if (const char *e = gm_opt("GM_KST_MAX_KEYS")) key_limit = std::min<unsigned long long>(key_limit, (unsigned long long)std::max(1ll, atoll(e)));  // (tests)
-  int nlong = second ? g->n_long_tasks : 0;
+  int nlong = second ? first->n_long_tasks : 0;
   while (!second) {  // the stream is indexed with 32 bits: halve the limit of a "short" list until it fits
     if ((e = hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * nv1, 0)) != hipSuccess) return fail(e, "hipMemsetAsync");
     if (win_count <= 2048) hipLaunchKernelGGL((kst_rows_kernel<false, 2048, false>), dim3((unsigned)blocks_count), dim3(256), 0, 0, tw_count, lmax, cnt.p, nullptr, nullptr, nullptr, nullptr, ed);
@@ -1356,8 +1173,8 @@ int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
     if (total < key_limit) break;
     lmax >>= 1;
     if (lmax < 4) {
-      g->kst_state = 2;
-      return GM_OK;
+      ks = KeyStream();
+      return kOnceNotApplicable;
     }
   }
   setup_trace("key stream: count pass + scans");
@@ -1381,35 +1198,70 @@ int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
   if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) return fail(e, "kst_rows_kernel");
   setup_trace("key stream: place pass");
   if (second) {  // (the first set stays what the triangle count reads)
-    g->d_kst2 = std::move(kst);
-    g->d_tdescl2 = std::move(tdl);
+    ke.kst2 = std::move(kst);
+    ke.tdescl2 = std::move(tdl);
+    ke.tedgel = std::move(tedgel);
+    ke.kst_et = std::move(kst_et);
   } else {
-    g->d_kst = std::move(kst);
-    g->d_trpl = std::move(trpl_new);
-    g->d_tdescl = std::move(tdl);
-    g->n_inline_keys = total;
-    g->n_long_tasks = nlong;
-    g->kst_lmax = lmax;
+    ks.kst = std::move(kst);
+    ks.rp = std::move(krp_new);
+    ks.trpl = std::move(trpl_new);
+    ks.tdescl = std::move(tdl);
+    ks.n_keys = total;
+    ks.n_long_tasks = nlong;
+    ks.lmax = lmax;
     if (skip_from < g->nv) {
-      g->tc_core_edges = core_edges;
-      g->tc_core_h = g->nv - skip_from;
-      g->kst_skip_from = skip_from;
+      ks.core_edges = core_edges;
+      ks.core_h = g->nv - skip_from;
+      ks.skip_from = skip_from;
+    }
+    if (edges) {
+      ks.tedgel = std::move(tedgel);
+      ks.kst_et = std::move(kst_et);
     }
   }
-  if (edges) {
-    g->d_tedgel = std::move(tedgel);
-    g->d_kst_et = std::move(kst_et);
-  }
-  if (!second) g->d_kst_rp = std::move(krp_new);
   g->setup.table_ms += timer.ms();
-  *built = true;
+  return kOnceBuilt;
+}
+
+// the KeyStream of a handle (gm_host.h): GM_OK also when the handle cannot have one (ids beyond 24 bits, keys beyond the 32-bit index space
+// at every list limit) -- *built says which.  edges: with the entries the edge supports need: a handle whose stream was built without them
+// gets a SECOND set of keys / longer lists with them (KeyEntries) -- same offsets (the counts per host do not depend on the order of
+// arrival), its own order
+int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core) {
+  auto have = [&]() { return g->kst.built() && (!edges || g->kst->kst_et != nullptr || g->kst_entries.built()); };
+  *built = have();
+  if (*built || g->ne == 0 || (g->kst.known() && !g->kst.built())) return GM_OK;
+  // (a stream without the hub corner's rows cannot carry the edge supports: they take the task lists)
+  if (edges && g->kst.built() && g->kst->skip_from < g->nv) return GM_OK;
+  {
+    const int rc = ensure_edesc(g);  // (takes the lock itself)
+    if (rc) return rc;
+  }
+  bool topo = false;
+  {
+    const int rc = graph_is_topological(g, &topo);  // (takes the lock itself)
+    if (rc) return rc;
+  }
+  if (!g->kst.known()) {
+    const int tc_h = (allow_core && !edges) ? tc_core_size(g) : 0;  // (takes the lock itself)
+    KeyEntries none;
+    const int rc = g->kst.ensure(g->mu, [&](KeyStream &ks) { return build_keystream(g, edges, allow_core, tc_h, topo, nullptr, ks, none); });
+    if (rc) return rc;
+  }
+  if (edges && g->kst.built() && g->kst->kst_et == nullptr && g->kst->skip_from >= g->nv) {  // built without the entries: the second set
+    KeyStream none;
+    const int rc = g->kst_entries.ensure(g->mu, [&](KeyEntries &ke) { return build_keystream(g, true, false, 0, topo, &*g->kst, none, ke); });
+    if (rc) return rc;
+  }
+  *built = have();
   return GM_OK;
 }
 
-int ensure_tasklists(gm_graph *g, bool /*with_edges*/) {
+int ensure_tasklists(gm_graph *g) {
   // The tasks' own entries (tedge, 4 B per edge: what the edge supports need) are always built with the lists.  Round 3 built them on
   // demand by freeing and rebuilding trp / tdesc -- under a launch of another thread that had already copied those pointers.
-  if (__atomic_load_n(&g->d_tdesc, __ATOMIC_ACQUIRE) || g->ne == 0) return GM_OK;
+  if (g->tasklists.known() || g->ne == 0) return GM_OK;
   {
     const int rc = ensure_edesc(g);  // (takes the lock itself)
     if (rc) return rc;
@@ -1417,65 +1269,58 @@ int ensure_tasklists(gm_graph *g, bool /*with_edges*/) {
   // the hub corner (gm_ctc.hip): its edges' supports / triangles come from the matrix cores -- where every row fits the stage (the rows beyond
   // it are the chunked kernel's, run_pattern) and the corner is a whole number of 512-vertex chunks
   const int tl_h = g->max_deg <= kTctStageMax ? tc_core_size(g, "GM_SUP_CORE_H", true) : 0;  // (takes the lock itself)
-  std::lock_guard<std::mutex> lk(g->mu);
-  if (g->d_tdesc) return GM_OK;
-  SetupTimer timer;
-  HIP_TRY(hipSetDevice(g->device));
-  const size_t ne = (size_t)g->ne, nv1 = (size_t)g->nv + 1;
-  PoolScope pool(g);
-  DevBuf<int> cnt;
-  ScanTemp tmp;
   bool topo = false;
   {
-    const int rc = graph_is_topological(g, &topo);
+    const int rc = graph_is_topological(g, &topo);  // (takes the lock itself)
     if (rc) return rc;
     if (gm_sweep_env("GM_TC_NO_TRIM")) topo = false;  // (A/B: whole lists streamed on a topologically numbered DAG too)
   }
-  setup_trace("tasks: sorted / topological check");
-  HIP_TRY(cnt.alloc(nv1));
-  HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(int) * nv1, 0));
-  // (few, fat workgroups: a workgroup's LDS histogram of the hub hosts pays when it sees many rows)
-  // (where no hub window exists -- a DAG that is not numbered topologically -- many thin workgroups: power-law LJ-size 30.9 vs 9.8 ms)
-  const long long blocks = std::min<long long>(((long long)g->nv * 8 + 255) / 256, (long long)g->cu_count * (topo ? 8 : 64));
-  TaskWalk tw;
-  tw.nv = g->nv; tw.stage_max = kTctStageMax; tw.topo = topo ? 1 : 0;
-  tw.hub0 = topo ? std::max(0, g->nv - kHubWin) : g->nv;
-  tw.rp = g->d_rp; tw.col = g->d_col; tw.edesc = g->d_edesc;
-  const int tl_skip = (topo && tl_h > 0) ? g->nv - tl_h : 0x7fffffff;
-  tw.skip_from = tl_skip;
-  hipLaunchKernelGGL((task_rows_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, 0, tw, cnt.p, nullptr, nullptr, nullptr);
-  setup_trace("tasks: count pass");
-  DevOwn<int> trp, tedge;
-  DevOwn<int2> td;
-  HIP_TRY(trp.alloc(sizeof(int) * nv1));
-  hipError_t e = dev_exclusive_sum(tmp, cnt.p, trp.get(), nv1);
-  if (e == hipSuccess) e = td.alloc(sizeof(int2) * ne);
-  if (e == hipSuccess) e = tedge.alloc(sizeof(int) * ne);
-  if (e == hipSuccess) e = hipMemsetAsync(td, 0, sizeof(int2) * ne, 0);  // (the edges of rows beyond the stage are no tasks: empty descriptors at the end)
-  if (e == hipSuccess) e = hipMemsetAsync(tedge, 0, sizeof(int) * ne, 0);
-  if (e == hipSuccess) e = hipMemsetAsync(cnt.p, 0, sizeof(int) * nv1, 0);
-  setup_trace("tasks: scan, allocations, clears");
-  if (e == hipSuccess) {
-    const long long pblocks = std::min<long long>(((long long)g->nv * 8 + 255) / 256, (long long)g->cu_count * (topo ? 16 : 64));  // (the place pass waits for its returning atomics)
-    hipLaunchKernelGGL((task_rows_kernel<true>), dim3((unsigned)pblocks), dim3(256), 0, 0, tw, cnt.p, trp.get(), td.get(), tedge.get());
-    e = hipDeviceSynchronize();
-  }
-  if (e != hipSuccess) return hip_fail(e, "task lists", __FILE__, __LINE__);
-  if (tl_skip < g->nv) {
-    g->tl_skip_from = tl_skip;
-    g->tl_core_h = g->nv - tl_skip;
-  }
-  g->d_trp = std::move(trp);
-  g->d_tedge = std::move(tedge);
-  g->d_tdesc_mem = std::move(td);
-  // d_tdesc is what the lock-free check at the top reads: published LAST, with release order, so that a first caller on another thread
-  // that sees it also sees the corner's skip row and the other arrays
-  __atomic_store_n(&g->d_tdesc, g->d_tdesc_mem.get(), __ATOMIC_RELEASE);
-  setup_trace("tasks: place pass");
-  if (!keystream_possible(g)) build_inline_copies(g, tmp);  // (a handle that cannot have the key stream: task-major copies of the short lists)
-  setup_trace("tasks: inline copies");
-  g->setup.table_ms += timer.ms();
-  return GM_OK;
+  // (the lists, the corner's skip row and the inline copies reach a first caller on another thread together: ADVICE r5)
+  return g->tasklists.ensure(g->mu, [&](TaskLists &tl) {
+    SetupTimer timer;
+    HIP_TRY(hipSetDevice(g->device));
+    const size_t ne = (size_t)g->ne, nv1 = (size_t)g->nv + 1;
+    PoolScope pool(g);
+    DevBuf<int> cnt;
+    ScanTemp tmp;
+    setup_trace("tasks: sorted / topological check");
+    HIP_TRY(cnt.alloc(nv1));
+    HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(int) * nv1, 0));
+    // (few, fat workgroups: a workgroup's LDS histogram of the hub hosts pays when it sees many rows)
+    // (where no hub window exists -- a DAG that is not numbered topologically -- many thin workgroups: power-law LJ-size 30.9 vs 9.8 ms)
+    const long long blocks = std::min<long long>(((long long)g->nv * 8 + 255) / 256, (long long)g->cu_count * (topo ? 8 : 64));
+    TaskWalk tw;
+    tw.nv = g->nv; tw.stage_max = kTctStageMax; tw.topo = topo ? 1 : 0;
+    tw.hub0 = topo ? std::max(0, g->nv - kHubWin) : g->nv;
+    tw.rp = g->d_rp; tw.col = g->d_col; tw.edesc = *g->edesc;
+    const int tl_skip = (topo && tl_h > 0) ? g->nv - tl_h : 0x7fffffff;
+    tw.skip_from = tl_skip;
+    hipLaunchKernelGGL((task_rows_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, 0, tw, cnt.p, nullptr, nullptr, nullptr);
+    setup_trace("tasks: count pass");
+    HIP_TRY(tl.trp.alloc(sizeof(int) * nv1));
+    hipError_t e = dev_exclusive_sum(tmp, cnt.p, tl.trp.get(), nv1);
+    if (e == hipSuccess) e = tl.tdesc.alloc(sizeof(int2) * ne);
+    if (e == hipSuccess) e = tl.tedge.alloc(sizeof(int) * ne);
+    if (e == hipSuccess) e = hipMemsetAsync(tl.tdesc, 0, sizeof(int2) * ne, 0);  // (the edges of rows beyond the stage are no tasks: empty descriptors at the end)
+    if (e == hipSuccess) e = hipMemsetAsync(tl.tedge, 0, sizeof(int) * ne, 0);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt.p, 0, sizeof(int) * nv1, 0);
+    setup_trace("tasks: scan, allocations, clears");
+    if (e == hipSuccess) {
+      const long long pblocks = std::min<long long>(((long long)g->nv * 8 + 255) / 256, (long long)g->cu_count * (topo ? 16 : 64));  // (the place pass waits for its returning atomics)
+      hipLaunchKernelGGL((task_rows_kernel<true>), dim3((unsigned)pblocks), dim3(256), 0, 0, tw, cnt.p, tl.trp.get(), tl.tdesc.get(), tl.tedge.get());
+      e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess) return hip_fail(e, "task lists", __FILE__, __LINE__);
+    if (tl_skip < g->nv) {
+      tl.skip_from = tl_skip;
+      tl.core_h = g->nv - tl_skip;
+    }
+    setup_trace("tasks: place pass");
+    if (!keystream_possible(g)) build_inline_copies(g, tl, tmp);  // (a handle that cannot have the key stream: task-major copies of the short lists)
+    setup_trace("tasks: inline copies");
+    g->setup.table_ms += timer.ms();
+    return kOnceBuilt;
+  });
 }
 
 // ---- MATCH MASKS of the edge supports (gm_sup.hip, round 5).  An IN-EDGE task -- the target v = s_i of u -> v hosts, the tail
@@ -1517,163 +1362,150 @@ __global__ __launch_bounds__(256) void sup_far_list_kernel(const int nv, const i
   if (k < nv && flag[k]) rows[pos[k]] = nv - 1 - k;
 }
 
-// d_csym / d_cfirst: the symmetric bit matrix of the hub corner the task lists leave out, and the positions the supports' epilogue needs
+// SupCorner: the symmetric bit matrix of the hub corner the task lists leave out, and the positions the supports' epilogue needs
 int ensure_sup_corner(gm_graph *g) {
-  if (g->tl_skip_from >= g->nv || g->d_csym) return GM_OK;
-  std::lock_guard<std::mutex> lk(g->mu);
-  if (g->d_csym) return GM_OK;
-  SetupTimer timer;
-  HIP_TRY(hipSetDevice(g->device));
-  const int h = g->tl_core_h, words = h / 32;
-  const size_t cells = (size_t)h * (size_t)words;
-  DevOwn<unsigned> bits;
-  DevOwn<unsigned short> first_pos;
-  HIP_TRY(bits.alloc(cells * sizeof(unsigned)));
-  hipError_t e = first_pos.alloc(cells * sizeof(unsigned short));
-  if (e == hipSuccess) e = hipMemsetAsync(bits, 0, cells * sizeof(unsigned), 0);
-  if (e == hipSuccess) e = hipMemsetAsync(first_pos, 0, cells * sizeof(unsigned short), 0);
-  int e0 = 0;
-  if (e == hipSuccess) e = hipMemcpy(&e0, g->d_rp + g->tl_skip_from, sizeof(int), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = launch_core_sym_fill(g->nv, g->tl_skip_from, words, (long long)e0, g->ne, g->d_rp, g->d_col, bits, first_pos, g->cu_count, 0);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) return hip_fail(e, "symmetric corner", __FILE__, __LINE__);
-  g->d_cfirst = std::move(first_pos);
-  g->d_csym = std::move(bits);
-  setup_trace("supports: symmetric corner");
-  g->setup.table_ms += timer.ms();
-  return GM_OK;
+  const TaskLists &tl = *g->tasklists;
+  if (tl.skip_from >= g->nv) return GM_OK;
+  return g->sup_corner.ensure(g->mu, [&](SupCorner &sc) {
+    SetupTimer timer;
+    HIP_TRY(hipSetDevice(g->device));
+    const int h = tl.core_h, words = h / 32;
+    const size_t cells = (size_t)h * (size_t)words;
+    HIP_TRY(sc.csym.alloc(cells * sizeof(unsigned)));
+    hipError_t e = sc.cfirst.alloc(cells * sizeof(unsigned short));
+    if (e == hipSuccess) e = hipMemsetAsync(sc.csym, 0, cells * sizeof(unsigned), 0);
+    if (e == hipSuccess) e = hipMemsetAsync(sc.cfirst, 0, cells * sizeof(unsigned short), 0);
+    int e0 = 0;
+    if (e == hipSuccess) e = hipMemcpy(&e0, g->d_rp + tl.skip_from, sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = launch_core_sym_fill(g->nv, tl.skip_from, words, (long long)e0, g->ne, g->d_rp, g->d_col, sc.csym, sc.cfirst, g->cu_count, 0);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "symmetric corner", __FILE__, __LINE__);
+    setup_trace("supports: symmetric corner");
+    g->setup.table_ms += timer.ms();
+    return kOnceBuilt;
+  });
 }
 
 // the shortest tail that gets a mask on this handle: kSupMaskMinTail, or the option GM_SUP_MASK_MIN as it stood when the handle's masks
 // were laid out (ensure_sup_masks) -- the kernels must use the value the offsets were built with
-int sup_mask_min_tail(const gm_graph *g) { return g->smask_min_tail > 0 ? g->smask_min_tail : kSupMaskMinTail; }
+int sup_mask_min_tail(const gm_graph *g) { return g->sup_masks->min_tail > 0 ? g->sup_masks->min_tail : kSupMaskMinTail; }
 
 int ensure_sup_masks(gm_graph *g) {
-  if (g->smask_state != 0) return GM_OK;
-  if (!g->d_tdesc || !g->d_tedge || !g->d_edesc) return GM_ERR_INVALID;  // (after ensure_tasklists)
+  if (g->sup_masks.known()) return GM_OK;
+  const TaskLists &tl = *g->tasklists;
+  if (!tl.tdesc || !tl.tedge || !*g->edesc) return GM_ERR_INVALID;  // (after ensure_tasklists)
   bool topo = false;
   {
-    const int rc = graph_is_topological(g, &topo);
+    const int rc = graph_is_topological(g, &topo);  // (takes the lock itself)
     if (rc) return rc;
   }
-  std::lock_guard<std::mutex> lk(g->mu);
-  if (g->smask_state != 0) return GM_OK;
-  if (!topo || gm_sweep_env("GM_TC_NO_TRIM") || gm_opt("GM_SUP_NO_MASKS") || g->ne < 1) {  // (tails exist on a topologically numbered DAG only)
-    g->smask_state = 2;
-    return GM_OK;
-  }
-  if (const char *e = gm_opt("GM_SUP_MASK_MIN")) g->smask_min_tail = std::max(1, atoi(e));
-  SetupTimer timer;
-  HIP_TRY(hipSetDevice(g->device));
-  const size_t ne = (size_t)g->ne;
-  PoolScope pool(g);
-  DevBuf<unsigned long long> off;
-  ScanTemp tmp;
-  HIP_TRY(off.alloc(ne + 1));
-  HIP_TRY(hipMemsetAsync(off.p, 0, sizeof(unsigned long long) * (ne + 1), 0));
-  TaskWalk tw;
-  tw.nv = g->nv; tw.stage_max = kTctStageMax; tw.topo = 1; tw.hub0 = g->nv;
-  tw.rp = g->d_rp; tw.col = g->d_col; tw.edesc = g->d_edesc;
-  tw.skip_from = g->tl_skip_from;  // (the corner's rows have no tasks: no masks)
-  const long long blocks = std::min<long long>(((long long)g->nv * 8 + 255) / 256, (long long)g->cu_count * 32);
-  hipLaunchKernelGGL(sup_mask_size_kernel, dim3((unsigned)std::max<long long>(1, blocks)), dim3(256), 0, 0, tw, sup_mask_min_tail(g), off.p);
-  HIP_TRY(dev_exclusive_sum(tmp, off.p, off.p, ne + 1));
-  unsigned long long total = 0;
-  HIP_TRY(hipMemcpy(&total, off.p + ne, sizeof total, hipMemcpyDeviceToHost));
-  setup_trace("support masks: sizes + scan");
-  if (total == 0 || total >= (unsigned long long)kNoMask) {
-    g->smask_state = 2;
+  return g->sup_masks.ensure(g->mu, [&](SupMasks &sm) {
+    if (!topo || gm_sweep_env("GM_TC_NO_TRIM") || gm_opt("GM_SUP_NO_MASKS") || g->ne < 1) return kOnceNotApplicable;  // (tails exist on a topologically numbered DAG only)
+    if (const char *e = gm_opt("GM_SUP_MASK_MIN")) sm.min_tail = std::max(1, atoi(e));
+    const int lmin = sm.min_tail > 0 ? sm.min_tail : kSupMaskMinTail;
+    SetupTimer timer;
+    HIP_TRY(hipSetDevice(g->device));
+    const size_t ne = (size_t)g->ne;
+    PoolScope pool(g);
+    DevBuf<unsigned long long> off;
+    ScanTemp tmp;
+    HIP_TRY(off.alloc(ne + 1));
+    HIP_TRY(hipMemsetAsync(off.p, 0, sizeof(unsigned long long) * (ne + 1), 0));
+    TaskWalk tw;
+    tw.nv = g->nv; tw.stage_max = kTctStageMax; tw.topo = 1; tw.hub0 = g->nv;
+    tw.rp = g->d_rp; tw.col = g->d_col; tw.edesc = *g->edesc;
+    tw.skip_from = tl.skip_from;  // (the corner's rows have no tasks: no masks)
+    const long long blocks = std::min<long long>(((long long)g->nv * 8 + 255) / 256, (long long)g->cu_count * 32);
+    hipLaunchKernelGGL(sup_mask_size_kernel, dim3((unsigned)std::max<long long>(1, blocks)), dim3(256), 0, 0, tw, lmin, off.p);
+    HIP_TRY(dev_exclusive_sum(tmp, off.p, off.p, ne + 1));
+    unsigned long long total = 0;
+    HIP_TRY(hipMemcpy(&total, off.p + ne, sizeof total, hipMemcpyDeviceToHost));
+    setup_trace("support masks: sizes + scan");
+    if (total == 0 || total >= (unsigned long long)kNoMask) {
+      g->setup.table_ms += timer.ms();
+      return kOnceNotApplicable;
+    }
+    // the rows that have a second mask word, from the top of the id range
+    DevBuf<int> fflag, fpos;
+    HIP_TRY(fflag.alloc((size_t)g->nv + 1));
+    HIP_TRY(fpos.alloc((size_t)g->nv + 1));
+    HIP_TRY(hipMemsetAsync(fflag.p, 0, sizeof(int) * ((size_t)g->nv + 1), 0));
+    hipLaunchKernelGGL(sup_far_flag_kernel, dim3((unsigned)((g->nv + 255) / 256)), dim3(256), 0, 0, g->nv, g->d_rp, lmin, kTctStageMax, tl.skip_from, fflag.p);
+    HIP_TRY(dev_exclusive_sum(tmp, fflag.p, fpos.p, (size_t)g->nv + 1));
+    int nfar = 0;
+    HIP_TRY(hipMemcpy(&nfar, fpos.p + g->nv, sizeof nfar, hipMemcpyDeviceToHost));
+    hipError_t e = sm.emoff.alloc(sizeof(unsigned) * ne);
+    if (e == hipSuccess) e = sm.far_rows.alloc(sizeof(int) * (size_t)std::max(nfar, 1));
+    if (e == hipSuccess) hipLaunchKernelGGL(sup_far_list_kernel, dim3((unsigned)((g->nv + 255) / 256)), dim3(256), 0, 0, g->nv, fflag.p, fpos.p, sm.far_rows.get());
+    if (e == hipSuccess) e = sm.tmoff.alloc(sizeof(unsigned) * ne);
+    if (e == hipSuccess) e = sm.smask.alloc(sizeof(unsigned long long) * (size_t)total);
+    // (every launch rewrites the words of the tasks it runs; a launch that leaves masked tasks out -- a chunk filter, an aborted launch --
+    // must find zeros, not what hipMalloc handed over: ADVICE r5)
+    if (e == hipSuccess) e = hipMemsetAsync(sm.smask, 0, sizeof(unsigned long long) * (size_t)total, 0);
+    if (e == hipSuccess) {
+      const long long eb = std::min<long long>(((long long)ne + 255) / 256, (long long)g->cu_count * 32);
+      hipLaunchKernelGGL(sup_mask_off_kernel, dim3((unsigned)eb), dim3(256), 0, 0, (long long)ne, off.p, sm.emoff.get());
+      hipLaunchKernelGGL(sup_mask_task_kernel, dim3((unsigned)eb), dim3(256), 0, 0, (long long)ne, tl.tdesc.get(), tl.tedge.get(), sm.emoff.get(), sm.tmoff.get());
+      e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess) {  // (an optimisation that did not fit: the atomics stay)
+      (void)hipGetLastError();
+      const int min_tail = sm.min_tail;
+      sm = SupMasks();
+      sm.min_tail = min_tail;
+      g->setup.table_ms += timer.ms();
+      return kOnceNotApplicable;
+    }
+    sm.n_far_rows = nfar;
+    sm.words = total;
+    setup_trace("support masks: offsets");
     g->setup.table_ms += timer.ms();
-    return GM_OK;
-  }
-  // the rows that have a second mask word, from the top of the id range
-  DevBuf<int> fflag, fpos;
-  HIP_TRY(fflag.alloc((size_t)g->nv + 1));
-  HIP_TRY(fpos.alloc((size_t)g->nv + 1));
-  HIP_TRY(hipMemsetAsync(fflag.p, 0, sizeof(int) * ((size_t)g->nv + 1), 0));
-  hipLaunchKernelGGL(sup_far_flag_kernel, dim3((unsigned)((g->nv + 255) / 256)), dim3(256), 0, 0, g->nv, g->d_rp, sup_mask_min_tail(g), kTctStageMax, g->tl_skip_from, fflag.p);
-  HIP_TRY(dev_exclusive_sum(tmp, fflag.p, fpos.p, (size_t)g->nv + 1));
-  int nfar = 0;
-  HIP_TRY(hipMemcpy(&nfar, fpos.p + g->nv, sizeof nfar, hipMemcpyDeviceToHost));
-  DevOwn<unsigned> emoff, tmoff;
-  DevOwn<unsigned long long> arena;
-  DevOwn<int> far_rows;
-  hipError_t e = emoff.alloc(sizeof(unsigned) * ne);
-  if (e == hipSuccess) e = far_rows.alloc(sizeof(int) * (size_t)std::max(nfar, 1));
-  if (e == hipSuccess) hipLaunchKernelGGL(sup_far_list_kernel, dim3((unsigned)((g->nv + 255) / 256)), dim3(256), 0, 0, g->nv, fflag.p, fpos.p, far_rows.get());
-  if (e == hipSuccess) e = tmoff.alloc(sizeof(unsigned) * ne);
-  if (e == hipSuccess) e = arena.alloc(sizeof(unsigned long long) * (size_t)total);
-  // (every launch rewrites the words of the tasks it runs; a launch that leaves masked tasks out -- a chunk filter, an aborted launch --
-  // must find zeros, not what hipMalloc handed over: ADVICE r5)
-  if (e == hipSuccess) e = hipMemsetAsync(arena, 0, sizeof(unsigned long long) * (size_t)total, 0);
-  if (e == hipSuccess) {
-    const long long eb = std::min<long long>(((long long)ne + 255) / 256, (long long)g->cu_count * 32);
-    hipLaunchKernelGGL(sup_mask_off_kernel, dim3((unsigned)eb), dim3(256), 0, 0, (long long)ne, off.p, emoff.get());
-    hipLaunchKernelGGL(sup_mask_task_kernel, dim3((unsigned)eb), dim3(256), 0, 0, (long long)ne, g->d_tdesc, g->d_tedge, emoff.get(), tmoff.get());
-    e = hipDeviceSynchronize();
-  }
-  if (e != hipSuccess) {  // (an optimisation that did not fit: the atomics stay)
-    (void)hipGetLastError();
-    g->smask_state = 2;
-    g->setup.table_ms += timer.ms();
-    return GM_OK;
-  }
-  g->d_emoff = std::move(emoff);
-  g->d_tmoff = std::move(tmoff);
-  g->d_smask = std::move(arena);
-  g->d_sup_far_rows = std::move(far_rows);
-  g->n_sup_far_rows = nfar;
-  g->smask_words = total;
-  g->smask_state = 1;
-  setup_trace("support masks: offsets");
-  g->setup.table_ms += timer.ms();
-  return GM_OK;
+    return kOnceBuilt;
+  });
 }
 
 // the rows beyond the stage of the task-list kernels: a handful per graph, found on the host copy of the offsets
 int ensure_long_rows(gm_graph *g) {
-  if (g->n_long_rows >= 0) return GM_OK;
+  if (g->long_rows.known()) return GM_OK;
   const std::vector<int> *rp = nullptr;
-  int rc = host_rp(g, &rp);
+  int rc = host_rp(g, &rp);  // (takes the lock itself)
   if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g->mu);
-  if (g->n_long_rows >= 0) return GM_OK;
-  std::vector<int> rows;
-  std::vector<long long> prefix(1, 0);
-  for (int v = 0; v < g->nv; ++v) {
-    const int d = (*rp)[(size_t)v + 1] - (*rp)[(size_t)v];
-    if (d > kTctStageMax) {
-      rows.push_back(v);
-      prefix.push_back(prefix.back() + d);
+  return g->long_rows.ensure(g->mu, [&](LongRows &lr) {
+    std::vector<int> rows;
+    std::vector<long long> prefix(1, 0);
+    for (int v = 0; v < g->nv; ++v) {
+      const int d = (*rp)[(size_t)v + 1] - (*rp)[(size_t)v];
+      if (d > kTctStageMax) {
+        rows.push_back(v);
+        prefix.push_back(prefix.back() + d);
+      }
     }
-  }
-  if (!rows.empty()) {
-    HIP_TRY(hipSetDevice(g->device));
-    HIP_TRY(g->d_long_rows.alloc(sizeof(int) * rows.size()));
-    HIP_TRY(g->d_long_prefix.alloc(sizeof(long long) * prefix.size()));
-    HIP_TRY(copy_to_device(g->d_long_rows, rows.data(), sizeof(int) * rows.size()));
-    HIP_TRY(copy_to_device(g->d_long_prefix, prefix.data(), sizeof(long long) * prefix.size()));
-  }
-  g->long_edges = prefix.back();
-  g->n_long_rows = (int)rows.size();
-  return GM_OK;
+    if (!rows.empty()) {
+      HIP_TRY(hipSetDevice(g->device));
+      HIP_TRY(lr.rows.alloc(sizeof(int) * rows.size()));
+      HIP_TRY(lr.prefix.alloc(sizeof(long long) * prefix.size()));
+      HIP_TRY(copy_to_device(lr.rows, rows.data(), sizeof(int) * rows.size()));
+      HIP_TRY(copy_to_device(lr.prefix, prefix.data(), sizeof(long long) * prefix.size()));
+    }
+    lr.edges = prefix.back();
+    lr.n = (int)rows.size();
+    return kOnceBuilt;
+  });
 }
 
 int ensure_edesc(gm_graph *g) {
-  if (g->d_edesc || g->ne == 0) return GM_OK;
-  std::lock_guard<std::mutex> lk(g->mu);
-  if (g->d_edesc) return GM_OK;
-  SetupTimer timer;
-  DevOwn<int2> d;
-  HIP_TRY(d.alloc(sizeof(int2) * (size_t)g->ne));
-  const long long blocks = std::min<long long>((g->ne + 255) / 256, (long long)g->cu_count * 32);
-  hipLaunchKernelGGL(edesc_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, g->ne, g->d_rp, g->d_col, d.get());
-  hipError_t e = hipDeviceSynchronize();
-  setup_trace("edge descriptors");
-  if (e != hipSuccess) return hip_fail(e, "edesc_kernel", __FILE__, __LINE__);
-  g->d_edesc = std::move(d);
-  g->setup.table_ms += timer.ms();
-  return GM_OK;
+  if (g->ne == 0) return GM_OK;
+  return g->edesc.ensure(g->mu, [&](DevOwn<int2> &d) {
+    SetupTimer timer;
+    HIP_TRY(d.alloc(sizeof(int2) * (size_t)g->ne));
+    const long long blocks = std::min<long long>((g->ne + 255) / 256, (long long)g->cu_count * 32);
+    hipLaunchKernelGGL(edesc_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, g->ne, g->d_rp, g->d_col, d.get());
+    hipError_t e = hipDeviceSynchronize();
+    setup_trace("edge descriptors");
+    if (e != hipSuccess) return hip_fail(e, "edesc_kernel", __FILE__, __LINE__);
+    g->setup.table_ms += timer.ms();
+    return kOnceBuilt;
+  });
 }
 
 // k-clique (k = 4): the plan of one rank's share for the re-hosted first level (gm_mine.h, gm_cbuild.hip). Everything below runs on
@@ -1851,46 +1683,41 @@ __global__ __launch_bounds__(256) void core_fill_kernel(int nv, int base, int wo
   }
 }
 int ensure_core_bitmap(gm_graph *g) {
-  if (g->core_state) return GM_OK;
+  if (g->core.known()) return GM_OK;
   bool topo = false;
-  int rc = graph_is_topological(g, &topo);
+  int rc = graph_is_topological(g, &topo);  // (takes the lock itself)
   if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g->mu);
-  if (g->core_state) return GM_OK;
-  long long want = kCoreHDefault;
-  if (const char *e = gm_sweep_env("GM_CORE_H")) want = atoll(e);  // (sweeps; 0 switches the gathered build off)
-  if (!topo || g->d_rp == nullptr || g->nv < 64 || want < 64) {
-    g->core_state = 2;
-    return GM_OK;
-  }
-  SetupTimer timer;
-  HIP_TRY(hipSetDevice(g->device));
-  const int h = (int)std::min<long long>((long long)g->nv, want);
-  const int base = g->nv - h;
-  const int words = (h + 31) / 32;
-  const size_t bytes = (size_t)h * (size_t)words * 4;
-  if (g->d_core.alloc(bytes) != hipSuccess) {  // no room: the streamed build does everything
-    (void)hipGetLastError();
-    g->core_state = 2;
-    return GM_OK;
-  }
-  HIP_TRY(hipMemsetAsync(g->d_core, 0, bytes, 0));
-  int e01[2] = {0, 0};
-  HIP_TRY(hipMemcpy(&e01[0], g->d_rp + base, sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&e01[1], g->d_rp + g->nv, sizeof(int), hipMemcpyDeviceToHost));
-  const long long n = (long long)e01[1] - e01[0];
-  if (n > 0) {
-    const long long blocks = std::min<long long>((n + 255) / 256, (long long)g->cu_count * 32);
-    hipLaunchKernelGGL(core_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, g->nv, base, words, (long long)e01[0], (long long)e01[1], g->d_rp, g->d_col, g->d_core);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  g->core_h = h;
-  g->core_base = base;
-  setup_trace("clique: core bitmap");
-  g->core_state = 1;
-  g->setup.table_ms += timer.ms();
-  return GM_OK;
+  return g->core.ensure(g->mu, [&](HubCore &c) {
+    long long want = kCoreHDefault;
+    if (const char *e = gm_sweep_env("GM_CORE_H")) want = atoll(e);  // (sweeps; 0 switches the gathered build off)
+    if (!topo || g->d_rp == nullptr || g->nv < 64 || want < 64) return kOnceNotApplicable;
+    SetupTimer timer;
+    HIP_TRY(hipSetDevice(g->device));
+    const int h = (int)std::min<long long>((long long)g->nv, want);
+    const int base = g->nv - h;
+    const int words = (h + 31) / 32;
+    const size_t bytes = (size_t)h * (size_t)words * 4;
+    if (c.bits.alloc(bytes) != hipSuccess) {  // no room: the streamed build does everything
+      (void)hipGetLastError();
+      return kOnceNotApplicable;
+    }
+    HIP_TRY(hipMemsetAsync(c.bits, 0, bytes, 0));
+    int e01[2] = {0, 0};
+    HIP_TRY(hipMemcpy(&e01[0], g->d_rp + base, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&e01[1], g->d_rp + g->nv, sizeof(int), hipMemcpyDeviceToHost));
+    const long long n = (long long)e01[1] - e01[0];
+    if (n > 0) {
+      const long long blocks = std::min<long long>((n + 255) / 256, (long long)g->cu_count * 32);
+      hipLaunchKernelGGL(core_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, g->nv, base, words, (long long)e01[0], (long long)e01[1], g->d_rp, g->d_col, c.bits.get());
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    c.h = h;
+    c.base = base;
+    setup_trace("clique: core bitmap");
+    g->setup.table_ms += timer.ms();
+    return kOnceBuilt;
+  });
 }
 
 // ---- the core bitmap cut into blocks of rows for the blocked gather (gm_mine.h CGatherBParams; gm_cgather.hip cgatherb_kernel) ----------
@@ -1916,80 +1743,72 @@ __global__ __launch_bounds__(256) void core_tri_fill_kernel(int nv, int base, lo
   }
 }
 int ensure_core_tri(gm_graph *g) {
-  if (g->cg_tri_state) return GM_OK;
+  if (g->core_blocks.known()) return GM_OK;
   {
     const int rc = ensure_core_bitmap(g);  // (takes the lock itself)
     if (rc) return rc;
   }
-  std::lock_guard<std::mutex> lk(g->mu);
-  if (g->cg_tri_state) return GM_OK;
-  if (g->core_state != 1 || g->core_h < 64) {
-    g->cg_tri_state = 2;
-    return GM_OK;
-  }
-  SetupTimer timer;
-  HIP_TRY(hipSetDevice(g->device));
-  const int h = g->core_h, delta = g->core_base & 31, words = cgb_words(h, delta);
-  std::vector<int> bid((size_t)h), rowbase((size_t)h);
-  std::vector<int4> blk;
-  long long total = 0;
-  {
-    int p0 = 0, used = 0;
-    for (int p = 0; p <= h; ++p) {
-      const int span = p < h ? words - cgb_first_word(p, delta) : 0;
-      if (p == h || used + span > kCgbWords || p - p0 >= kCgbMaxRows) {  // close the block [p0, p)
-        if (p > p0) {
-          blk.push_back(make_int4(p0, p - p0, (int)total, used));
-          total += (used + 3) & ~3;  // (images start at multiples of four words: 16-byte copies)
+  return g->core_blocks.ensure(g->mu, [&](CoreBlocks &cb) {
+    if (!g->core.built() || g->core->h < 64) return kOnceNotApplicable;
+    SetupTimer timer;
+    HIP_TRY(hipSetDevice(g->device));
+    const int h = g->core->h, core_base = g->core->base, delta = core_base & 31, words = cgb_words(h, delta);
+    std::vector<int> bid((size_t)h), rowbase((size_t)h);
+    std::vector<int4> blk;
+    long long total = 0;
+    {
+      int p0 = 0, used = 0;
+      for (int p = 0; p <= h; ++p) {
+        const int span = p < h ? words - cgb_first_word(p, delta) : 0;
+        if (p == h || used + span > kCgbWords || p - p0 >= kCgbMaxRows) {  // close the block [p0, p)
+          if (p > p0) {
+            blk.push_back(make_int4(p0, p - p0, (int)total, used));
+            total += (used + 3) & ~3;  // (images start at multiples of four words: 16-byte copies)
+          }
+          p0 = p;
+          used = 0;
+          if (p == h) break;
         }
-        p0 = p;
-        used = 0;
-        if (p == h) break;
+        bid[(size_t)p] = (int)blk.size();
+        rowbase[(size_t)p] = used - cgb_first_word(p, delta);
+        used += span;
       }
-      bid[(size_t)p] = (int)blk.size();
-      rowbase[(size_t)p] = used - cgb_first_word(p, delta);
-      used += span;
     }
-  }
-  if (total >= (1ll << 31) || blk.size() >= 65536) {
-    g->cg_tri_state = 2;
-    return GM_OK;
-  }
-  DevOwn<unsigned> tri;
-  DevOwn<int> d_bid, d_rowbase;
-  DevOwn<int4> d_blk;
-  int e01[2] = {0, 0};
-  hipError_t e = tri.alloc(sizeof(unsigned) * (size_t)std::max<long long>(total, 4));
-  if (e == hipSuccess) e = d_bid.alloc(sizeof(int) * (size_t)h);
-  if (e == hipSuccess) e = d_rowbase.alloc(sizeof(int) * (size_t)h);
-  if (e == hipSuccess) e = d_blk.alloc(sizeof(int4) * blk.size());
-  if (e == hipSuccess) e = hipMemsetAsync(tri, 0, sizeof(unsigned) * (size_t)std::max<long long>(total, 4), 0);
-  if (e == hipSuccess) e = copy_to_device(d_bid, bid.data(), sizeof(int) * (size_t)h);
-  if (e == hipSuccess) e = copy_to_device(d_rowbase, rowbase.data(), sizeof(int) * (size_t)h);
-  if (e == hipSuccess) e = copy_to_device(d_blk, blk.data(), sizeof(int4) * blk.size());
-  if (e == hipSuccess) e = hipMemcpy(&e01[0], g->d_rp + g->core_base, sizeof(int), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(&e01[1], g->d_rp + g->nv, sizeof(int), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) {
-    const long long n = (long long)e01[1] - e01[0];
-    if (n > 0)
-      hipLaunchKernelGGL(core_tri_fill_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, (long long)g->cu_count * 32)), dim3(256), 0, 0, g->nv, g->core_base,
-                         (long long)e01[0], (long long)e01[1], g->d_rp, g->d_col, d_bid, d_rowbase, d_blk, tri);
-    e = hipDeviceSynchronize();
-  }
-  if (e != hipSuccess) {  // (no room: the row-major gather does the work)
-    (void)hipGetLastError();
-    g->cg_tri_state = 2;
-    return GM_OK;
-  }
-  g->d_cg_tri = std::move(tri);
-  g->d_cg_bid = std::move(d_bid);
-  g->d_cg_rowbase = std::move(d_rowbase);
-  g->d_cg_blk = std::move(d_blk);
-  g->n_cg_blocks = (int)blk.size();
-  g->cg_tri_state = 1;
-  setup_trace("clique: core blocks");
-  g->setup.table_ms += timer.ms();
-  return GM_OK;
+    if (total >= (1ll << 31) || blk.size() >= 65536) return kOnceNotApplicable;
+    DevOwn<unsigned> tri;
+    DevOwn<int> d_bid, d_rowbase;
+    DevOwn<int4> d_blk;
+    int e01[2] = {0, 0};
+    hipError_t e = tri.alloc(sizeof(unsigned) * (size_t)std::max<long long>(total, 4));
+    if (e == hipSuccess) e = d_bid.alloc(sizeof(int) * (size_t)h);
+    if (e == hipSuccess) e = d_rowbase.alloc(sizeof(int) * (size_t)h);
+    if (e == hipSuccess) e = d_blk.alloc(sizeof(int4) * blk.size());
+    if (e == hipSuccess) e = hipMemsetAsync(tri, 0, sizeof(unsigned) * (size_t)std::max<long long>(total, 4), 0);
+    if (e == hipSuccess) e = copy_to_device(d_bid, bid.data(), sizeof(int) * (size_t)h);
+    if (e == hipSuccess) e = copy_to_device(d_rowbase, rowbase.data(), sizeof(int) * (size_t)h);
+    if (e == hipSuccess) e = copy_to_device(d_blk, blk.data(), sizeof(int4) * blk.size());
+    if (e == hipSuccess) e = hipMemcpy(&e01[0], g->d_rp + core_base, sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&e01[1], g->d_rp + g->nv, sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) {
+      const long long n = (long long)e01[1] - e01[0];
+      if (n > 0)
+        hipLaunchKernelGGL(core_tri_fill_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, (long long)g->cu_count * 32)), dim3(256), 0, 0, g->nv, core_base,
+                           (long long)e01[0], (long long)e01[1], g->d_rp, g->d_col, d_bid, d_rowbase, d_blk, tri);
+      e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess) {  // (no room: the row-major gather does the work)
+      (void)hipGetLastError();
+      return kOnceNotApplicable;
+    }
+    cb.tri = std::move(tri);
+    cb.bid = std::move(d_bid);
+    cb.rowbase = std::move(d_rowbase);
+    cb.blk = std::move(d_blk);
+    cb.n = (int)blk.size();
+    setup_trace("clique: core blocks");
+    g->setup.table_ms += timer.ms();
+    return kOnceBuilt;
+  });
 }
 
 __global__ __launch_bounds__(256) void iota_u32_kernel(long long n, unsigned *__restrict__ out) {
@@ -2093,14 +1912,14 @@ __global__ __launch_bounds__(256) void cgb_item_place_kernel(long long n, const 
 constexpr unsigned long long kCgbItemCost = GM_CGB_ITEM_COST;  // probes (+ overheads) of a work item: ~80 us of one workgroup
 static int build_gather_index(gm_graph *g, CliquePlan &pl, CliqueRound &rd, ScanTemp &tmp) {
   const int nslots = (int)(rd.w1 - rd.w0);
-  if (nslots <= 0 || pl.core_base < 0 || g->cg_tri_state != 1 || rd.words >= (1ull << 32)) return GM_OK;  // (no index: the row-major gather)
+  if (nslots <= 0 || pl.core_base < 0 || !g->core_blocks.built() || rd.words >= (1ull << 32)) return GM_OK;  // (no index: the row-major gather)
   auto blocks = [](long long n) { return dim3((unsigned)std::max<long long>(1, (n + 255) / 256)); };
   DevBuf<int> cnt, uoff;
   HIP_TRY(cnt.alloc((size_t)nslots + 1));
   HIP_TRY(uoff.alloc((size_t)nslots + 1));
   HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)nslots + 1), 0));
   const dim3 wgrid((unsigned)(((long long)nslots + 3) / 4));
-  hipLaunchKernelGGL((cgb_units_kernel<false>), wgrid, dim3(256), 0, 0, (int)rd.w0, nslots, pl.d_verts, g->d_rp, g->d_col, pl.d_slot_base, pl.core_base, g->d_cg_bid,
+  hipLaunchKernelGGL((cgb_units_kernel<false>), wgrid, dim3(256), 0, 0, (int)rd.w0, nslots, pl.d_verts, g->d_rp, g->d_col, pl.d_slot_base, pl.core_base, g->core_blocks->bid.get(),
                      cnt.p, nullptr, nullptr, nullptr, nullptr);
   HIP_TRY(dev_exclusive_sum(tmp, cnt.p, uoff.p, (size_t)nslots + 1));
   int nu = 0;
@@ -2129,12 +1948,12 @@ static int build_gather_index(gm_graph *g, CliquePlan &pl, CliqueRound &rd, Scan
   HIP_TRY(idx.alloc((size_t)nu));
   HIP_TRY(idx_s.alloc((size_t)nu));
   HIP_TRY(recs.alloc((size_t)nu));
-  hipLaunchKernelGGL((cgb_units_kernel<true>), wgrid, dim3(256), 0, 0, (int)rd.w0, nslots, pl.d_verts, g->d_rp, g->d_col, pl.d_slot_base, pl.core_base, g->d_cg_bid,
+  hipLaunchKernelGGL((cgb_units_kernel<true>), wgrid, dim3(256), 0, 0, (int)rd.w0, nslots, pl.d_verts, g->d_rp, g->d_col, pl.d_slot_base, pl.core_base, g->core_blocks->bid.get(),
                      nullptr, uoff.p, poff.p, keys.p, recs.p);
   hipLaunchKernelGGL(iota_u32_kernel, blocks(nu), dim3(256), 0, 0, (long long)nu, idx.p);
   {
     int bits = 1;
-    while ((1 << bits) < g->n_cg_blocks) ++bits;
+    while ((1 << bits) < g->core_blocks->n) ++bits;
     size_t bytes = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keys.p, keys_s.p, idx.p, idx_s.p, nu, 0, bits));
     HIP_TRY(tmp.reserve(bytes));
@@ -2232,12 +2051,12 @@ static int build_clique_round(gm_graph *g, CliquePlan &pl, CliqueRound &rd, Scan
   HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(int) * nv1, 0));
   const long long kblocks = std::min<long long>(((long long)nv * 8 + 255) / 256, (long long)g->cu_count * (pl.topo ? 8 : 64));
   const int hub0 = pl.topo ? std::max(0, nv - kHubWin) : nv;
-  hipLaunchKernelGGL((cb_task_rows_kernel<false>), dim3((unsigned)kblocks), dim3(256), 0, 0, nv, g->d_rp, g->d_col, g->d_edesc, ntask_of.p, pl.topo ? 1 : 0, hub0,
+  hipLaunchKernelGGL((cb_task_rows_kernel<false>), dim3((unsigned)kblocks), dim3(256), 0, 0, nv, g->d_rp, g->d_col, g->edesc->get(), ntask_of.p, pl.topo ? 1 : 0, hub0,
                      cnt.p, nullptr, nullptr, nullptr);
   HIP_TRY(dev_exclusive_sum(tmp, cnt.p, rd.d_trp.get(), nv1));
   HIP_TRY(rd.d_tasks.alloc(sizeof(CBuildTask) * (size_t)nt));
   HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(int) * nv1, 0));
-  hipLaunchKernelGGL((cb_task_rows_kernel<true>), dim3((unsigned)kblocks), dim3(256), 0, 0, nv, g->d_rp, g->d_col, g->d_edesc, ntask_of.p, pl.topo ? 1 : 0, hub0,
+  hipLaunchKernelGGL((cb_task_rows_kernel<true>), dim3((unsigned)kblocks), dim3(256), 0, 0, nv, g->d_rp, g->d_col, g->edesc->get(), ntask_of.p, pl.topo ? 1 : 0, hub0,
                      cnt.p, rd.d_trp, rd.d_base, rd.d_tasks);
   HIP_TRY(hipGetLastError());
   // host chunks: runs of consecutive vertices whose DAG rows fit the stage (longer rows host nothing), costs from the task lists,
@@ -2288,7 +2107,8 @@ int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, un
   PoolScope pool(g);  // (the per-vertex arrays of the rounds)
   ScanTemp tmp;
   auto blocks = [](long long n) { return dim3((unsigned)std::max<long long>(1, (n + 255) / 256)); };
-  if (!g->wide_valid) {  // once per graph: the wide vertices, longest rows first (select + stable radix sort by row length)
+  // once per graph: the wide vertices, longest rows first (select + stable radix sort by row length)
+  if (const int rc_w = g->wide.ensure(g->mu, [&](WideVerts &wv) {
     const int nv = g->nv;
     DevBuf<int> flag, iota, sel, nsel, degs, keyo;
     HIP_TRY(flag.alloc((size_t)std::max(nv, 1)));
@@ -2304,19 +2124,19 @@ int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, un
       HIP_TRY(hipcub::DeviceSelect::Flagged(tmp.buf.p, bytes, iota.p, flag.p, sel.p, nsel.p, nv));
       HIP_TRY(hipMemcpy(&m, nsel.p, sizeof(int), hipMemcpyDeviceToHost));
     }
-    g->n_wide = (size_t)m;
+    wv.n = (size_t)m;
     if (m > 0) {
       HIP_TRY(degs.alloc((size_t)m));
       HIP_TRY(keyo.alloc((size_t)m));
       hipLaunchKernelGGL(gather_deg_kernel, blocks(m), dim3(256), 0, 0, m, sel.p, g->d_rp, degs.p);
-      HIP_TRY(g->d_wide_sorted.alloc(sizeof(int) * (size_t)m));
+      HIP_TRY(wv.sorted.alloc(sizeof(int) * (size_t)m));
       size_t bytes = 0;
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, degs.p, keyo.p, sel.p, g->d_wide_sorted.get(), m));
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, degs.p, keyo.p, sel.p, wv.sorted.get(), m));
       HIP_TRY(tmp.reserve(bytes));
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(tmp.buf.p, bytes, degs.p, keyo.p, sel.p, g->d_wide_sorted.get(), m));
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(tmp.buf.p, bytes, degs.p, keyo.p, sel.p, wv.sorted.get(), m));
     }
-    g->wide_valid = true;
-  }
+    return kOnceBuilt;
+  })) return rc_w;
   {  // topological numbering? (decides whether the in-edge tasks stream only the part of N+(u) beyond v)
     bool topo = false;
     const int rc = graph_is_topological(g, &topo);
@@ -2325,7 +2145,7 @@ int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, un
     if (pl.topo) {  // the dense hub core: rows of the wide vertices' matrices are gathered from it (gm_cgather.hip)
       const int rc2 = ensure_core_bitmap(g);
       if (rc2) return rc2;
-      if (g->core_state == 1) pl.core_base = g->core_base;
+      if (g->core.built()) pl.core_base = g->core->base;
     }
   }
   {  // this rank's share of the narrow table: every world-th chunk of the cost-ordered dequeue list, a contiguous range, or the
@@ -2345,14 +2165,14 @@ int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, un
   }
   // this rank's share of the wide list
   int64_t wfirst = 0, wstep = 1, wcount = 0;
-  gm_partition((int64_t)g->n_wide, rank, world, policy == GM_PART_VERTEX ? GM_PART_RANGE : policy, &wfirst, &wstep, &wcount);
+  gm_partition((int64_t)g->wide->n, rank, world, policy == GM_PART_VERTEX ? GM_PART_RANGE : policy, &wfirst, &wstep, &wcount);
   std::vector<int> hd((size_t)wcount);
   if (wcount > 0) {
     DevBuf<int> degs;
     HIP_TRY(pl.d_verts.alloc(sizeof(int) * (size_t)wcount));
     HIP_TRY(pl.d_slot_base.alloc(sizeof(unsigned long long) * (size_t)wcount));
     HIP_TRY(degs.alloc((size_t)wcount));
-    hipLaunchKernelGGL(wide_share_kernel, blocks(wcount), dim3(256), 0, 0, (int)wcount, (long long)wfirst, (long long)wstep, g->d_wide_sorted, g->d_rp, pl.d_verts, degs.p);
+    hipLaunchKernelGGL(wide_share_kernel, blocks(wcount), dim3(256), 0, 0, (int)wcount, (long long)wfirst, (long long)wstep, g->wide->sorted.get(), g->d_rp, pl.d_verts, degs.p);
     pl.verts.resize((size_t)wcount);
     HIP_TRY(copy_to_host(pl.verts.data(), pl.d_verts, sizeof(int) * (size_t)wcount));
     HIP_TRY(copy_to_host(hd.data(), degs.p, sizeof(int) * (size_t)wcount));
@@ -2443,12 +2263,12 @@ int get_clique_plan(gm_graph *g, int rank, int world, int policy, int target, un
   }
   setup_trace("clique: rounds built");
   const size_t need = (size_t)need_words * 4;
-  if (need > g->wide_mat_bytes) {
-    g->wide_mat_bytes = 0;
-    HIP_TRY(g->d_wide_mat.alloc(std::max<size_t>(need, 16)));
-    g->wide_mat_bytes = need;
+  if (need > g->arena.mat_bytes) {
+    g->arena.mat_bytes = 0;
+    HIP_TRY(g->arena.mat.alloc(std::max<size_t>(need, 16)));
+    g->arena.mat_bytes = need;
   }
-  if (!g->d_wide_queue) HIP_TRY(g->d_wide_queue.alloc(65536));
+  if (!g->arena.queue) HIP_TRY(g->arena.queue.alloc(65536));
   setup_trace("clique: arena");
   HIP_TRY(hipDeviceSynchronize());
   std::lock_guard<std::mutex> lk(g->mu);
