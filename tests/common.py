@@ -101,3 +101,23 @@ def list_windows(sym, size, upto, sentinel=-7):
     host = buf.cpu().numpy()
     assert bool((host[3 * upto:] == sentinel).all()), "nothing behind the last window"
     return host[:3 * upto].reshape(-1, 3)
+
+
+KCL_ROW_CONSTANTS = {"regs2": "kcl_local_regs2_row", "split": "kcl_local_split_row", "regs8": "kcl_local_regs8_row", "regs12": "kcl_local_regs12_row",
+                     "lds": "kcl_local_lds_row"}
+
+
+def kcl_row_constants():
+    """the row lengths at which gm_clique_local changes path, read from the library (gm_constant), under the short names the cells of
+    tests/planted_cliques.py use; "lanes": the entries of a row whose sets take one word per lane of the wide kernel (64 lanes of 32
+    bits; not exported)"""
+    import ctypes as C
+
+    from graphminer_amd import _lib
+
+    lib, out = _lib.load(), {"lanes": 64 * 32}
+    for key, name in KCL_ROW_CONSTANTS.items():
+        v = C.c_int64(0)
+        _lib.check(lib.gm_constant(name.encode(), C.byref(v)), "gm_constant")
+        out[key] = int(v.value)
+    return out
