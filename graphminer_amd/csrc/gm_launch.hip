@@ -436,6 +436,7 @@ static int fill_mine_params(PatternRun &r, int k) {
       p.g.tdesc = ks.tdescl;
     } else if (!pl.support && tl.colk && tl.tdesck && !(la->tune[6] & GM_T6_NO_KEYSTREAM)) {
       p.g.col = tl.colk;
+      p.g.col_entries = (long long)g->ne + (long long)tl.n_copy_keys;  // (the descriptors of the copies point behind ne)
       p.g.tdesc = tl.tdesck;
     }
   }

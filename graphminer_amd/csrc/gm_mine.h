@@ -9,7 +9,7 @@
 // else's main must not change what it runs on an ambient variable).  What tests need to reach a path on a small graph, and the documented
 // fallbacks, are named options set through the C ABI -- gm_dev_option(name, value), include/graphminer_amd.h -- and read with gm_opt():
 //   GM_DIAMOND_PER_EDGE, GM_SUP_STREAM / GM_SUP_NO_MASKS / GM_SUP_MASK_MIN (edge supports), GM_TC_CORE_H / GM_SUP_CORE_H (hub corner),
-//   GM_BIG_NE, GM_KST_MAX_KEYS, GM_TOPO_MIN_ROW, GM_WIDE_ARENA_MB, GM_TCT_SPLIT_ALWAYS, GM_RECT_LDS_MIN / GM_RECT_LDS_RANGES / GM_WRECT_RANGE (limits lowered for tests), GM_ORIENT_TWO_GATHERS,
+//   GM_BIG_NE, GM_KST_MAX_KEYS, GM_TOPO_MIN_ROW, GM_WIDE_ARENA_MB, GM_TCT_SPLIT_ALWAYS, GM_TCH_WIDE_NE, GM_RECT_LDS_MIN / GM_RECT_LDS_RANGES / GM_WRECT_RANGE (limits lowered for tests), GM_ORIENT_TWO_GATHERS,
 //   GM_RELABEL_GLOBAL_SORT (the previous setup paths, compared in tests), GM_NO_TEMP_POOL, and the n-GPU runner's GM_FORCE_RCCL_PATH /
 //   GM_DIAMOND_SUPPORTS_MAX_WORLD (host/multi.cc).  Only GM_SETUP_TRACE (setup steps on stderr: diagnostics, no algorithm) is an
 //   environment variable.  In -DGM_DEVEL builds (make DEVEL=1) an option that is not set falls back to the environment, and the
@@ -107,6 +107,10 @@ struct GraphView {
   const unsigned *kst = nullptr;
   const int *kst_rp = nullptr;
   const int2 *kst_et = nullptr;  // edge supports: per key of kst {the DAG entry it was copied from, the entry of its task's own edge}
+  // entries of the array `col` points at where that is longer than the graph's own ne (the triangle count of a handle without the key
+  // stream: col[] followed by the task-major copies of the short lists, gm_host.h TaskLists::colk -- tdesc then points behind ne), else 0.
+  // Whoever swaps `col` sets it in the same breath: launch_tch chooses its key addressing by it (gm_tch_rule.h).
+  long long col_entries = 0;
 };
 
 // lookup lists of at least this many keys are streamed one task at a time with a wave-uniform descriptor, shorter ones flattened 64 to a batch

@@ -18,6 +18,7 @@
 // Chunk table, task lists, parts, dequeue order: those of tct_kernel (the kernel is chosen per launch, gm_launch.hip).
 #include <type_traits>
 #include "gm_flat.h"
+#include "gm_tch_rule.h"
 
 namespace gm {
 
@@ -29,8 +30,10 @@ constexpr int kTchTiles = GM_TCH_TILES;  // 64-key tiles in flight per wave (lon
 #define GM_TCH_TILES_SMALL 2
 #endif
 constexpr int kTchTilesSmall = GM_TCH_TILES_SMALL;  // ... 1024-bucket kernel
-// ... in the flattened pass of the short lists, per stage (one group ahead is in flight on top; R-MAT-22 / power law / flat degrees /
-// R-MAT-24 formula 3-motif, ms: 4 tiles 3.02 / 1.08 / 0.86 / 42.9, 8 tiles 3.04 / 1.12 / 0.90 / 42.1 -- the 2048-bucket kernel has the registers for 8)
+// ... in the flattened pass of the short lists, per stage (one group ahead is in flight on top).  Chosen in round 4, on the kernel
+// before the hub corner and before the peeled steady state -- R-MAT-22 / power law / flat degrees / R-MAT-24 formula 3-motif, ms then:
+// 4 tiles 3.02 / 1.08 / 0.86 / 42.9, 8 tiles 3.04 / 1.12 / 0.90 / 42.1 -- and not swept again since: the 1024-bucket kernel holds 79
+// of its 80 registers with 4 tiles, the 2048-bucket kernel has the registers for 8
 constexpr int kTchFlatTilesSmall = 4, kTchFlatTilesBig = 8;
 
 // lookup lists of at least this many keys are streamed one task at a time, shorter ones flattened 64 to a batch.  Its own threshold
@@ -43,6 +46,8 @@ constexpr int kTchFlatTilesSmall = 4, kTchFlatTilesBig = 8;
 #endif
 constexpr int kTchLongList = GM_TCH_LONG_LIST;
 
+// (kTchFlatBias, kTchNarrowEntries and the rule that chooses between the narrow and the WIDE key addressing of the flattened pass: gm_tch_rule.h)
+
 constexpr int kTchOvfCap = 128;
 constexpr unsigned kTchEmpty = 0xffffffffu, kTchMarker = 0xfffffffeu;  // (ids are < 2^31 - 1)
 constexpr unsigned kTchMul = 0x9E3779B1u;
@@ -52,7 +57,8 @@ constexpr unsigned kTchMul = 0x9E3779B1u;
 // workgroups per CU)
 template <int BITWIN>
 struct alignas(16) TchWave {
-  int2 desc[GM_WAVE];              // per non-empty list of the batch: {key_base - offset among the flattened positions, salt of the host row}
+  int2 desc[GM_WAVE];              // per non-empty list of the batch: {key_base - offset among the flattened positions (times four, modulo
+                                   // 2^32, in the narrow form: kTchFlatBias), salt of the host row}
   unsigned bits[BITWIN / 32 + 8];  // list-start marks of the flattened positions, one bit each (+ the over-read of the last group)
 };
 
@@ -157,7 +163,7 @@ __device__ __forceinline__ unsigned tch_surplus(const TchLds<STAGE> &B, const in
 }
 
 // One batch of tasks: stream the lists (llen_all keys from col[key_base ..), 0 = no task) against the set; returns the matches (wave-uniform).
-template <int STAGE>
+template <int STAGE, bool WIDE>
 __device__ __forceinline__ unsigned tch_pass(TchLds<STAGE> &B, TchWave<TchLds<STAGE>::kBitWindow> &L, const int *__restrict__ col, const bool fallback, const int lane,
                                              const int llen_all, const int key_base, const unsigned salt_l) {
   // (tiles per group of a long list: a list of 200 .. 300 keys fills groups of 128 keys better than groups of 256 -- R-MAT-22, 1 / 2 / 3 / 4 tiles:
@@ -243,54 +249,83 @@ __device__ __forceinline__ unsigned tch_pass(TchLds<STAGE> &B, TchWave<TchLds<ST
   // broadcast 8-byte LDS read and a v_mbcnt pair per tile, a scalar popcount for the carry; a window is 8192 positions (1 KB of
   // marks), so that -- unlike the 512 byte-marks per window of the other kernels -- a whole batch is usually ONE window and the keys
   // of the NEXT tile group are requested before the current group is looked up (measured: TF = 8 tiles in flight without the
-  // pipeline R-MAT-22 3.34 -> 3.22 ms) ----------------------------------------------------------------------------------------------
+  // pipeline R-MAT-22 3.34 -> 3.22 ms).  On R-MAT-22 88 % of the streamed keys outside the hub corner pass through this loop and none
+  // through the one-at-a-time path above, so its steady state is peeled: per 64 keys 8 vector instructions of lookup,
+  // 5 of owner resolution, 1 of addressing (profiles/r13/ab_tc_flat_steady.txt) ------------------------------------------------------
   const int incl = wave_incl_scan_add(llen);
   const int total = readlane(incl, GM_WAVE - 1);
   if (total == 0) return cnt;  // wave-uniform
   const int off = incl - llen;
   const unsigned long long nzm = __ballot(llen > 0);
-  if (llen > 0) L.desc[rank_below(nzm)] = make_int2(key_base - off, (int)salt_l);  // (compacted: the k-th non-empty list)
+  // (compacted: the k-th non-empty list.  The narrow form keeps the key base as a BYTE offset modulo 2^32: see kTchFlatBias)
+  if (llen > 0) L.desc[rank_below(nzm)] = make_int2(WIDE ? key_base - off : (int)((unsigned)(key_base - off) << 2), (int)salt_l);
   constexpr int G = GM_WAVE * TF, kBitWin = TchLds<STAGE>::kBitWindow;
   constexpr int TH = 4, NH = TF / TH;  // a group is looked up in halves of four tiles (the 16-byte buckets of eight would not fit the registers)
   static_assert(TF % TH == 0, "tile groups are made of half-groups of four");
+  static_assert(kTchFlatBias >= 4u * (unsigned)(GM_WAVE * (kTchLongList - 1) + G), "the bias covers every flattened position of a batch and the over-run of its last group");
   struct Grp {
     int key[NH][TH];
     unsigned salt[NH][TH];
     unsigned long long inm[NH][TH];
   };
+  // (the descriptors through their LDS byte address, wave-uniform: owner k is at dbase + 8 k, one shift-add from the v_mbcnt pair)
+  using LdsDesc = const __attribute__((address_space(3))) unsigned long long;
+  const unsigned dbase = (unsigned)readfirst((int)(unsigned)(size_t)(LdsDesc *)reinterpret_cast<const unsigned long long *>(&L.desc[0]));
+  const char *const colb = reinterpret_cast<const char *>(col) - kTchFlatBias;  // (never dereferenced below col: every offset carries the bias)
+  const unsigned lane4 = ((unsigned)lane << 2) + kTchFlatBias;  // (the bias rides on the lane's part of the offset)
   for (int wb = 0; wb < total; wb += kBitWin) {
     const int wn = min(kBitWin, total - wb);
     const int nw = ((wn + G - 1) / G) * (G / 32) + 2;
     for (int i = lane; i < nw; i += GM_WAVE) L.bits[i] = 0u;
     wave_sync();
     if (llen > 0 && off > wb && off < wb + kBitWin) atomicOr(&L.bits[(off - 1 - wb) >> 5], 1u << ((off - 1 - wb) & 31));
-    int carry = __popcll(__ballot(llen > 0 && off <= wb)) - 1;  // the list that owns position wb
+    // the descriptor of the list that owns position wb, as its LDS address; every mark passed moves it on by one descriptor
+    unsigned carry = dbase + ((unsigned)(__popcll(__ballot(llen > 0 && off <= wb)) - 1) << 3);
     wave_sync();
-    auto stage_a = [&](const int g, Grp &r) {  // owners, descriptors, key loads of tile group g of the window
+    // owners, descriptors, key loads of tile group g of the window.  FULL: the group lies wholly inside the window and below `total`
+    // (every group of a window but its last): no range test, no ballot, no guarded select on the owner and on the index.
+    auto stage_a = [&](auto full, const int g, Grp &r) {
+      constexpr bool FULL = decltype(full)::value;
       int2 d[TF];
       bool in[TF];
+      const int p0 = wb + g * G;  // wave-uniform
       // the 2 * TF mark words of the group: one LDS read (lane l holds word l), then two v_readlane per tile
       const int mw = (int)L.bits[((g * G) >> 5) + (lane & (2 * TF - 1))];
 #pragma unroll
       for (int q = 0; q < TF; ++q) {
         const unsigned long long m = ((unsigned long long)(unsigned)readlane(mw, 2 * q + 1) << 32) | (unsigned)readlane(mw, 2 * q);
-        const int own = carry + rank_below(m);
-        carry += __popcll(m);
-        in[q] = (wb + g * G + q * GM_WAVE + lane) < total;
-        r.inm[q / TH][q % TH] = __ballot(in[q]);
-        d[q] = L.desc[in[q] ? own : 0];  // unconditional LDS read
+        const unsigned own = carry + ((unsigned)rank_below(m) << 3);
+        carry += (unsigned)__popcll(m) << 3;
+        asm volatile("" : "+s"(carry));  // (kept in a scalar register as it stands: re-associated, every tile paid a vector add for its part of the sum)
+        in[q] = FULL || (p0 + q * GM_WAVE + lane) < total;
+        r.inm[q / TH][q % TH] = FULL ? ~0ull : __ballot(in[q]);
+        const unsigned long long dw = *(LdsDesc *)(size_t)(in[q] ? own : dbase);  // unconditional LDS read, the descriptor as one 8-byte word
+        d[q] = make_int2((int)(unsigned)dw, (int)(unsigned)(dw >> 32));
       }
 #pragma unroll
       for (int q = 0; q < TF; ++q) {
-        r.key[q / TH][q % TH] = col[in[q] ? d[q].x + (wb + g * G + q * GM_WAVE + lane) : 0];  // unconditional load (select on the index)
+        if constexpr (WIDE) {  // exact for every index below 2^31: the index as an unsigned 32-bit sum (d.x may be negative, the sum is not)
+          const unsigned idx = (unsigned)d[q].x + (unsigned)(p0 + q * GM_WAVE + lane);
+          r.key[q / TH][q % TH] = col[in[q] ? idx : 0u];  // unconditional load (select on the index)
+        } else {
+          // address = (col - bias + 4 p0) + zero-extended 32-bit (4 (key_base - off) + (4 lane + bias)) + 256 q: a scalar base, ONE
+          // vector add, the tile in the load's immediate offset.  The 32-bit sum is 4 (index - p0 - 64 q) + bias with index - p0 - 64 q
+          // > -(positions of a batch): never negative, and below 2^32 while the array streamed from has fewer than kTchNarrowEntries entries (gm_tch_rule.h).
+          const unsigned idle = kTchFlatBias - ((unsigned)(p0 + q * GM_WAVE) << 2);  // a lane beyond `total` loads col[0]
+          const unsigned voff = in[q] ? (unsigned)d[q].x + lane4 : idle;
+          r.key[q / TH][q % TH] = *reinterpret_cast<const int *>(colb + ((size_t)(unsigned)p0 << 2) + (size_t)voff + (size_t)(q * GM_WAVE * 4));
+        }
         r.salt[q / TH][q % TH] = (unsigned)d[q].y;
       }
     };
-    auto stage_b = [&](const Grp &r) {
+    auto stage_b = [&](auto full, const Grp &r) {
+      constexpr bool FULL = decltype(full)::value;
 #pragma unroll
       for (int h = 0; h < NH; ++h) {
-        unsigned long long hm[TH], nm[TH];
-        tch_probe<STAGE, TH>(B, col, fallback, r.key[h], r.salt[h], r.inm[h], hm, nm);
+        unsigned long long inm[TH], hm[TH], nm[TH];
+#pragma unroll
+        for (int q = 0; q < TH; ++q) inm[q] = FULL ? ~0ull : r.inm[h][q];  // (a compile-time all-ones: no s_and on the hit and marker masks)
+        tch_probe<STAGE, TH>(B, col, fallback, r.key[h], r.salt[h], inm, hm, nm);
         unsigned long long any_need = 0ull;
 #pragma unroll
         for (int q = 0; q < TH; ++q) {
@@ -300,16 +335,30 @@ __device__ __forceinline__ unsigned tch_pass(TchLds<STAGE> &B, TchWave<TchLds<ST
         if (any_need != 0ull) cnt += tch_surplus<STAGE, TH>(B, lane, r.key[h], r.salt[h], nm);  // rare
       }
     };
-    const int ng = (wn + G - 1) / G;
+    // the full groups in the peeled form, one group ahead in flight; the last group of the window, if it is partial, in the guarded
+    // form -- requested under the last full group's lookup, so the pipeline holds across the switch
+    constexpr std::true_type kFull{};
+    constexpr std::false_type kGuarded{};
+    const int nfull = wn / G, ng = (wn + G - 1) / G;
     Grp cur;
-    stage_a(0, cur);
-    for (int g = 0; g + 1 < ng; ++g) {
-      Grp nxt;
-      stage_a(g + 1, nxt);
-      stage_b(cur);
-      cur = nxt;
+    if (nfull == 0) {  // (wn > 0: the window is one partial group)
+      stage_a(kGuarded, 0, cur);
+    } else {
+      stage_a(kFull, 0, cur);
+      for (int g = 0; g + 1 < nfull; ++g) {
+        Grp nxt;
+        stage_a(kFull, g + 1, nxt);
+        stage_b(kFull, cur);
+        cur = nxt;
+      }
+      if (ng > nfull) {
+        Grp nxt;
+        stage_a(kGuarded, nfull, nxt);
+        stage_b(kFull, cur);
+        cur = nxt;
+      }
     }
-    stage_b(cur);
+    stage_b(kGuarded, cur);  // (the last group, full or not: a full one carries all-ones masks)
     wave_sync();
   }
   return cnt;
@@ -318,7 +367,7 @@ __device__ __forceinline__ unsigned tch_pass(TchLds<STAGE> &B, TchWave<TchLds<ST
 #ifndef GM_TCH_MIN_WG
 #define GM_TCH_MIN_WG 6
 #endif
-template <int STAGE>
+template <int STAGE, bool WIDE>
 __global__ __launch_bounds__((tch_waves<STAGE>() * GM_WAVE), (STAGE <= 1024 ? GM_TCH_MIN_WG : GM_TCH_MIN_WG_BIG))
 void tch_kernel(const MineParams p) {
   __shared__ TchLds<STAGE> B;
@@ -371,17 +420,21 @@ void tch_kernel(const MineParams p) {
         }
       }
       {
-        const uint4 empty = make_uint4(kTchEmpty, kTchEmpty, kTchEmpty, kTchEmpty);
+        // (the two constants are made here, per chunk: hoisted out of the dequeue loop, their register tuples -- four words of ones,
+        // two of zeros -- stayed occupied across the streaming loops, which have none to spare at six waves per SIMD)
+        unsigned ones = kTchEmpty, zero = 0u;
+        asm volatile("" : "+v"(ones), "+v"(zero));
+        const uint4 empty = make_uint4(ones, ones, ones, ones);
         for (int i = tid; i < STAGE; i += nthreads) B.table[i] = empty;
-        for (int i = tid; i < STAGE / 2; i += nthreads) fill32[i] = 0u;
+        for (int i = tid; i < STAGE / 2; i += nthreads) fill32[i] = zero;
         if (tid < kTchOvfCap) {
-          B.ovf_key[tid] = -1;
-          B.ovf_salt[tid] = -1;
+          B.ovf_key[tid] = (int)ones;
+          B.ovf_salt[tid] = (int)ones;
         }
         if (tid == 0) {
-          B.n_ovf = 0;
-          B.next_batch = 0;
-          B.next_group = 0;
+          B.n_ovf = (int)zero;
+          B.next_batch = (int)zero;
+          B.next_group = (int)zero;
         }
       }
       __syncthreads();
@@ -490,7 +543,7 @@ void tch_kernel(const MineParams p) {
         }
       }
       // ---- waves: batches of 64 tasks ---------------------------------------------------------------------------------
-      const int tb = B.trpl[0], ntask = B.trpl[nvl] - tb;
+      const int tb = readfirst(B.trpl[0]), ntask = readfirst(B.trpl[nvl]) - tb;  // (scalar registers: they live across every batch)
       for (;;) {
         int bi = 0;
         if (lane == 0) bi = atomicAdd(&B.next_batch, 1);
@@ -503,7 +556,7 @@ void tch_kernel(const MineParams p) {
         const int lo = tch_local_row(B.trpl, nvl, te);  // the host row of this task
         const int ru = B.rpl[lo], a = B.rpl[lo + 1] - ru;
         const bool act = valid && d.y > 0 && a > 0;
-        c0 += (unsigned long long)tch_pass<STAGE>(B, L, col, fallback, lane, act ? d.y : 0, d.x, H::salt(lo));
+        c0 += (unsigned long long)tch_pass<STAGE, WIDE>(B, L, col, fallback, lane, act ? d.y : 0, d.x, H::salt(lo));
       }
       __syncthreads();  // the table is rewritten by the next chunk
     }
@@ -522,8 +575,16 @@ hipError_t launch_tch(const MineParams &p, int stage, int grid_blocks, hipStream
   static_assert(sizeof(TchWave<4096>) * tch_waves<kTctStageMax>() >= (size_t)kTctStageMax * 2, "fill counters alias the wave scratch");
   if (p.g.trp == nullptr || p.g.tdesc == nullptr) return hipErrorInvalidValue;
   const dim3 grid((unsigned)grid_blocks);
-  if (stage <= 1024) hipLaunchKernelGGL((tch_kernel<1024>), grid, dim3(kWavesPerBlock * GM_WAVE), 0, stream, p);
-  else hipLaunchKernelGGL((tch_kernel<kTctStageMax>), grid, dim3(tch_waves<kTctStageMax>() * GM_WAVE), 0, stream, p);
+  // (the rule of gm_tch_rule.h, on the extent of the array the keys are streamed from -- not on the DAG's own entry count)
+  const bool wide = tch_wide_form(tch_key_entries(p.g.ne, p.g.col_entries), gm_opt("GM_TCH_WIDE_NE"));
+  const dim3 block_small(kWavesPerBlock * GM_WAVE), block_big(tch_waves<kTctStageMax>() * GM_WAVE);
+  if (stage <= 1024) {
+    if (wide) hipLaunchKernelGGL((tch_kernel<1024, true>), grid, block_small, 0, stream, p);
+    else hipLaunchKernelGGL((tch_kernel<1024, false>), grid, block_small, 0, stream, p);
+  } else {
+    if (wide) hipLaunchKernelGGL((tch_kernel<kTctStageMax, true>), grid, block_big, 0, stream, p);
+    else hipLaunchKernelGGL((tch_kernel<kTctStageMax, false>), grid, block_big, 0, stream, p);
+  }
   return hipGetLastError();
 }
 
