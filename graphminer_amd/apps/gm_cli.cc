@@ -1,8 +1,8 @@
 // gm_cli.cc -- one source for the whole command-line surface of the HIP solvers.
 //
-// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
+// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL|RECTLOCAL> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
 //   tc_gpu_base tc_multigpu tc_multigpu_base | sgl_gpu_base sgl_multigpu | clique_gpu_base clique_multigpu kcl_gpu_base |
-//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base | cliquelocal_gpu_base
+//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base | cliquelocal_gpu_base | rectlocal_gpu_base
 // The observable behaviour -- positional argv, defaults, usage text, banner and FINAL result lines -- is that of the
 // reference mains (src/triangle/main.cc:7-27, src/sgl/main.cc:9-35, src/clique/main.cc:8-28, src/motif/main.cc:9-31,
 // Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.  truss_gpu_base <graph prefix> [k] has no
@@ -14,6 +14,8 @@
 // cliquelocal_gpu_base <graph prefix> <k> [out prefix] counts the k-cliques at every vertex and on every edge (gm_clique_local):
 // `total_num_cliques = N` in kcl_gpu_base's spelling, then `max_vertex_cliques = A` and `max_edge_cliques = B`; with an out prefix the
 // per-vertex counts go to <out>.vertex.u64 and the per-entry counts to <out>.entry.u64 as raw little-endian uint64.
+// rectlocal_gpu_base <graph prefix> [out prefix] counts the 4-cycles at every vertex and on every edge (gm_rect_local): `max_vertex_rectangles
+// = A` and `max_edge_rectangles = B`, then `total_num = N` in sgl_gpu_base's spelling as the last line; the same two files with an out prefix.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -31,11 +33,12 @@
 #define GM_SGL6 6
 #define GM_TCLIST 7
 #define GM_CLIQUELOCAL 8
-#if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL)
+#define GM_RECTLOCAL 9
+#if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL)
 #include <hip/hip_runtime_api.h>
 #endif
 #ifndef GM_APP
-#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL"
+#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL|GM_RECTLOCAL"
 #endif
 
 namespace {
@@ -48,7 +51,7 @@ struct Cli {
   int adj_sorted = 1;  // [adj_sorted(1)] (tc only)
 };
 
-#if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_CLIQUELOCAL
+#if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_CLIQUELOCAL && GM_APP != GM_RECTLOCAL
 // positional layout: TC has no <second>; the others do
 Cli parse(int argc, char **argv, bool has_second) {
   Cli c;
@@ -84,6 +87,9 @@ void usage_and_exit(const char *self) {
 #elif GM_APP == GM_CLIQUELOCAL
   std::printf("Usage: %s <graph prefix> <k> [out prefix]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4 cliques\n", self);
+#elif GM_APP == GM_RECTLOCAL
+  std::printf("Usage: %s <graph prefix> [out prefix]\n", self);
+  std::printf("Example: %s /graph_inputs/mico/graph rectangles\n", self);
 #else
   std::printf("Usage: %s<graph> <k> [ngpu(0)] [chunk_size(1024)]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4\n", self);
@@ -116,12 +122,12 @@ static int strip_dev_options(int argc, char **argv) {
 
 int main(int argc, char **argv) {
   argc = strip_dev_options(argc, argv);
-  const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS && GM_APP != GM_TCLIST);
+  const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_RECTLOCAL);
   if (argc < (has_second ? 3 : 2)) usage_and_exit(argv[0]);
-#if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL
+#if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL
   Cli c;
   c.graph = argv[1];
-  if (argc > 2) c.second = argv[2];  // [k] / [out.bin] / <k>
+  if (argc > 2) c.second = argv[2];  // [k] / [out.bin] / <k> / [out prefix]
 #else
   const Cli c = parse(argc, argv, has_second);
 #endif
@@ -268,6 +274,45 @@ int main(int argc, char **argv) {
   std::printf("\ntotal_num_cliques = %llu\n\n", (unsigned long long)total);
   std::printf("max_vertex_cliques = %llu\n", (unsigned long long)(kv.empty() ? 0 : *std::max_element(kv.begin(), kv.end())));
   std::printf("max_edge_cliques = %llu\n", (unsigned long long)(ke.empty() ? 0 : *std::max_element(ke.begin(), ke.end())));
+
+#elif GM_APP == GM_RECTLOCAL
+  std::printf("local 4-cycle counts (undirected graph only)\n");
+  std::fflush(stdout);
+  Graph g(c.graph);
+  g.print_meta_data();
+  const gm_csr csr = g.csr();
+  const std::string out = c.second;
+  const size_t nv = (size_t)csr.nv, ne = (size_t)csr.ne;
+  gm_graph *h = nullptr;
+  int rc = gm_graph_upload(&csr, 0, &h);
+  uint64_t total = 0;
+  std::vector<uint64_t> rv(nv), re(ne);
+  uint64_t *d_rv = nullptr, *d_re = nullptr;
+  // (the two arrays are the call's results and the caller's buffers)
+  if (rc == GM_OK && hipMalloc(reinterpret_cast<void **>(&d_rv), sizeof(uint64_t) * (nv > 0 ? nv : 1)) != hipSuccess) rc = GM_ERR_HIP;
+  if (rc == GM_OK && hipMalloc(reinterpret_cast<void **>(&d_re), sizeof(uint64_t) * (ne > 0 ? ne : 1)) != hipSuccess) rc = GM_ERR_HIP;
+  if (rc == GM_OK) rc = gm_rect_local(h, nullptr, d_rv, d_re, &total, nullptr);
+  if (rc == GM_OK && nv > 0 && hipMemcpy(rv.data(), d_rv, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+  if (rc == GM_OK && ne > 0 && hipMemcpy(re.data(), d_re, sizeof(uint64_t) * ne, hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+  if (d_rv) (void)hipFree(d_rv);
+  if (d_re) (void)hipFree(d_re);
+  gm_graph_free(h);
+  if (rc == GM_OK && !out.empty()) {  // (the hosts this runs on are little-endian: the counts go out as they lie in memory)
+    const struct { std::string path; const std::vector<uint64_t> *v; } files[2] = {{out + ".vertex.u64", &rv}, {out + ".entry.u64", &re}};
+    for (const auto &file : files) {
+      FILE *f = std::fopen(file.path.c_str(), "wb");
+      const bool ok = f && std::fwrite(file.v->data(), sizeof(uint64_t), file.v->size(), f) == file.v->size();
+      if (f && std::fclose(f) != 0) rc = GM_ERR_IO;
+      if (!ok) rc = GM_ERR_IO;
+    }
+  }
+  if (rc != GM_OK) {
+    std::fprintf(stderr, "%s: %s %s\n", argv[0], gm_strerror(rc), gm_last_error());
+    return 1;
+  }
+  std::printf("max_vertex_rectangles = %llu\n", (unsigned long long)(rv.empty() ? 0 : *std::max_element(rv.begin(), rv.end())));
+  std::printf("max_edge_rectangles = %llu\n", (unsigned long long)(re.empty() ? 0 : *std::max_element(re.begin(), re.end())));
+  std::printf("total_num = %llu\n", (unsigned long long)total);
 
 #elif GM_APP == GM_SGL6
   std::printf("Subgraph Listing/Counting (undirected graph only)\n");

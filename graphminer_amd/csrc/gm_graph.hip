@@ -276,6 +276,7 @@ int finish_handle(gm_graph *g) {
     gm_touch_sup();
     gm_touch_wtri();
     gm_touch_wrect();
+    gm_touch_rect_local();
     gm_touch_local();
     gm_touch_list();
     gm_touch_kcl_local();
@@ -1210,7 +1211,7 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
   DevBuf<int> dupflag;
   HIP_TRY(dupflag.alloc(1));
   HIP_TRY(hipMemsetAsync(dupflag.p, 0, sizeof(int), 0));
-  HIP_TRY(newid.alloc(nv1, mode == 2));  // (the topological copy keeps it: the local counts map the caller's ids through it)
+  HIP_TRY(newid.alloc(nv1, mode != 1));  // (the topological copy and the ascending one keep it: the local counts map the caller's ids through it)
   HIP_TRY(newdeg.alloc(nv1));
   HIP_TRY(vkeys.alloc(nv1));
   HIP_TRY(vsorted.alloc(nv1));
@@ -1319,7 +1320,7 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
       return GM_OK;
     }
   }
-  if (mode == 2) r->d_newid.take(newid);
+  if (mode != 1) r->d_newid.take(newid);
   std::lock_guard<std::mutex> lk(g->mu);
   g->relabel_cache[mode] = r;
   g->setup.relabel_ms += timer.ms();

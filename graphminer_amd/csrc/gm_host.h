@@ -4,7 +4,7 @@
 //   gm_launch.hip  the launch layer (interface: gm_launch.h, for the three solver units only): launch prologue / epilogue, run_pattern,
 //                  gm_kernel_times, gm_tc / gm_clique / gm_motif, and every kernel of the layer
 //   gm_solve_sgl.hip    the SgL family: gm_sgl, the rectangle / house / pentagon map solvers, gm_diamond_support_*, gm_sgl4 / 5 / 6   (host code only)
-//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local                                                    (host code only)
+//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_rect_local                                     (host code only)
 //   gm_tools.hip   set-op batch, R-MAT generator, PMC / issue-rate calibration kernels, self test
 // Host-side counterparts in the reference:
 //   GraphGPU::init / init_edgelist          include/graph_gpu.h:69-194
@@ -460,6 +460,15 @@ struct WrectPlan {
   unsigned long long n_tasks = 0;
   int range = 0, grp = 1;
 };
+// the local 4-cycle counts (gm_rect_local.hip, gm_rect_local), on the graph the walk runs on (the copy numbered ascending in degree, or the
+// handle itself): ids per range (GM_RECT_LOCAL_RANGE), ranges per bit of the row masks, the masks, the task list -- wrect_kernel's plan at
+// a range of its own
+struct RectLocalPlan {
+  DevOwn<unsigned long long> mask;
+  DevOwn<int2> tasks;
+  unsigned long long n_tasks = 0;
+  int range = 0, grp = 1;
+};
 struct SymDegrees {  // the 5-vertex closed forms (gm_sgl5_raw): the symmetric degrees of the DAG's vertices
   DevOwn<int> deg;
 };
@@ -502,11 +511,12 @@ struct gm_graph {
   Once<RectLdsPlan> rect_lds;
   Once<HouseLdsPlan> house_lds;
   Once<WrectPlan> wrect;
+  Once<RectLocalPlan> rect_local;
   Once<SymDegrees> w5deg;
   Once<RevIndex> lrev;
   Once<ListOffsets> list_off;
   // gm_graph_sort_neighbors rewrites the rows: it refuses a handle on which one of these describes them already.  NOT checked (the list
-  // predates them): core, core_blocks, long_rows, sup_corner, sup_masks, kst_entries, facts other than sum_c2, rect_lds, house_lds, wrect,
+  // predates them): core, core_blocks, long_rows, sup_corner, sup_masks, kst_entries, facts other than sum_c2, rect_lds, house_lds, wrect, rect_local,
   // w5deg, lrev, list_off, relabel_cache[2], clique_plans -- most of them cannot exist without one that is
   bool rows_in_use() const {
     return !tables.empty() || edesc.built() || tasklists.built() || kst.built() || dag_cache || relabel_cache[0] || relabel_cache[1] || rect_idx.built() ||
@@ -547,6 +557,9 @@ struct gm_graph {
     DevOwn<unsigned> kcl_scratch;
     size_t kcl_scratch_bytes = 0;
     DevOwn<unsigned long long> ent64; // per entry of the symmetric graph
+    // local 4-cycle counts, on the graph the walk runs on: the credits of every entry (zeroed by every call).  On the SYMMETRIC handle the
+    // counts in the caller's entry order are ent64's, as for the k-cliques
+    DevOwn<unsigned long long> racc;
   } local;
   struct MapWork {  // the global counter maps of run_rect_acc / run_house_acc (rectangle, pentagon, house by wedge accumulation)
     DevOwn<unsigned> rect_acc;
@@ -567,7 +580,7 @@ struct gm_graph {
     size_t bytes = 0;
   } scratch;
   // ---- the handle's own ---------------------------------------------------------------------------------------------------------------------
-  DevOwn<int> d_newid;       // the topological copy made by get_relabeled (mode 2): id in the graph it was made from -> id here (nv)
+  DevOwn<int> d_newid;       // a copy made by get_relabeled, mode 0 (ascending in degree) or 2 (topological): id in the graph it was made from -> id here (nv)
   DevOwn<unsigned long long> d_counters;  // [4] + queue word, 64 B
   static constexpr int kEvRing = 64;  // HIP-event pairs of the most recent launches
   hipEvent_t ev[kEvRing][4] = {};      // [0], [1]: around the launch; [2], [3]: around its hub-corner kernel (gm_ctc.hip) when it has one
@@ -699,6 +712,7 @@ void gm_touch_tch();
 void gm_touch_sup();
 void gm_touch_wtri();
 void gm_touch_wrect();
+void gm_touch_rect_local();
 void gm_touch_local();
 void gm_touch_list();
 void gm_touch_kcl_local();

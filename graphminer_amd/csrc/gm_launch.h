@@ -134,6 +134,7 @@ int run_tc(const gm_graph *dag, const gm_launch *la, uint64_t *out, int nout, gm
 int ensure_dag_cache(gm_graph *g);  // the oriented copy of a symmetric handle, built once
 // gm_solve_sgl.hip: the handle the edge supports of a symmetric graph run on; the rectangle kernels (gm_motif4_partial takes them too)
 int diamond_run_on(const gm_graph *sym, const gm_launch *la, gm_graph **run_on);
+int ensure_idx0(gm_graph *g, const GraphView &gv);  // the neighbours below every vertex (RectIdx), built once per graph
 int run_rect_acc(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm_stats *st, bool pentagon = false);
 int run_rect_flat(const gm_graph *cg, const gm_launch *la_in, uint64_t *h_out, gm_stats *st, bool pentagon = false);
 

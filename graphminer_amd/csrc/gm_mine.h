@@ -9,7 +9,7 @@
 // else's main must not change what it runs on an ambient variable).  What tests need to reach a path on a small graph, and the documented
 // fallbacks, are named options set through the C ABI -- gm_dev_option(name, value), include/graphminer_amd.h -- and read with gm_opt():
 //   GM_DIAMOND_PER_EDGE, GM_SUP_STREAM / GM_SUP_NO_MASKS / GM_SUP_MASK_MIN (edge supports), GM_TC_CORE_H / GM_SUP_CORE_H (hub corner),
-//   GM_BIG_NE, GM_KST_MAX_KEYS, GM_TOPO_MIN_ROW, GM_WIDE_ARENA_MB, GM_TCT_SPLIT_ALWAYS, GM_TCH_WIDE_NE, GM_RECT_LDS_MIN / GM_RECT_LDS_RANGES / GM_WRECT_RANGE (limits lowered for tests), GM_ORIENT_TWO_GATHERS,
+//   GM_BIG_NE, GM_KST_MAX_KEYS, GM_TOPO_MIN_ROW, GM_WIDE_ARENA_MB, GM_TCT_SPLIT_ALWAYS, GM_TCH_WIDE_NE, GM_RECT_LDS_MIN / GM_RECT_LDS_RANGES / GM_WRECT_RANGE / GM_RECT_LOCAL_RANGE (limits lowered for tests), GM_ORIENT_TWO_GATHERS,
 //   GM_RELABEL_GLOBAL_SORT (the previous setup paths, compared in tests), GM_NO_TEMP_POOL, and the n-GPU runner's GM_FORCE_RCCL_PATH /
 //   GM_DIAMOND_SUPPORTS_MAX_WORLD (host/multi.cc).  Only GM_SETUP_TRACE (setup steps on stderr: diagnostics, no algorithm) is an
 //   environment variable.  In -DGM_DEVEL builds (make DEVEL=1) an option that is not set falls back to the environment, and the
@@ -666,6 +666,37 @@ int wrect_per_cu();
 hipError_t launch_wrect(const WrectParams &p, int grid_blocks, hipStream_t stream);
 hipError_t launch_wrect_mask(int nv, const int *rp, const int *col, int range, int grp, unsigned long long *rmask, int cu_count, hipStream_t stream);
 hipError_t launch_sgl6_sums(const Sgl6EntryParams &p, int cu_count, hipStream_t stream);
+// local 4-cycle counts (gm_rect_local.hip, gm_rect_local): wrect_kernel's pruned walk made twice per (centre, range of ids) -- count the
+// 2-paths c(x) of every end in LDS, then credit c(x) - 1 to the entry of every 2-path edge -- with one 32-bit counter per id of the range.
+// Exported through gm_constant ("rect_local_range", "rect_local_one_task", "rect_local_long_row"): the tests place centres and rows on both
+// sides of each of them.
+constexpr int kRectLocalRange = 4096;  // ids of one LDS range (16 KB of counters; GM_RECT_LOCAL_RANGE lowers it for tests)
+constexpr int kRectLocalWaves = 4;
+constexpr int kRectLocalThreads = kRectLocalWaves * 64;  // a centre with at most this many neighbours below it is ONE task (a row per thread): the plan and the kernel share it
+constexpr int kRectLocalLong = 64;     // keys of a row inside the range from which the wave strides the row on its own
+struct RectLocalParams {
+  const int *rp, *col;              // the graph the walk runs on (rows ascending)
+  const int *idx0;                  // per vertex: its neighbours below it
+  const unsigned long long *rmask;  // per vertex: bit j = the row has a key in the ranges [j grp, (j + 1) grp) (wrect_mask_kernel)
+  int range, grp;                   // ids per range (<= kRectLocalRange); ranges per bit of rmask
+  const int2 *tasks;                // {centre, range} or {centre, -1} = every range of a centre of at most kRectLocalThreads neighbours below it
+  unsigned long long count;
+  unsigned long long *queue;
+  unsigned long long *acc;          // per entry of that graph (zeroed by the caller): += the 4-cycles credited to it
+};
+struct RectLocalMapParams {
+  int nv;
+  long long ne;
+  const int *rp, *col;              // the caller's symmetric CSR
+  const int *newid;                 // caller's id -> id of the graph the walk ran on (nullptr: the same ids)
+  const int *drp, *dcol;            // that graph
+  const unsigned long long *acc;    // its credits, one per entry: an edge's 4-cycles are the sum over its two entries
+  unsigned long long *out;          // per caller's entry: the 4-cycles of its edge
+  unsigned long long *sum;          // [0] += the sum of out[] (8 R)
+};
+int rect_local_per_cu();
+hipError_t launch_rect_local(const RectLocalParams &p, int grid_blocks, hipStream_t stream);
+hipError_t launch_rect_local_map(const RectLocalMapParams &p, int cu_count, hipStream_t stream);
 // local counts and the k-truss (gm_local.hip): the supports of the oriented copy back at the caller's entries, the triangles per vertex, and
 // the peeling rounds on the symmetric graph
 template <class V>  // the value per entry: unsigned = a support (gm_tc_local, the k-truss), unsigned long long = a k-clique count (gm_clique_local)

@@ -1,6 +1,6 @@
-// gm_solve_local.hip -- local counts, the k-truss, the triangle listing and the local k-clique counts over the launch layer (gm_launch.h):
-// gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local.  Host code only: the kernels are gm_local.hip's, gm_list.hip's and
-// gm_kcl_local.hip's, so this unit has no code object and no warm-up.
+// gm_solve_local.hip -- local counts, the k-truss, the triangle listing, the local k-clique and 4-cycle counts over the launch layer (gm_launch.h):
+// gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_rect_local.  Host code only: the kernels are gm_local.hip's,
+// gm_list.hip's, gm_kcl_local.hip's and gm_rect_local.hip's, so this unit has no code object and no warm-up.
 #include "gm_launch.h"
 
 // ---- local counts and the k-truss (gm_local.hip; DESIGN.md "Local counts and k-truss") ----------------------------------------------------
@@ -169,6 +169,94 @@ extern "C" int gm_clique_local(const gm_graph *sym, int k, const gm_launch *la, 
   if (total) *total = out[0] / ((uint64_t)k * (uint64_t)(k - 1));  // sum_e K_e over both directions = k (k - 1) K
   if (st) {
     st->kernel_ms = s.kernel_ms;
+    st->grid = (uint32_t)grid;
+  }
+  return GM_OK;
+}
+
+// ---- local 4-cycle counts (gm_rect_local.hip; DESIGN.md "Local 4-cycle counts") -----------------------------------------------------------
+// The credits of every entry of the graph the walk runs on -- the copy numbered ascending in degree (the one run_wrect takes), or the handle
+// itself (tune[6] & GM_T6_AS_NUMBERED) -- into run_on->local.racc, then back: the mapping kernel sums the two entries of an edge into the
+// caller's entry order, the row sums / 2 per vertex.  The plan is built once per graph that runs it: GM_RECT_LOCAL_RANGE (ids per LDS
+// range, default and limit kRectLocalRange) is read then.
+extern "C" int gm_rect_local(const gm_graph *sym, const gm_launch *la, uint64_t *d_vertex_cnt, uint64_t *d_entry_cnt, uint64_t *total, gm_stats *st) {
+  if (total) *total = 0;
+  if (int rc = local_refusals(sym, la)) return rc;
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kRectLocalThreads);
+  uint64_t out[4] = {0, 0, 0, 0};
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, out, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+  if (sym->ne == 0) {
+    if (d_vertex_cnt && sym->nv > 0) HIP_TRY(hipMemsetAsync(d_vertex_cnt, 0, sizeof(uint64_t) * (size_t)sym->nv, ctx.stream));
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    return GM_OK;
+  }
+  gm_graph *run_on = g;
+  if (!(l2.tune[6] & GM_T6_AS_NUMBERED)) {
+    if (int rc = get_relabeled(g, 0, &run_on)) return rc;
+    if (!run_on->d_newid) return GM_ERR_INVALID;  // (a renumbered copy always remembers its numbering)
+  }
+  if (int rc = ensure_idx0(run_on, graph_view(run_on))) return rc;
+  if (const int rc = run_on->rect_local.ensure(run_on->mu, [&](RectLocalPlan &rl) {  // (two first calls on one handle: one builds, the other waits)
+        OtherSetupScope scope(run_on);
+        const size_t nv = (size_t)run_on->nv;
+        int range = kRectLocalRange;
+        if (const char *e = gm_opt("GM_RECT_LOCAL_RANGE")) range = std::max(16, std::min(kRectLocalRange, std::atoi(e)));
+        const long long nranges = std::max<long long>(1, ((long long)run_on->nv + range - 1) / range);
+        rl.range = range;
+        rl.grp = (int)((nranges + 63) / 64);
+        HIP_TRY(rl.mask.alloc(sizeof(unsigned long long) * std::max<size_t>(nv, 1)));
+        HIP_TRY(launch_wrect_mask(run_on->nv, run_on->d_rp, run_on->d_col, range, rl.grp, rl.mask, run_on->cu_count, 0));
+        std::vector<int> idx0h(std::max<size_t>(nv, 1));
+        if (nv) HIP_TRY(hipMemcpy(idx0h.data(), run_on->rect_idx->idx0, sizeof(int) * nv, hipMemcpyDeviceToHost));
+        const std::vector<int2> tasks = wrect_tasks(idx0h.data(), nv, range, kRectLocalThreads);  // (the hubs' per-range tasks first)
+        rl.n_tasks = tasks.size();
+        HIP_TRY(rl.tasks.alloc(sizeof(int2) * std::max<size_t>(tasks.size(), 1)));
+        if (!tasks.empty()) HIP_TRY(hipMemcpy(rl.tasks, tasks.data(), sizeof(int2) * tasks.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipDeviceSynchronize());
+        return kOnceBuilt;
+      })) return rc;
+  const size_t dne = (size_t)std::max<long long>(run_on->ne, 1);
+  {
+    std::lock_guard<std::mutex> lk(run_on->mu);
+    if (!run_on->local.racc) HIP_TRY(run_on->local.racc.alloc(sizeof(unsigned long long) * dne));
+  }
+  if (!d_entry_cnt) {
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (!g->local.ent64) HIP_TRY(g->local.ent64.alloc(sizeof(unsigned long long) * (size_t)g->ne));
+  }
+  HIP_TRY(hipMemsetAsync(g->d_counters, 0, kCounterBlockBytes, ctx.stream));  // (a first call renumbered the graph since begin_launch)
+  if (int rc = start_timer(ctx)) return rc;
+  HIP_TRY(hipMemsetAsync(run_on->local.racc, 0, sizeof(unsigned long long) * dne, ctx.stream));
+  const RectLocalPlan &plan = *run_on->rect_local;
+  RectLocalParams p;
+  memset(&p, 0, sizeof p);
+  p.rp = run_on->d_rp; p.col = run_on->d_col; p.idx0 = run_on->rect_idx->idx0;
+  p.rmask = plan.mask; p.range = plan.range; p.grp = plan.grp;
+  p.tasks = plan.tasks; p.count = plan.n_tasks;
+  p.queue = queue_word64(g, QW64_MAIN);
+  p.acc = run_on->local.racc;
+  const int grid = grid_for((long long)p.count, g->cu_count, rect_local_per_cu());
+  if (p.count > 0) HIP_TRY(launch_rect_local(p, grid, ctx.stream));
+  RectLocalMapParams mp;
+  memset(&mp, 0, sizeof mp);
+  mp.nv = g->nv; mp.ne = g->ne; mp.rp = g->d_rp; mp.col = g->d_col;
+  mp.newid = run_on != g ? run_on->d_newid.get() : nullptr;
+  mp.drp = run_on->d_rp; mp.dcol = run_on->d_col; mp.acc = run_on->local.racc;
+  unsigned long long *ent = d_entry_cnt ? (unsigned long long *)d_entry_cnt : g->local.ent64.get();
+  mp.out = ent; mp.sum = g->d_counters;
+  HIP_TRY(launch_rect_local_map(mp, g->cu_count, ctx.stream));
+  // (every 4-cycle at v uses two of v's entries)
+  if (d_vertex_cnt) HIP_TRY(launch_local_vertices(g->nv, g->d_rp, ent, 2u, (unsigned long long *)d_vertex_cnt, g->cu_count, ctx.stream));
+  gm_stats s;
+  memset(&s, 0, sizeof s);
+  if (int rc = end_launch(ctx, FIN_RAW4, 0, out, 4, &s)) return rc;
+  if (total) *total = out[0] / 8ull;  // sum_e R_e over both directions = 2 sum_v R_v = 8 R
+  if (st) {
+    st->kernel_ms = s.kernel_ms;
+    st->chunks = (uint64_t)p.count;
     st->grid = (uint32_t)grid;
   }
   return GM_OK;

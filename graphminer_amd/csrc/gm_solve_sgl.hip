@@ -44,7 +44,7 @@ static int build_centre_tasks(gm_graph *g, WorkLaunch work_launch, const char *w
 }
 
 // rectangle, flattened over wedges (rect_flat_kernel in gm_mine.hip)
-static int ensure_idx0(gm_graph *g, const GraphView &gv) {
+int ensure_idx0(gm_graph *g, const GraphView &gv) {
   return g->rect_idx.ensure(g->mu, [&](RectIdx &ri) {
     OtherSetupScope scope(g);
     HIP_TRY(ri.idx0.alloc(sizeof(int) * (size_t)std::max(g->nv, 1)));

@@ -149,6 +149,7 @@ extern "C" int gm_constant(const char *name, int64_t *value) {
               {"wide_max_deg", kWideMaxDeg},           {"bit_words", kBitWords},
       {"kcl_local_lds_row", kKclLocalLdsRow}, {"kcl_local_regs2_row", kKclLocalRegs2Row}, {"kcl_local_regs8_row", kKclLocalRegs8Row}, {"kcl_local_regs12_row", kKclLocalRegs12Row},
       {"kcl_local_split_row", kKclLocalSplitRow},
+      {"rect_local_range", kRectLocalRange}, {"rect_local_one_task", kRectLocalThreads}, {"rect_local_long_row", kRectLocalLong},
   };
   for (const auto &e : tab)
     if (strcmp(e.name, name) == 0) {

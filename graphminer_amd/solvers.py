@@ -291,6 +291,22 @@ def clique_local(g: DeviceGraph, k: int, *, vertex=True, entries=True, chunk=0, 
     return (*res, _stats(st)) if return_stats else res
 
 
+# ---- local 4-cycle counts (include/graphminer_amd.h: gm_rect_local) -----------------------------------------------------------------------
+def rect_local(g: DeviceGraph, *, vertex=True, entries=True, chunk=0, return_stats=False, **kw):
+    """(total, R_v as np.uint64[nv] or None, R_uv per entry as np.uint64[ne] or None) of a SYMMETRIC graph, in the caller's numbering and
+    entry order: R_v the 4-cycles that contain v, R_uv the 4-cycles that contain the edge of entry (u, v); total = the `rectangle` count.
+    One GPU."""
+    import torch
+
+    la, st, total = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0)
+    rv = _dev_array(g, g.nv, torch.int64) if vertex else None
+    re = _dev_array(g, g.ne, torch.int64) if entries else None
+    _lib.check(_lib.load().gm_rect_local(g.handle, C.byref(la), rv.data_ptr() if vertex else None, re.data_ptr() if entries else None,
+                                         C.byref(total), C.byref(st)), "gm_rect_local")
+    res = (int(total.value), _to_numpy(rv, g.nv, "uint64") if vertex else None, _to_numpy(re, g.ne, "uint64") if entries else None)
+    return (*res, _stats(st)) if return_stats else res
+
+
 # ---- triangle listing (include/graphminer_amd.h: gm_tc_list) ------------------------------------------------------------------------------
 def tc_list(g: DeviceGraph, *, first=0, cap=None, chunk=0, return_stats=False, **kw):
     """(total, triangles as np.int32[n_written, 3]) of a SYMMETRIC graph: rows a < b < c in the caller's numbering, every triangle once, in

@@ -408,6 +408,29 @@ int gm_clique(const gm_graph *dag, int k, const gm_launch *launch, uint64_t *tot
 int gm_clique_local(const gm_graph *sym, int k, const gm_launch *launch, uint64_t *d_vertex_cnt, uint64_t *d_entry_cnt, uint64_t *total,
                     gm_stats *stats);
 
+/* ---- local 4-cycle counts (csrc/gm_rect_local.hip; DESIGN.md "Local 4-cycle counts") --------------------------------------------------
+ * The 4-cycles (edge-induced, as the `rectangle` of gm_sgl counts them: src/sgl/cpu_kernels/rectangle.h) at every vertex and on every
+ * edge, in the CALLER's numbering and entry order: the input of square clustering coefficients, of butterfly supports on bipartite data,
+ * of the 4-vertex orbit counts.  SYMMETRIC graph with ascending rows, as for the local triangle counts.
+ *   d_vertex_cnt: DEVICE uint64[nv] or NULL -- R_v, the 4-cycles that contain v (half the sum of row v of the entry counts: a 4-cycle
+ *                 at v uses two of v's entries).
+ *   d_entry_cnt:  DEVICE uint64[ne] or NULL -- for entry i = (u, v) of row u: R_uv, the 4-cycles that contain the edge; the two
+ *                 directions of an edge are equal.
+ *   total (may be NULL): the 4-cycle count, sum of the entries / 8 = sum_v R_v / 4; equal to gm_sgl("rectangle").
+ * All arithmetic is uint64 modulo 2^64 and integer: the results do not depend on the launch or on the order in which the workgroups arrive.
+ * The kernel makes the pruned walk of the 6-vertex closed forms' 4-cycle kernel twice per centre and range of ids -- count the 2-paths of
+ * every end in LDS, then credit every 2-path edge -- with one 64-bit atomic per 2-path whose end has at least two, and one per spoke.
+ * By default the call runs on the copy numbered ascending in degree (cached on the handle, the copy gm_sgl6_raw's Z runs on).
+ * launch->tune[6] & GM_T6_AS_NUMBERED: on the graph as given.  The counts are the same on both.  gm_dev_option("GM_RECT_LOCAL_RANGE", ..),
+ * read when a graph's plan is built: ids per LDS range, 16 up to the default (gm_constant "rect_local_range").
+ * The contract of the local counts above: one GPU, synchronous; a null handle -> GM_ERR_INVALID, >= 2^31 entries -> GM_ERR_TOO_LARGE,
+ * world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED, unsorted rows -> GM_ERR_INVALID, ne == 0 -> GM_OK with zeros (d_vertex_cnt is
+ * zeroed when given); launch->stream is honoured; stats->kernel_ms covers every kernel of the call, stats->tasks = the directed
+ * entries, stats->chunks = the (centre, range) tasks; before or after any other solver on the handle, whose arrays it leaves alone; ONE
+ * such call at a time per handle; every array it keeps on the handle is freed with the handle. */
+int gm_rect_local(const gm_graph *sym, const gm_launch *launch, uint64_t *d_vertex_cnt, uint64_t *d_entry_cnt, uint64_t *total,
+                  gm_stats *stats);
+
 /* MotifSolver on the SYMMETRIC graph. k = 3: counts[0] = wedges, counts[1] = triangles
  * (the CPU order, src/motif/cpu_kernels/automine_base.h:13,18; NOT the swapped order of
  * src/motif/gpu_kernels/motif3_edge_warp.cuh:19-22). ncounts must be
