@@ -122,6 +122,7 @@ SYMBOLS = [
     ("gm_tc_pairs_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("gm_tc_pair_rule", C.c_int, [_P, C.c_int, C.c_int, C.c_uint64, _P]),
     ("gm_sup_core_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("gm_map_plan_info", C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64), C.c_int]),
     ("gm_diamond_support_partial", C.c_int, [_P, C.POINTER(gm_launch), _P, C.c_int64, C.POINTER(gm_stats)]),
     ("gm_diamond_support_finish", C.c_int, [_P, C.POINTER(gm_launch), _P, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
     ("gm_constant", C.c_int, [C.c_char_p, C.POINTER(C.c_int64)]),

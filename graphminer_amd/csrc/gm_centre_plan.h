@@ -1,6 +1,9 @@
 // gm_centre_plan.h -- the once-per-graph plans of the map solvers (rectangle / house by wedge accumulation, the weighted 4-cycles) as pure
 // functions of host arrays: no HIP runtime, no globals, no developer options (gm_solve_sgl.hip reads those and builds the device side).  A slip
-// here costs time, not counts, so no parity test sees it: tests/centre_plan_host_check.cc checks them with a plain host compiler.
+// in the ORDER or the grouping of the tasks costs time, not counts, so no parity test sees it: tests/centre_plan_host_check.cc checks them
+// with a plain host compiler.  The counter widths lb[] of rect_lds_ranges and the row limits that choose a field width are another matter: one
+// step too narrow and a counter carries into the field of the neighbouring end -- a wrong count.  The host check holds every range's lb against
+// the degrees of the blocks it covers, and tests/test_gpu_map_kernels.py puts counters on the last value of every width.
 #pragma once
 #include <hip/hip_vector_types.h>
 
@@ -8,6 +11,10 @@
 #include <vector>
 
 namespace gm {
+
+// house_lds_kernel, a one-task centre: up to this many neighbours its ends count in 6 + 10-bit fields (n <= 32, S <= 32 * 31 = 992 < 2^10), two to a
+// word and four ranges per walk; above it 11 + 21-bit fields, two ranges per walk.  The kernel and house_lds_min_of below read the same constant.
+constexpr int kHouseFw16Rows = 32;
 
 // The tasks of the map kernels (rect_acc_kernel / pent_acc_kernel / house_acc_kernel) from centres ordered heaviest first: a centre with at
 // least `heavy` 2-paths gets a whole workgroup (a task of its own), the light ones go four to a task
@@ -57,7 +64,7 @@ inline int house_lds_ranges(long long nv, int ids, int max_ranges, int *cut) {
 // 111 walks -- the fixed 4096 made the house 1.27 x SLOWER than the global maps.)  A developer option that sets the threshold is taken as given.
 inline unsigned long long house_lds_min_of(int degree, int n_ranges, unsigned long long lds_min, bool lds_min_given, unsigned long long per_walk, int per_wg) {
   if (lds_min_given || degree > per_wg) return lds_min;
-  const int per = degree <= 32 ? 4 : 2;  // ranges per walk (house_lds_kernel: 16-bit counters up to 32 neighbours)
+  const int per = degree <= kHouseFw16Rows ? 4 : 2;  // ranges per walk (house_lds_kernel: 16-bit counters up to kHouseFw16Rows neighbours)
   return std::max<unsigned long long>(lds_min, per_walk * (unsigned long long)((n_ranges + per - 1) / per));
 }
 struct CentreTasks {

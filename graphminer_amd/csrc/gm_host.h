@@ -295,6 +295,8 @@ struct CentrePlan {             // once per graph, published whole
   DevOwn<int4> d_acc_tasks;     // the "cut" list: first n_cut tasks walk only ends below cut
   unsigned long long n_lds_tasks = 0, n_acc_tasks = 0, n_cut = 0;
   int cut = 0, bnd_stride = 0;
+  // what the lists hold, for gm_map_plan_info: {v, k} / {v, -1} LDS tasks; whole-workgroup acc tasks in the front / in the whole list
+  unsigned long long n_lds_range = 0, n_lds_whole = 0, n_front_heavy = 0, n_acc_heavy = 0;
 };
 
 // ------------------------------------------------------------------------------------------------

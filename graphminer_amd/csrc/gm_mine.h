@@ -266,6 +266,17 @@ hipError_t launch_rect_acc(const RectAccParams &p, int grid_blocks, hipStream_t 
 constexpr int kRectLdsWords = GM_RECT_LDS_WORDS;  // 128 KB of counters
 constexpr int kRectLdsRanges = 32;    // at most
 constexpr int kRectLdsWaves = 16;
+#ifndef GM_RECT_LDS_TILES
+#define GM_RECT_LDS_TILES 8
+#endif
+constexpr int kRectLdsTiles = GM_RECT_LDS_TILES;  // tiles of 64 keys requested together by a wave of rect_lds_kernel
+#ifndef GM_RECT_LDS_LONG
+#define GM_RECT_LDS_LONG 64
+#endif
+constexpr int kRectLdsLong = GM_RECT_LDS_LONG;  // keys of a row inside the range from which the wave takes the row on its own
+// Exported through gm_constant ("map_rect_block", "map_one_task_rows", "map_long_row", "map_tile_group", "map_mark_window", "map_house_ids",
+// "map_house_wg_row", "map_house_wg_queue", "map_heavy_centre", "map_house_fw16_rows", "map_lds_min_default", "map_house_walk_min_default"): tests/map_probe_graphs.py places counters, rows and
+// centres on both sides of each.
 struct RectLdsRanges {
   int n;                          // ranges in use
   int rb[kRectLdsRanges + 1];     // range k = ids [rb[k], rb[k + 1]), ascending; rb[0] = cut, rb[n] = nv
@@ -311,6 +322,10 @@ struct HouseAccParams {
 // word each -- the same packing as the global maps -- from the last id down; tasks as for the rectangle (RectLdsParams)
 constexpr int kHouseLdsIds = 16384;  // 128 KB of 64-bit counters
 constexpr int kHouseLdsRanges = 256;  // at most: the last 4 M ids (and a row-bound table of at most 4 GB: gm_solve_sgl.hip)
+constexpr int kHouseLongQ = 192, kHouseLongWg = 1024;  // house_lds_kernel, one-task centres: queue entries; keys from which a row is shared out
+constexpr unsigned long long kMapLdsMinDefault = 4096;   // GM_RECT_LDS_MIN where no option is given: 2-paths from which a centre counts in the LDS maps
+constexpr unsigned long long kHouseWalkMinDefault = 200;  // GM_HOUSE_WALK_MIN likewise: 2-paths per walk of a one-task centre of the house (house_lds_min_of)
+constexpr unsigned long long kHeavyCentre = 1ull << 15;  // 2-paths above which a centre of the map kernels gets a whole workgroup (emit_centre_tasks, gm_centre_plan.h)
 struct HouseLdsRanges {
   int n, cut, nv;  // range k = ids [rb(k), rb(k + 1)), ascending; rb(0) = cut, rb(n) = nv
   __host__ __device__ int rb(int k) const {

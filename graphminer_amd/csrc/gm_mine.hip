@@ -25,6 +25,7 @@
 //  * k-clique keeps the candidate sets as an LDS bit-matrix over N+(u) (row = edge (u,v1), bit j =
 //    N+(u)[j] in N+(v1)); deeper DFS levels are popcounts of row ANDs without touching HBM.
 #include "gm_chunk.h"
+#include "gm_centre_plan.h"  // kHouseFw16Rows
 
 namespace gm {
 
@@ -245,10 +246,6 @@ __global__ __launch_bounds__(256) void rect_acc_kernel(const RectAccParams p) {
 // below v0, the entries of row x inside the range come from a table of row bounds (bnd: one binary search per (x, range boundary), once per
 // graph), every 2-path is ONE non-returning LDS atomic into a dense map, and sum C(c, 2) is taken when the map is read back and cleared.
 // The ends below cut stay with rect_acc_kernel (RectAccParams::cut).  Same count: rectangle.h:1-11 as restated above rect_work_kernel.
-#ifndef GM_RECT_LDS_TILES
-#define GM_RECT_LDS_TILES 8
-#endif
-constexpr int kRectLdsTiles = GM_RECT_LDS_TILES;  // tiles of 64 keys requested together by a wave of rect_lds_kernel
 struct alignas(16) WaveLdsFlat {  // what flat_pass<SEARCH_NONE> uses of the per-wave scratch
   int4 desc[GM_WAVE];
   unsigned char marks[kMarkWindow];
@@ -356,11 +353,6 @@ __global__ __launch_bounds__(256) void rect_work_cut_kernel(GraphView g, const i
   work[v] = w;
   work[(size_t)g.nv + (size_t)v] = wc;
 }
-
-#ifndef GM_RECT_LDS_LONG
-#define GM_RECT_LDS_LONG 64
-#endif
-constexpr int kRectLdsLong = GM_RECT_LDS_LONG;  // keys of a row inside the range from which the wave takes the row on its own
 
 __global__ __launch_bounds__(kRectLdsWaves *GM_WAVE) void rect_lds_kernel(const RectLdsParams p) {
   __shared__ RectLds S;
@@ -763,7 +755,6 @@ __global__ __launch_bounds__(256) void house_acc_kernel(const HouseAccParams p) 
 // EVERY 2-path of every centre (sum_x d(x)^2: 70 G on R-MAT-20 ef 16, 3.6 s at the rate of the L2 atomics), so the scheme of rect_lds_kernel
 // pays even more: ranges of 16 K ids (one 64-bit LDS word each) from the last id down, (centre, range) tasks for the centres with more
 // neighbours than a workgroup has threads, one task for all ranges of the others; what lies below the ranges stays with house_acc_kernel.
-constexpr int kHouseLongQ = 192, kHouseLongWg = 1024;  // queue entries; keys from which a row is shared out
 struct alignas(16) HouseLds {
   unsigned long long map[kHouseLdsIds];
   WaveLdsFlat w[kRectLdsWaves];
@@ -978,7 +969,7 @@ __global__ __launch_bounds__(kRectLdsWaves *GM_WAVE) void house_lds_kernel(const
       // (at most 32 neighbours: n <= 32 and S <= 32 * 31 fit 6 + 10 bits -- 16-bit counters, two to a word, FOUR ranges per walk: most
       // one-task centres are low-degree vertices beside a hub, and what a walk costs them is its ~2.5 us, not its keys)
       unsigned *map32 = reinterpret_cast<unsigned *>(S.map);
-      const bool fw16 = nitems <= 32;
+      const bool fw16 = nitems <= kHouseFw16Rows;
       const int rw = fw16 ? 4 : 2;                // ranges per walk
       const unsigned nb = fw16 ? 6u : 11u;        // bits of n in a counter
       const unsigned nm = (1u << nb) - 1u, fm = fw16 ? 0xffffu : 0xffffffffu;

@@ -3,7 +3,6 @@
 // here, so the unit has no code object and no warm-up.  Reference launch logic: src/sgl/gpu_base.cu:37-75.
 #include "gm_launch.h"
 
-constexpr unsigned long long kHeavyCentre = 1ull << 15;  // 2-paths above which a centre of the map kernels gets a whole workgroup (emit_centre_tasks, gm_centre_plan.h)
 // a host vector as a fresh device array (of at least one element)
 template <class T>
 static int upload(DevOwn<T> &d, const std::vector<T> &h) {
@@ -107,6 +106,12 @@ static int upload_centre_tasks(const CentreTasks &t, CentrePlan &pl) {
   pl.n_acc_tasks = t.acc_tasks.size();
   pl.n_lds_tasks = t.lds_tasks.size();
   pl.n_cut = t.n_cut;
+  for (const int2 &l : t.lds_tasks) ++(l.y >= 0 ? pl.n_lds_range : pl.n_lds_whole);
+  for (size_t i = 0; i < t.acc_tasks.size(); ++i)
+    if (t.acc_tasks[i].y == -2) {
+      ++pl.n_acc_heavy;
+      if (i < t.n_cut) ++pl.n_front_heavy;
+    }
   return GM_OK;
 }
 static int max_lds_ranges(int limit) {
@@ -120,7 +125,7 @@ static int ensure_rect_plan(gm_graph *g, const GraphView &gv) {  // (after ensur
   return g->rect_lds.ensure(g->mu, [&](RectLdsPlan &out) {
     OtherSetupScope scope(g);
     const size_t nv = (size_t)g->nv;
-    unsigned long long lds_min = 4096;
+    unsigned long long lds_min = kMapLdsMinDefault;
     if (const char *e = gm_opt("GM_RECT_LDS_MIN")) lds_min = std::strtoull(e, nullptr, 10);
     const int nblk = (int)((nv + kRectLdsWords - 1) / kRectLdsWords);
     std::vector<int> bmax((size_t)std::max(nblk, 1), 0);
@@ -157,7 +162,7 @@ static int ensure_house_plan(gm_graph *g, const GraphView &gv) {
     OtherSetupScope scope(g);
     const size_t nv = (size_t)g->nv;
     const char *lds_min_given = gm_opt("GM_RECT_LDS_MIN");
-    const unsigned long long lds_min = lds_min_given ? std::strtoull(lds_min_given, nullptr, 10) : 4096;
+    const unsigned long long lds_min = lds_min_given ? std::strtoull(lds_min_given, nullptr, 10) : kMapLdsMinDefault;
     HouseLdsRanges &rr = out.ranges = HouseLdsRanges{0, 0, g->nv};
     rr.n = house_lds_ranges((long long)g->nv, kHouseLdsIds, max_lds_ranges(kHouseLdsRanges), &rr.cut);
     CentrePlan &pl = out.plan;
@@ -170,7 +175,7 @@ static int ensure_house_plan(gm_graph *g, const GraphView &gv) {
     std::vector<int> deg(nv + 1, 0);  // (the offsets, then their differences)
     if (nv) HIP_TRY(hipMemcpy(deg.data(), g->d_rp, sizeof(int) * (nv + 1), hipMemcpyDeviceToHost));
     for (size_t v = 0; v < nv; ++v) deg[v] = deg[v + 1] - deg[v];
-    unsigned long long per_walk = 200;
+    unsigned long long per_walk = kHouseWalkMinDefault;
     if (const char *e = gm_sweep_env("GM_HOUSE_WALK_MIN")) per_walk = std::strtoull(e, nullptr, 10);
     const CentreTasks tasks = plan_house_tasks(nv, est.data(), est.data() + nv, deg.data(), rr.n, lds_min, lds_min_given != nullptr, per_walk, kRectLdsWaves * GM_WAVE, kHeavyCentre);
     if (int rc = upload_centre_tasks(tasks, pl)) return rc;
@@ -497,6 +502,35 @@ extern "C" int gm_sup_core_info(const gm_graph *sym, int64_t info[4]) {
   }
   info[2] = nb * (nb + 1) / 2;           // pairs of 256-row blocks of the product
   info[3] = on ? (run_on->tasklists->core_h >> 9) : 0;  // 512-column chunks of a row
+  return GM_OK;
+}
+// tooling (tests): the plan the rectangle / the house of this handle built for its LDS maps (after a first gm_sgl of that pattern with the
+// maps in LDS), on the copy that call ran on: the handle the most recent call was recorded on where it holds the plan, else the handle itself
+// (the house; the rectangle under GM_T6_AS_NUMBERED), else its copy numbered ascending in degree.  Read-only: nothing is built here.
+//   out[0] ranges n   [1] cut   [2] {v, k} LDS tasks   [3] {v, -1} LDS tasks   [4] front acc tasks (n_cut)   [5] whole-workgroup acc tasks
+//   [6] four-to-a-task acc tasks   [7] whole-workgroup tasks among the front;   the rectangle: [8 .. 8 + n] rb[0 .. n], then lb[0 .. n)
+extern "C" int gm_map_plan_info(const gm_graph *sym, const char *pattern, int64_t *out, int n) {
+  if (!sym || !pattern || !out) return GM_ERR_INVALID;
+  const bool is_rect = strcmp(pattern, "rectangle") == 0;
+  if (!is_rect && strcmp(pattern, "house") != 0) return GM_ERR_INVALID;
+  auto has = [&](const gm_graph *g) { return g && (is_rect ? g->rect_lds.built() : g->house_lds.built()); };
+  const gm_graph *on = has(sym->ring_alias) ? sym->ring_alias : has(sym) ? sym : has(sym->relabel_cache[0]) ? sym->relabel_cache[0] : nullptr;
+  if (!on) return GM_ERR_INVALID;  // (no such call yet)
+  const CentrePlan &pl = is_rect ? on->rect_lds->plan : on->house_lds->plan;
+  const int nr = is_rect ? on->rect_lds->ranges.n : on->house_lds->ranges.n;
+  if (n < 8 + (is_rect ? 2 * nr + 1 : 0)) return GM_ERR_INVALID;
+  out[0] = nr;
+  out[1] = pl.cut;
+  out[2] = (int64_t)pl.n_lds_range;
+  out[3] = (int64_t)pl.n_lds_whole;
+  out[4] = (int64_t)pl.n_cut;
+  out[5] = (int64_t)pl.n_acc_heavy;
+  out[6] = (int64_t)(pl.n_acc_tasks - pl.n_acc_heavy);
+  out[7] = (int64_t)pl.n_front_heavy;
+  if (is_rect) {
+    for (int k = 0; k <= nr; ++k) out[8 + k] = on->rect_lds->ranges.rb[k];
+    for (int k = 0; k < nr; ++k) out[9 + nr + k] = on->rect_lds->ranges.lb[k];
+  }
   return GM_OK;
 }
 extern "C" int gm_diamond_support_partial(const gm_graph *sym, const gm_launch *la, uint32_t *d_support, int64_t n_entries, gm_stats *st) {

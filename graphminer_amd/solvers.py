@@ -100,6 +100,32 @@ def SglSolver(g: DeviceGraph, pattern: str, *, rank=0, world=1, chunk=0, return_
     return (int(total.value), _stats(st)) if return_stats else int(total.value)
 
 
+def map_constants() -> dict:
+    """the sizes at which the map kernels of the rectangle / the house change path (gm_constant "map_*"), by their short names"""
+    out = {}
+    for name in ("rect_block", "one_task_rows", "long_row", "tile_group", "mark_window", "house_ids", "house_wg_row", "house_wg_queue",
+                 "heavy_centre", "house_fw16_rows", "lds_min_default", "house_walk_min_default"):
+        v = C.c_int64(0)
+        _lib.check(_lib.load().gm_constant(("map_" + name).encode(), C.byref(v)), "gm_constant")
+        out[name] = int(v.value)
+    return out
+
+
+def map_plan_info(g: DeviceGraph, pattern: str) -> dict:
+    """the plan SglSolver(g, "rectangle" | "house") built for its LDS maps (gm_map_plan_info; after a first such call on this handle), on
+    the copy that call ran on: ranges "n", "cut", the numbers of tasks by kind, and for the rectangle the range bounds "rb" (n + 1 ids) and
+    "lb" (log2 of every range's counter width)"""
+    out = (C.c_int64 * 80)()
+    _lib.check(_lib.load().gm_map_plan_info(g.handle, pattern.encode(), out, 80), "gm_map_plan_info")
+    n = int(out[0])
+    info = {"n": n, "cut": int(out[1]), "lds_range_tasks": int(out[2]), "lds_whole_tasks": int(out[3]), "front_tasks": int(out[4]),
+            "heavy_tasks": int(out[5]), "light_tasks": int(out[6]), "front_heavy_tasks": int(out[7])}
+    if pattern == "rectangle":
+        info["rb"] = [int(out[8 + k]) for k in range(n + 1)]
+        info["lb"] = [int(out[9 + n + k]) for k in range(n)]
+    return info
+
+
 def CliqueSolver(g: DeviceGraph, k: int, *, rank=0, world=1, chunk=0, return_stats=False, **kw):
     """k-clique count on the ORIENTED graph."""
     lib = _lib.load()

@@ -315,6 +315,14 @@ int gm_diamond_support_info(const gm_graph *sym, int64_t info[4]);
  * out: info[0] = H (0: none), info[1] = DAG entries inside the corner, info[2] = pairs of 256-row blocks, info[3] = 512-column chunks per
  * row.  gm_dev_option("GM_SUP_CORE_H", ..) (read when the handle's task lists are built): 0 = off, a multiple of 512 = that H. */
 int gm_sup_core_info(const gm_graph *sym, int64_t info[4]);
+/* Tooling (tests): the plan gm_sgl "rectangle" / "house" built for its LDS maps on this handle -- valid after a first such call with the maps
+ * in LDS, GM_ERR_INVALID before -- read from the copy that call ran on (the copy numbered ascending in degree, or the handle itself: the
+ * house, and the rectangle under GM_T6_AS_NUMBERED).  Read-only.  out[0] = ranges n, [1] = cut (first id of the ranges), [2] = (centre,
+ * range) LDS tasks, [3] = one-task (centre, -1) LDS tasks, [4] = tasks in front of the acc list (LDS centres: their ends below the cut),
+ * [5] = whole-workgroup acc tasks, [6] = four-centres-to-a-task acc tasks, [7] = whole-workgroup tasks among the front; the rectangle then
+ * out[8 .. 8 + n] = the range bounds rb[0 .. n] and out[9 + n .. 9 + 2 n) = log2 of the counter width of every range (3, 4 or 5).
+ * n_out below what is written -> GM_ERR_INVALID; 80 is always enough. */
+int gm_map_plan_info(const gm_graph *sym, const char *pattern, int64_t *out, int n_out);
 int gm_diamond_support_partial(const gm_graph *sym, const gm_launch *launch, uint32_t *d_support, int64_t n_entries, gm_stats *stats);
 int gm_diamond_support_finish(const gm_graph *sym, const gm_launch *launch, const uint32_t *d_support, int64_t count, uint64_t *total,
                               gm_stats *stats);
@@ -519,7 +527,10 @@ int gm_issue_calib(int kind, int waves_per_simd, int iters, double *cycles_per_w
 
 /* Tooling: a kernel constant by name ("tct_stage_max", "topo_min_mean_row", "motif_trim_min_list", "cb_min_deg", "cb_max_deg",
  * "long_list", "stage_cap", "default_chunk", "mma_words_small", "mma_words_big", "wide_max_deg", "bit_words") -- what the byte model
- * of bench.py needs to know about the kernels, read from the headers they are compiled with. GM_ERR_INVALID for an unknown name. */
+ * of bench.py needs to know about the kernels, read from the headers they are compiled with -- and the sizes at which the map kernels of
+ * the rectangle / the house change path, for the tests that place graphs on both sides: "map_rect_block" (ids of a block of 32-bit
+ * counters), "map_one_task_rows", "map_long_row", "map_tile_group", "map_mark_window", "map_house_ids", "map_house_wg_row",
+ * "map_house_wg_queue", "map_heavy_centre", "map_house_fw16_rows", "map_lds_min_default", "map_house_walk_min_default".  GM_ERR_INVALID for an unknown name. */
 int gm_constant(const char *name, int64_t *value);
 
 /* Developer / test options (tooling).  The library reads NO algorithm switch from the environment; the named switches that tests and A/B

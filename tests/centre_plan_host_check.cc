@@ -331,6 +331,41 @@ static void rect_ranges() {
   }
 }
 
+// Seeded random block maxima, nv no multiple of the block: the ranges tile [rb[0], nv) without gap or overlap, and every range's counters
+// hold the largest degree among the blocks it covers -- "degree < 2^(2^lb)" is what keeps a field of rect_lds_kernel from carrying into
+// the next end's (a width one step too narrow is a wrong COUNT, not lost time).  blockmax[b] covers the ids [nv - (b + 1) words, nv - b words).
+static void rect_ranges_random() {
+  std::mt19937 rng(20261020u);
+  auto rnd = [&](int lo, int hi) { return lo + (int)(rng() % (unsigned)(hi - lo + 1)); };
+  const int edge[] = {0, 1, 254, 255, 256, 257, 65534, 65535, 65536, 65537, 1 << 20};
+  for (int draw = 0; draw < 2000; ++draw) {
+    const int words = 1 << rnd(2, 5), max_ranges = rnd(1, 12);
+    const int nblk = rnd(1, 40);
+    const long long nv = (long long)(nblk - 1) * words + rnd(1, words - 1);  // (the lowest block is a partial one)
+    I bmax((size_t)nblk);
+    for (int &b : bmax) b = rnd(0, 2) ? edge[rnd(0, 10)] : rnd(0, 3) ? rnd(0, 300) : rnd(0, 70000);
+    I rb((size_t)max_ranges + 1, -1), lb((size_t)max_ranges, -1);
+    const int n = rect_lds_ranges(nv, bmax, words, max_ranges, rb.data(), lb.data());
+    CHECK(n >= 1 && n <= max_ranges && rb[(size_t)n] == (int)nv && rb[0] >= 0 && (n == max_ranges || rb[0] == 0));
+    for (int k = 0; k < n; ++k) {
+      const int lo = rb[(size_t)k], hi = rb[(size_t)k + 1], w = lb[(size_t)k];
+      CHECK(lo < hi);  // ascending, no overlap; [rb[k], rb[k + 1]) follow each other by construction of the array: no gap
+      CHECK(w >= 3 && w <= 5 && hi - lo <= (words << (5 - w)) && (hi - lo == (words << (5 - w)) || lo == 0));
+      CHECK((nv - hi) % words == 0);  // ranges are whole blocks counted from the top
+      if (lo >= hi) continue;
+      int m = 0;  // largest degree among the blocks that hold an id of [lo, hi)
+      for (long long b = (nv - hi) / words; b <= (nv - 1 - lo) / words; ++b) m = std::max(m, bmax[(size_t)b]);
+      CHECK(w == 5 || (long long)m < (1ll << (1 << w)));
+      if (w == 5) continue;
+      // ... and not wider than the rule asks: the look-ahead window of the next narrower width holds a degree that needs this one
+      int mw = 0;
+      const long long b0 = (nv - hi) / words;
+      for (long long b = b0; b < std::min<long long>(b0 + (w == 4 ? 4 : 0), nblk); ++b) mw = std::max(mw, bmax[(size_t)b]);
+      if (w == 4) CHECK(mw >= 256);
+    }
+  }
+}
+
 static void house_ranges() {
   int cut = -1;
   CHECK(house_lds_ranges(200, 64, 256, &cut) == 4 && cut == 0);
@@ -370,6 +405,7 @@ int main() {
   house_literals();
   random_properties();
   rect_ranges();
+  rect_ranges_random();
   house_ranges();
   house_threshold();
   wrect();
