@@ -178,7 +178,7 @@ __global__ __launch_bounds__(kCtcBWaves *GM_WAVE) void core_tc_block_kernel(cons
     const long long t64 = (long long)p.first + (long long)q * p.step;
     if (t64 >= (long long)p.ntasks) break;
     int IB, JB, piece;
-    if (!SUP && p.tasks != nullptr) {  // the chosen pairs' pieces, longest first (gm_tables.hip tc_pairs_setup)
+    if (!SUP && p.tasks != nullptr) {  // the chosen pairs' pieces, longest first (gm_tasks.hip tc_pairs_setup)
       const unsigned t = p.tasks[t64];
       IB = (int)(t & 255u);
       JB = (int)((t >> 8) & 255u);

@@ -286,6 +286,8 @@ int finish_handle(gm_graph *g) {
     gm_touch_ctc();
     gm_touch_sgl();
     gm_touch_tables();
+    gm_touch_tasks();
+    gm_touch_clique_plan();
     gm_touch_launch();
     gm_touch_tools();
     (void)hipDeviceSynchronize();
@@ -738,9 +740,8 @@ static int orient_impl(const gm_graph *sym, const OffT *rp_in, gm_graph **out) {
   HIP_TRY(nseg_of.alloc((size_t)nv + 1));
   HIP_TRY(seg_first.alloc((size_t)nv + 1));
   hipLaunchKernelGGL((orient_segcount_kernel<OffT>), dim3(vb), dim3(256), 0, 0, nv, rp_in, nseg_of.p);
-  HIP_TRY(dev_exclusive_sum(tmp, nseg_of.p, seg_first.p, (size_t)nv + 1));
   int nseg = 0;
-  HIP_TRY(hipMemcpy(&nseg, seg_first.p + nv, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(dev_scan_total(tmp, nseg_of.p, seg_first.p, (size_t)nv, &nseg));
   HIP_TRY(segs.alloc((size_t)nseg));
   HIP_TRY(segcnt.alloc((size_t)nseg));
   if (nseg) hipLaunchKernelGGL((orient_segfill_kernel<OffT>), dim3(vb), dim3(256), 0, 0, nv, rp_in, seg_first.p, segs.p);
@@ -770,9 +771,8 @@ static int orient_impl(const gm_graph *sym, const OffT *rp_in, gm_graph **out) {
     // the oriented graph of a symmetric graph of >= 2^31 entries: half of them -- checked in 64 bits before the offsets are narrowed
     DevBuf<long long> rp64;
     if ((e = rp64.alloc((size_t)nv + 1)) != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__));
-    if ((e = dev_exclusive_sum(tmp, deg.p, rp64.p, (size_t)nv + 1)) != hipSuccess) return fail(hip_fail(e, "ExclusiveSum", __FILE__, __LINE__));
     long long total = 0;
-    if ((e = hipMemcpy(&total, rp64.p + nv, sizeof(long long), hipMemcpyDeviceToHost)) != hipSuccess) return fail(hip_fail(e, "hipMemcpy", __FILE__, __LINE__));
+    if ((e = dev_scan_total(tmp, deg.p, rp64.p, (size_t)nv, &total)) != hipSuccess) return fail(hip_fail(e, "ExclusiveSum", __FILE__, __LINE__));
     if (total >= 0x7fffffffLL) {
       g_last_error = "gm_graph_orient: the oriented graph has " + std::to_string(total) + " entries (>= 2^31: beyond the 32-bit task index of the mining kernels)";
       return fail(GM_ERR_TOO_LARGE);
@@ -1166,7 +1166,7 @@ int graph_rows_sorted(gm_graph *g, bool *out) {
   return rc;
 }
 
-// "topological" as the task lists use it (an in-edge task streams only the entries BEHIND its own: gm_tables.hip): every edge u -> v has
+// "topological" as the task lists use it (an in-edge task streams only the entries BEHIND its own: gm_tasks.hip): every edge u -> v has
 // u < v AND the rows are ascending (the first entry of a row alone was tested, which says nothing about an unsorted row)
 int graph_is_topological(gm_graph *g, bool *out) {
   bool sorted = false;
@@ -1204,7 +1204,6 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
   const size_t nv1 = (size_t)nv + 1, n1 = (size_t)std::max<long long>(ne, 1);
   PoolScope pool(g);  // (the sort buffers: two 64-bit keys per entry + hipCUB's own)
   setup_trace("relabel: begin");
-  auto blocks = [](long long n) { return dim3((unsigned)std::max<long long>(1, (n + 255) / 256)); };
   ScanTemp tmp;
   DevBuf<int> indeg, newid, newdeg;
   DevBuf<unsigned long long> vkeys, vsorted, keys, sorted;
@@ -1223,14 +1222,11 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
   int bits = 1;
   while (bits < 32 && (1ll << bits) < (long long)nv) ++bits;
   if (nv > 0) {
-    hipLaunchKernelGGL(relabel_vkeys_kernel, blocks(nv), dim3(256), 0, 0, nv, g->d_rp, (mode == 2 && !g->d_symdeg) ? indeg.p : (const int *)nullptr,
+    hipLaunchKernelGGL(relabel_vkeys_kernel, grid_1d(nv), dim3(256), 0, 0, nv, g->d_rp, (mode == 2 && !g->d_symdeg) ? indeg.p : (const int *)nullptr,
                        mode == 2 ? g->d_symdeg : (const int *)nullptr, vkeys.p);
-    size_t bytes = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, vkeys.p, vsorted.p, nv, 0, 64));
-    HIP_TRY(tmp.reserve(bytes));
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp.buf.p, bytes, vkeys.p, vsorted.p, nv, 0, 64));
+    HIP_TRY(dev_sort_keys(tmp, vkeys.p, vsorted.p, (size_t)nv, 0, 64));
   }
-  hipLaunchKernelGGL(relabel_newid_kernel, blocks((long long)nv1), dim3(256), 0, 0, nv, vsorted.p, mode == 1 ? 1 : 0, g->d_rp, newid.p, newdeg.p);
+  hipLaunchKernelGGL(relabel_newid_kernel, grid_1d((long long)nv1), dim3(256), 0, 0, nv, vsorted.p, mode == 1 ? 1 : 0, g->d_rp, newid.p, newdeg.p);
   setup_trace("relabel: vertex sort");
   gm_graph *r = new gm_graph();
   r->device = g->device;
@@ -1287,13 +1283,10 @@ int get_relabeled(gm_graph *g, int mode, gm_graph **out) {
     setup_trace("relabel: rows sorted in LDS");
   } else if (ne > 0) {
     if ((e = keys.alloc(n1)) != hipSuccess || (e = sorted.alloc(n1)) != hipSuccess) return fail(e, "hipMalloc(keys)");
-    hipLaunchKernelGGL(relabel_keys_kernel, blocks((ne + 3) / 4), dim3(256), 0, 0, nv, ne, g->d_rp, g->d_col, newid.p, bits, keys.p);
+    hipLaunchKernelGGL(relabel_keys_kernel, grid_1d((ne + 3) / 4), dim3(256), 0, 0, nv, ne, g->d_rp, g->d_col, newid.p, bits, keys.p);
   setup_trace("relabel: allocations + entry keys");
-    size_t bytes = 0;
-    if ((e = hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, keys.p, sorted.p, (int)ne, 0, 2 * bits)) != hipSuccess) return fail(e, "SortKeys(size)");
-    if ((e = tmp.reserve(bytes)) != hipSuccess) return fail(e, "hipMalloc(sort temp)");
-    if ((e = hipcub::DeviceRadixSort::SortKeys(tmp.buf.p, bytes, keys.p, sorted.p, (int)ne, 0, 2 * bits)) != hipSuccess) return fail(e, "SortKeys");
-    hipLaunchKernelGGL(relabel_cols_kernel, blocks(ne), dim3(256), 0, 0, ne, sorted.p, r->d_col, bits, dupflag.p);
+    if ((e = dev_sort_keys(tmp, keys.p, sorted.p, (size_t)ne, 0, 2 * bits)) != hipSuccess) return fail(e, "SortKeys");
+    hipLaunchKernelGGL(relabel_cols_kernel, grid_1d(ne), dim3(256), 0, 0, ne, sorted.p, r->d_col, bits, dupflag.p);
   }
   setup_trace("relabel: entry sort + columns");
   if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) return fail(e, "relabel kernels");

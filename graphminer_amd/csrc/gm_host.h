@@ -1,6 +1,8 @@
 // gm_host.h -- host-side internals shared by the translation units behind the C ABI (include/graphminer_amd.h):
 //   gm_graph.hip   handle, upload / adopt, orientation, neighbour sort, degree renumbering      (GraphGPU::init, Graph::orientation)
-//   gm_tables.hip  task-chunk tables, edge descriptors, task lists, k-clique plans, partitions  (Graph::init_edgelist, Scheduler)
+//   gm_tables.hip  task-chunk tables, their bitmap sets and rank shares, partitions              (Graph::init_edgelist, Scheduler)
+//   gm_tasks.hip   edge descriptors, task lists, key stream, block-pair rule, support masks / corner of the triangle-count family
+//   gm_clique_plan.hip  the 4-clique plan: wide vertices, core bitmap and its blocks, rounds, gather index
 //   gm_launch.hip  the launch layer (interface: gm_launch.h, for the three solver units only): launch prologue / epilogue, run_pattern,
 //                  gm_kernel_times, gm_tc / gm_clique / gm_motif, and every kernel of the layer
 //   gm_solve_sgl.hip    the SgL family: gm_sgl, the rectangle / house / pentagon map solvers, gm_diamond_support_*, gm_sgl4 / 5 / 6   (host code only)
@@ -48,6 +50,13 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
     hipError_t _e = (call);                                        \
     if (_e != hipSuccess) return hip_fail(_e, #call, __FILE__, __LINE__); \
   } while (0)
+// A step that may fail without the call failing (an optimisation that did not fit): taken before the step, drop() forgets its failure --
+// the runtime's sticky error, and the text and code hip_fail recorded go back to what they were
+struct HipFailureMark {
+  std::string text = g_last_error;
+  int code = g_last_hip_error;
+  void drop() const { (void)hipGetLastError(); g_last_error = text; g_last_hip_error = code; }
+};
 
 // The temporaries of the setup paths (a table build has ~20 of them) come out of ONE device allocation per handle: a bump allocator
 // that a PoolScope opens at the top of a setup function and rewinds at its end. hipMalloc / hipFree cost 0.1-0.3 ms each and hipFree
@@ -131,7 +140,7 @@ struct ScanTemp {  // temp storage of the hipCUB calls, grown on demand
 };
 
 
-// (dev_exclusive_sum, the hipCUB scan over a ScanTemp: gm_scan.h -- only the units that include hipCUB pay for it)
+// (dev_exclusive_sum and the other hipCUB helpers over a ScanTemp: gm_scan.h -- only the units that include hipCUB pay for them)
 
 // estimated work (adjacency entries touched) above which a chunk is cut into parts
 // Rows longer than kBitmapMinDeg get a dense vertex-id bitmap, longest first, within kBitmapBudget bytes: SPLIT chunks
@@ -236,7 +245,7 @@ static inline void chunk_range_of_vertex_share(const ChunkTable *tb, int nv, int
 // dequeue order `which` (0 / 1, or -1 = record order); needs the device twins of the per-record scalars (a device-built table)
 int get_share_order(gm_graph *g, ChunkTable *t, int world, int rank, int policy, int which, const ShareOrder **out);
 
-// k-clique (k = 4): the plan of one rank's share (gm_mine.h "level 1 re-hosted"; built by get_clique_plan, gm_tables.hip).
+// k-clique (k = 4): the plan of one rank's share (gm_mine.h "level 1 re-hosted"; built by get_clique_plan, gm_clique_plan.hip).
 // OWNERS are the vertices whose matrices this rank builds and counts: the vertices of its share of the narrow chunk table + its share
 // of the wide list. The matrix arena is bounded (GM_WIDE_ARENA_MB): a share whose matrices need more is processed in ROUNDS; a round
 // has its own owners, offsets, task lists (every DAG edge of an owner, at the endpoint that hosts it) and host-chunk table.
@@ -304,7 +313,7 @@ struct CentrePlan {             // once per graph, published whole
 // local value under g->mu and the whole value is published at once; readers go through the Once and never see a half-built group.  Every
 // comment says who builds the group and who reads it.
 // ------------------------------------------------------------------------------------------------
-// Task lists of the shorter-list-streams triangle count.  Built by ensure_tasklists (gm_tables.hip); read by plan_pattern / fill_mine_params
+// Task lists of the shorter-list-streams triangle count.  Built by ensure_tasklists (gm_tasks.hip); read by plan_pattern / fill_mine_params
 // (gm_launch.hip), ensure_sup_corner / ensure_sup_masks, gm_sup_corner_info.
 struct TaskLists {
   DevOwn<int> trp;      // row offsets (nv + 1)
@@ -322,13 +331,13 @@ struct TaskLists {
   int skip_from = 0x7fffffff;
 };
 // The symmetric bit matrix of the corner the task lists leave out (core_h / 32 words per row), and first[row][word] = position of the
-// word's first entry inside its row.  Built by ensure_sup_corner (gm_tables.hip); read by launch_pattern (core_tc_block_kernel<true>).
+// word's first entry inside its row.  Built by ensure_sup_corner (gm_tasks.hip); read by launch_pattern (core_tc_block_kernel<true>).
 struct SupCorner {
   DevOwn<unsigned> csym;
   DevOwn<unsigned short> cfirst;
 };
 // MATCH MASKS of the in-edge tasks with long tails: per DAG entry / per task the offset of the task's mask in the arena (64-bit words;
-// kNoMask: the task keeps its atomics), the arena itself (written and read by every launch).  Built by ensure_sup_masks (gm_tables.hip);
+// kNoMask: the task keeps its atomics), the arena itself (written and read by every launch).  Built by ensure_sup_masks (gm_tasks.hip);
 // not applicable: DAG not topological, arena beyond 2^32 words, no room, GM_SUP_NO_MASKS.  Read by plan_pattern / fill_mine_params /
 // launch_pattern and gm_sup_mask_info.
 struct SupMasks {
@@ -342,7 +351,7 @@ struct SupMasks {
 // nv <= 2^24: instead of descriptors that point at copies, the copies ARE the task list of the short lists -- a key stream in host order,
 // every key tagged with its host's low 8 bits (GraphView::kst), offsets per host vertex, and the longer lists as their own task lists
 // (trpl / tdescl).  No descriptor, no row search, no flattening for the short lists: one coalesced load per 64 keys.
-// Built by ensure_keystream (gm_tables.hip), first set; not applicable: ids beyond 24 bits, keys beyond the 32-bit index, GM_TC_NO_KEY_STREAM.
+// Built by ensure_keystream (gm_tasks.hip), first set; not applicable: ids beyond 24 bits, keys beyond the 32-bit index, GM_TC_NO_KEY_STREAM.
 // Read by plan_pattern / fill_mine_params / launch_pattern, gm_tc_core_info / gm_tc_pairs_info.
 struct KeyStream {
   DevOwn<unsigned> kst;  // the stream itself
@@ -374,7 +383,7 @@ struct KeyStream {
   long long pair_info[6] = {0, 0, 0, 0, 0, 0};  // gm_tc_pairs_info
 };
 // The entries of a key stream that was built WITHOUT them, for the edge supports: a second set kst2 / tdescl2 (same offsets, its own order
-// of arrival) with its kst_et / tedgel.  Built by ensure_keystream(g, true) (gm_tables.hip) after the first set; fill_mine_params reads
+// of arrival) with its kst_et / tedgel.  Built by ensure_keystream(g, true) (gm_tasks.hip) after the first set; fill_mine_params reads
 // the second set where it exists, else the first set's own entries.
 struct KeyEntries {
   DevOwn<int2> kst_et;
@@ -383,7 +392,7 @@ struct KeyEntries {
   DevOwn<int2> tdescl2;
 };
 // The rows beyond the stage of the task-list kernels (> kTctStageMax entries): ids and the prefix of their lengths.  Built by
-// ensure_long_rows (gm_tables.hip); read by launch_pattern.
+// ensure_long_rows (gm_tasks.hip); read by launch_pattern.
 struct LongRows {
   DevOwn<int> rows;
   DevOwn<long long> prefix;
@@ -392,7 +401,7 @@ struct LongRows {
 };
 // A topologically numbered DAG: dense adjacency bitmap of its LAST h vertices (the hubs, when the numbering is by degree) -- row v - base
 // holds bit w - base for every edge v -> w.  The rows of the wide vertices' 4-clique matrices whose first endpoint lies in this core are
-// GATHERED from it (gm_cgather.hip), the triangle count takes its corner (gm_ctc.hip).  Built by ensure_core_bitmap (gm_tables.hip); not
+// GATHERED from it (gm_cgather.hip), the triangle count takes its corner (gm_ctc.hip).  Built by ensure_core_bitmap (gm_clique_plan.hip); not
 // applicable: not topological, too small, no room, GM_CORE_H = 0.  Read by tc_core_size / tc_pairs_setup / ensure_core_tri /
 // get_clique_plan, launch_clique_wide / launch_pattern, gm_tc_core_info.
 struct HubCore {
@@ -400,7 +409,7 @@ struct HubCore {
   int h = 0, base = 0;
 };
 // ... and the same bits cut into BLOCKS of consecutive rows for the blocked gather (gm_cgather.hip cgatherb_kernel).  Built by
-// ensure_core_tri (gm_tables.hip); not applicable: no core bitmap, no room.  Read by build_gather_index, launch_clique_wide,
+// ensure_core_tri (gm_clique_plan.hip); not applicable: no core bitmap, no room.  Read by build_gather_index, launch_clique_wide,
 // gm_clique4_gather_info.
 struct CoreBlocks {
   DevOwn<unsigned> tri;     // block images: of every core row the words from its diagonal word on
@@ -409,7 +418,7 @@ struct CoreBlocks {
   DevOwn<int4> blk;         // per block: {first row, rows, image offset, image words}
   int n = 0;
 };
-// k-clique: the wide DAG vertices (clique_is_wide), longest rows first.  Built and read by get_clique_plan (gm_tables.hip).
+// k-clique: the wide DAG vertices (clique_is_wide), longest rows first.  Built and read by get_clique_plan (gm_clique_plan.hip).
 struct WideVerts {
   DevOwn<int> sorted;
   size_t n = 0;
@@ -494,7 +503,7 @@ struct gm_graph {
   DevOwn<int> d_col_mem;
   DevOwn<int> d_symdeg;  // a DAG made by gm_graph_orient: the degrees of the symmetric graph it came from (its topological numbering sorts by them)
   // ---- built on first use, published whole (the group structs above; gm_once.h) ------------------------------------------------------
-  Once<DevOwn<int2>> edesc;  // per CSR entry: {rp[col[e]], degree(col[e])} (ensure_edesc, gm_tables.hip; read by the table / task-list builds and fill_mine_params)
+  Once<DevOwn<int2>> edesc;  // per CSR entry: {rp[col[e]], degree(col[e])} (ensure_edesc, gm_tasks.hip; read by the table / task-list builds and fill_mine_params)
   Once<TaskLists> tasklists;
   Once<SupCorner> sup_corner;
   Once<SupMasks> sup_masks;
@@ -724,6 +733,8 @@ void gm_touch_cgather();
 void gm_touch_ctc();
 void gm_touch_sgl();
 void gm_touch_tables();
+void gm_touch_tasks();
+void gm_touch_clique_plan();
 void gm_touch_launch();
 void gm_touch_tools();
 
@@ -734,17 +745,28 @@ int convert_offsets(const int64_t *rp64, int nv, long long ne, std::vector<int> 
 int get_relabeled(gm_graph *g, int mode, gm_graph **out);  // gm_graph.hip: cached renumbered copy (0 / 1 by degree, 2 topological)
 int graph_is_topological(gm_graph *g, bool *out);
 int graph_rows_sorted(gm_graph *g, bool *out);
-int ensure_long_rows(gm_graph *g);  // (gm_tables.hip) g->long_rows: the rows of more than kTctStageMax entries
-int ensure_core_tri(gm_graph *g);     // (gm_tables.hip) g->core_blocks of a handle with a core bitmap; GM_OK also when not applicable
-int ensure_core_bitmap(gm_graph *g);  // (gm_tables.hip) g->core of a topologically numbered DAG; GM_OK also when not applicable
+int ensure_long_rows(gm_graph *g);  // (gm_tasks.hip) g->long_rows: the rows of more than kTctStageMax entries
+int ensure_core_tri(gm_graph *g);     // (gm_clique_plan.hip) g->core_blocks of a handle with a core bitmap; GM_OK also when not applicable
+int ensure_core_bitmap(gm_graph *g);  // (gm_clique_plan.hip) g->core of a topologically numbered DAG; GM_OK also when not applicable
 int get_table(gm_graph *g, int target, bool allow_split, int bit_words, unsigned long long part_cap, int stage_cap, ChunkTable **out,
               const RowFilter &rf = RowFilter(), int bitmap_min_deg = kBitmapMinDeg);
-int ensure_edesc(gm_graph *g);
+// (gm_tables.hip) one table on the device, into `t` (its parameters set by the caller: get_table, and the host-chunk tables of the clique
+// rounds); trp / tlen / tstride: the task lists the costs of an rf.tct table are counted from; default: the graph's, gm_tch.hip
+int build_table_device(gm_graph *g, ChunkTable &t, bool sym_table, double &bitmap_ms, const int *trp = nullptr, const int *tlen = nullptr, int tstride = 2);
+void launch_gather_deg(int m, const int *verts, const int *rp, int *deg);  // (gm_tables.hip) deg[i] = the length of row verts[i]
+// The placement passes that walk the rows eight lanes each (task_rows_kernel / kst_rows_kernel, gm_tasks.hip; cb_task_rows_kernel,
+// gm_clique_plan.hip) count the in-edge tasks of the last kHubWin hosts of a topologically numbered DAG in an LDS histogram per workgroup;
+// their grid: 8 rows per wave and trip, at most per_cu workgroups per CU
+constexpr int kHubWin = 4096;
+inline dim3 row_walk_grid(const gm_graph *g, int per_cu) {
+  return dim3((unsigned)std::max<long long>(1, std::min<long long>(((long long)g->nv * 8 + 255) / 256, (long long)g->cu_count * per_cu)));
+}
+int ensure_edesc(gm_graph *g);  // (gm_tasks.hip)
 int ensure_tasklists(gm_graph *g);
 int ensure_keystream(gm_graph *g, bool edges, bool *built, bool allow_core = false);  // allow_core: the rows of the hub core may stay out (gm_ctc.hip)
-int sup_mask_min_tail(const gm_graph *g);  // (gm_tables.hip) kSupMaskMinTail or the option GM_SUP_MASK_MIN when the handle's masks were laid out
-int ensure_sup_corner(gm_graph *g);  // (gm_tables.hip) g->sup_corner of a handle whose task lists leave a hub corner out
-int ensure_sup_masks(gm_graph *g);  // (gm_tables.hip) g->sup_masks of a topologically numbered DAG with task lists; GM_OK also when not applicable
+int sup_mask_min_tail(const gm_graph *g);  // (gm_tasks.hip) kSupMaskMinTail or the option GM_SUP_MASK_MIN when the handle's masks were laid out
+int ensure_sup_corner(gm_graph *g);  // (gm_tasks.hip) g->sup_corner of a handle whose task lists leave a hub corner out
+int ensure_sup_masks(gm_graph *g);  // (gm_tasks.hip) g->sup_masks of a topologically numbered DAG with task lists; GM_OK also when not applicable
 int ensure_mean_sq_deg(gm_graph *g);
 int ensure_tri_per_edge(gm_graph *g);  // (gm_launch.hip) |N+(u) ^ N+(v)| averaged over a sample of the DAG's entries
 unsigned long long task_part_cap(gm_graph *g, int world);

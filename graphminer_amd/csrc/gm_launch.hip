@@ -1184,7 +1184,7 @@ extern "C" int gm_tc_core_info(const gm_graph *dag, int64_t info[4]) {
   return GM_OK;
 }
 
-// ... and the block pairs of it the product takes (tc_pairs_setup, gm_tables.hip): info[0] = rows of the region (0: no selection -- the full
+// ... and the block pairs of it the product takes (tc_pairs_setup, gm_tasks.hip): info[0] = rows of the region (0: no selection -- the full
 // triangle of gm_tc_core_info's corner, or none), [1] = pairs taken, [2] = pairs that hold keys, [3] = DAG entries in the product,
 // [4] = keys of the stream's model that left the stream, [5] = R of the rule
 extern "C" int gm_tc_pairs_info(const gm_graph *dag, int64_t info[6]) {

@@ -450,7 +450,7 @@ __host__ __device__ inline int cgb_words(int h, int delta) { return (h + delta +
 // one wave per block, blocks dealt by a dequeue word, t = first + q * step for a rank's share.
 constexpr int kCtcWaves = 4;
 constexpr int kCtcMaxH = 32768;        // f32 accumulators stay exact; the core bitmap (kCoreHDefault) is no larger
-constexpr int kTcCoreHDefault = 32768; // the largest corner considered (tc_core_size, gm_tables.hip: by density); GM_TC_CORE_H overrides
+constexpr int kTcCoreHDefault = 32768; // the largest corner considered (tc_core_size, gm_tasks.hip: by density); GM_TC_CORE_H overrides
 struct CoreTcParams {
   const unsigned *core;      // the core bitmap (gm_host.h HubCore): row_words words per row
   int row_words;
@@ -466,7 +466,7 @@ struct CoreTcParams {
   int base;
   const unsigned short *first_pos;
   unsigned *sup;
-  // the triangle count's chosen block pairs (gm_tables.hip tc_pairs_setup): n_list entries IB | JB << 8 | piece << 16, longest first;
+  // the triangle count's chosen block pairs (gm_tasks.hip tc_pairs_setup): n_list entries IB | JB << 8 | piece << 16, longest first;
   // nullptr: every pair IB <= JB of the corner, every piece
   const unsigned *tasks;
   int n_list;

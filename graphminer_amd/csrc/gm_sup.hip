@@ -23,7 +23,7 @@
 // N+(u)[i + 1 ..) is streamed): the streamed edge (u, s_j) of such a match is an entry of row u right behind the task's own entry, and the
 // task needs no atomic to report it -- it stores WHICH keys of its tail matched (bit k of its mask = key k), 64 keys per plain 8-byte
 // store, and sup_cols_kernel sums the masks of a row by column: entry j of row u += sum_{i < j} bit (j - i - 1) of the mask of entry i.
-// Masks: the in-edge tasks with tails of >= kSupMaskMinTail keys (ensure_sup_masks, gm_tables.hip: offsets per task / per entry); long
+// Masks: the in-edge tasks with tails of >= kSupMaskMinTail keys (ensure_sup_masks, gm_tasks.hip: offsets per task / per entry); long
 // tails (>= kLongList keys, one task at a time) store their tiles' ballots directly, the tails of the flattened pass collect theirs in six
 // LDS words per batch lane.  Out-edge tasks, short tails and the surplus-list matches of unmasked tasks keep the atomics.  One GPU, a
 // topologically numbered DAG; a rank's share of a larger job (gm_diamond_support_partial) runs without masks.

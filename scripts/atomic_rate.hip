@@ -1,5 +1,5 @@
 // Random-address atomic rates on gfx950: device (agent) scope against workgroup scope on a counter copy private to the XCD.
-// The key stream's count / place passes (gm_tables.hip, kst_rows_kernel) spend 3/4 of their time in one random global atomic per
+// The key stream's count / place passes (gm_tasks.hip, kst_rows_kernel) spend 3/4 of their time in one random global atomic per
 // in-edge task (profiles/r04/ab_setup_orient_relabel.txt); this measures what a per-XCD copy with L2-scope atomics would buy, and
 // checks that such atomics from different workgroups of one XCD add up (sum over the copies == atomics issued).
 //   hipcc --offload-arch=gfx950 -O3 scripts/atomic_rate.hip -o /tmp/atomic_rate && /tmp/atomic_rate

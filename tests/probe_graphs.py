@@ -13,7 +13,7 @@ private leaves to one common degree D above every gadget vertex's degree.  Under
 degree, ties by id) every gadget vertex then points AT the hubs, hub rows are empty, a leaf's only task streams an empty row, the hubs keep
 their relative order in the topological copy (ids by (degree, old id)), and the only triangles are the planted ones.
 
-Who hosts (csrc/gm_tables.hip task_walk_rows): the edge s -> t of the DAG is hosted by s when tail >= d+(t), else by t; tail = d+(s) as
+Who hosts (csrc/gm_tasks.hip task_walk_rows): the edge s -> t of the DAG is hosted by s when tail >= d+(t), else by t; tail = d+(s) as
 numbered, the entries of N+(s) behind t on the topological copy.  The host's row is staged, the other list is streamed.
 
 Families (ids: gadget vertices, then hubs, then -- `batch` only -- the high mids, then leaves):
@@ -441,5 +441,5 @@ def surplus() -> Probe:
 
 
 def hosts_as_source(tail: int, d_target: int) -> bool:
-    """the host rule of csrc/gm_tables.hip task_walk_rows for the DAG edge s -> t, both rows within the stage: does s host (and stream N+(t))?"""
+    """the host rule of csrc/gm_tasks.hip task_walk_rows for the DAG edge s -> t, both rows within the stage: does s host (and stream N+(t))?"""
     return tail >= d_target

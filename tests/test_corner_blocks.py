@@ -1,4 +1,4 @@
-"""The block geometry of the blocked 4-clique gather (csrc/gm_tables.hip ensure_core_tri, csrc/gm_cgather.hip cgatherb_kernel), restated on the
+"""The block geometry of the blocked 4-clique gather (csrc/gm_clique_plan.hip ensure_core_tri, csrc/gm_cgather.hip cgatherb_kernel), restated on the
 CPU: blocks of consecutive core rows whose stored words (row p keeps the words from (p + 1) >> 5 on) fit the LDS budget; gathering a row of a
 vertex's matrix from the block images gives the same bits as gathering it from the row-major bitmap.  CPU only."""
 import numpy as np

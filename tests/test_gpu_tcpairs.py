@@ -1,4 +1,4 @@
-"""Triangle count: the hub corner chosen per PAIR of 256-row blocks (tc_pairs_setup, gm_tables.hip) -- the masked product (gm_ctc.hip) takes
+"""Triangle count: the hub corner chosen per PAIR of 256-row blocks (tc_pairs_setup, gm_tasks.hip) -- the masked product (gm_ctc.hip) takes
 the edges of the chosen pairs (IB <= JB) of a region at the end of the core bitmap, the key stream everything else.  Every triangle is
 counted by its (smallest, middle) edge, so the total must equal the oracle's (omp_base.cc:15-21) for ANY set of pairs: every forced
 selection, the rule, ranks' shares, the kernels without the stream (their corner stays row-based), the formula 3-motif and the diamond.

@@ -59,7 +59,7 @@ def check_hubs(p, dag, stage, hub_row_max=0):
 
 
 def streamed(dag_row_s, dag_row_t, t, topo):
-    """the DAG edge s -> t: (the list streamed, the row it is looked up in), by the host rule of csrc/gm_tables.hip"""
+    """the DAG edge s -> t: (the list streamed, the row it is looked up in), by the host rule of csrc/gm_tasks.hip"""
     i = int(np.flatnonzero(dag_row_s == t)[0])
     tail = len(dag_row_s) - i - 1 if topo else len(dag_row_s)
     if PG.hosts_as_source(tail, len(dag_row_t)):

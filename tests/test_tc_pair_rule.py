@@ -1,5 +1,5 @@
 """The rule that chooses which pairs of 256-row blocks (IB <= JB) of the hub corner the triangle count's masked product takes
-(gm_tc_pair_rule, gm_tables.hip): a pair is taken iff  keys * R > 65536 * (region - 512 * (JB >> 1))  -- the keys the stream would move for
+(gm_tc_pair_rule, gm_tasks.hip): a pair is taken iff  keys * R > 65536 * (region - 512 * (JB >> 1))  -- the keys the stream would move for
 the pair's edges, R bit-products a key, against the bit-products of the pair's column range.  CPU only: the exported host function against a
 restatement in Python integers, on random cell tables."""
 import numpy as np
