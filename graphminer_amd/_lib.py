@@ -106,6 +106,7 @@ SYMBOLS = [
     ("gm_truss_decompose", C.c_int, [_P, C.POINTER(gm_launch), _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(gm_stats)]),
     ("gm_clique_local", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), _P, _P, C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
     ("gm_rect_local", C.c_int, [_P, C.POINTER(gm_launch), _P, _P, C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
+    ("gm_motif_local", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), _P, C.POINTER(C.c_uint64), C.c_int, C.POINTER(gm_stats)]),
     ("gm_tc_list", C.c_int, [_P, C.POINTER(gm_launch), C.c_uint64, C.c_uint64, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                              C.POINTER(gm_stats)]),
     ("gm_motif_formula", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.c_int, C.POINTER(gm_stats)]),

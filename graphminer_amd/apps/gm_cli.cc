@@ -1,8 +1,8 @@
 // gm_cli.cc -- one source for the whole command-line surface of the HIP solvers.
 //
-// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL|RECTLOCAL> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
+// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL|RECTLOCAL|MOTIFLOCAL> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
 //   tc_gpu_base tc_multigpu tc_multigpu_base | sgl_gpu_base sgl_multigpu | clique_gpu_base clique_multigpu kcl_gpu_base |
-//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base | cliquelocal_gpu_base | rectlocal_gpu_base
+//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base | cliquelocal_gpu_base | rectlocal_gpu_base | motiflocal_gpu_base
 // The observable behaviour -- positional argv, defaults, usage text, banner and FINAL result lines -- is that of the
 // reference mains (src/triangle/main.cc:7-27, src/sgl/main.cc:9-35, src/clique/main.cc:8-28, src/motif/main.cc:9-31,
 // Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.  truss_gpu_base <graph prefix> [k] has no
@@ -16,6 +16,9 @@
 // per-vertex counts go to <out>.vertex.u64 and the per-entry counts to <out>.entry.u64 as raw little-endian uint64.
 // rectlocal_gpu_base <graph prefix> [out prefix] counts the 4-cycles at every vertex and on every edge (gm_rect_local): `max_vertex_rectangles
 // = A` and `max_edge_rectangles = B`, then `total_num = N` in sgl_gpu_base's spelling as the last line; the same two files with an out prefix.
+// motiflocal_gpu_base <graph prefix> <k> [out prefix] counts the graphlet-degree orbits of every vertex (gm_motif_local, k = 3 | 4): one line
+// `orbit <o>: sum = S max = M` per orbit, then `pattern <i>: <count>` as motif_gpu_base's last lines; with an out prefix the orbits go to
+// <out>.orbits.u64 as raw little-endian uint64, orbit-major.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -34,11 +37,12 @@
 #define GM_TCLIST 7
 #define GM_CLIQUELOCAL 8
 #define GM_RECTLOCAL 9
-#if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL)
+#define GM_MOTIFLOCAL 10
+#if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL)
 #include <hip/hip_runtime_api.h>
 #endif
 #ifndef GM_APP
-#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL|GM_RECTLOCAL"
+#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL|GM_RECTLOCAL|GM_MOTIFLOCAL"
 #endif
 
 namespace {
@@ -51,7 +55,7 @@ struct Cli {
   int adj_sorted = 1;  // [adj_sorted(1)] (tc only)
 };
 
-#if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_CLIQUELOCAL && GM_APP != GM_RECTLOCAL
+#if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_CLIQUELOCAL && GM_APP != GM_RECTLOCAL && GM_APP != GM_MOTIFLOCAL
 // positional layout: TC has no <second>; the others do
 Cli parse(int argc, char **argv, bool has_second) {
   Cli c;
@@ -90,6 +94,9 @@ void usage_and_exit(const char *self) {
 #elif GM_APP == GM_RECTLOCAL
   std::printf("Usage: %s <graph prefix> [out prefix]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph rectangles\n", self);
+#elif GM_APP == GM_MOTIFLOCAL
+  std::printf("Usage: %s <graph prefix> <k> [out prefix]\n", self);
+  std::printf("Example: %s /graph_inputs/mico/graph 4 orbits\n", self);
 #else
   std::printf("Usage: %s<graph> <k> [ngpu(0)] [chunk_size(1024)]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4\n", self);
@@ -124,7 +131,7 @@ int main(int argc, char **argv) {
   argc = strip_dev_options(argc, argv);
   const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_RECTLOCAL);
   if (argc < (has_second ? 3 : 2)) usage_and_exit(argv[0]);
-#if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL
+#if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL
   Cli c;
   c.graph = argv[1];
   if (argc > 2) c.second = argv[2];  // [k] / [out.bin] / <k> / [out prefix]
@@ -313,6 +320,46 @@ int main(int argc, char **argv) {
   std::printf("max_vertex_rectangles = %llu\n", (unsigned long long)(rv.empty() ? 0 : *std::max_element(rv.begin(), rv.end())));
   std::printf("max_edge_rectangles = %llu\n", (unsigned long long)(re.empty() ? 0 : *std::max_element(re.begin(), re.end())));
   std::printf("total_num = %llu\n", (unsigned long long)total);
+
+#elif GM_APP == GM_MOTIFLOCAL
+  const int k = std::atoi(c.second.c_str());
+  std::printf("local %d-motif counts (undirected graph only)\n", k);
+  std::fflush(stdout);
+  Graph g(c.graph);
+  g.print_meta_data();
+  const gm_csr csr = g.csr();
+  const std::string out = argc > 3 ? argv[3] : "";
+  const size_t nv = (size_t)csr.nv, no = k == 3 ? 4 : 15, nc = k == 3 ? 2 : 6;
+  gm_graph *h = nullptr;
+  int rc = gm_graph_upload(&csr, 0, &h);
+  std::vector<uint64_t> orb(no * nv), counts(nc, 0);
+  uint64_t *d_orb = nullptr;
+  // (the array is the call's result and the caller's buffer)
+  if (rc == GM_OK && hipMalloc(reinterpret_cast<void **>(&d_orb), sizeof(uint64_t) * (orb.empty() ? 1 : orb.size())) != hipSuccess) rc = GM_ERR_HIP;
+  if (rc == GM_OK) rc = gm_motif_local(h, k, nullptr, d_orb, counts.data(), (int)nc, nullptr);
+  if (rc == GM_OK && !orb.empty() && hipMemcpy(orb.data(), d_orb, sizeof(uint64_t) * orb.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+  if (d_orb) (void)hipFree(d_orb);
+  gm_graph_free(h);
+  if (rc == GM_OK && !out.empty()) {  // (the hosts this runs on are little-endian: the counts go out as they lie in memory)
+    FILE *f = std::fopen((out + ".orbits.u64").c_str(), "wb");
+    const bool ok = f && std::fwrite(orb.data(), sizeof(uint64_t), orb.size(), f) == orb.size();
+    if (f && std::fclose(f) != 0) rc = GM_ERR_IO;
+    if (!ok) rc = GM_ERR_IO;
+  }
+  if (rc != GM_OK) {
+    std::fprintf(stderr, "%s: %s %s\n", argv[0], gm_strerror(rc), gm_last_error());
+    return 1;
+  }
+  for (size_t o = 0; o < no; ++o) {
+    uint64_t sum = 0, mx = 0;
+    for (size_t v = 0; v < nv; ++v) {
+      sum += orb[o * nv + v];
+      mx = std::max(mx, orb[o * nv + v]);
+    }
+    std::printf("orbit %d: sum = %llu max = %llu\n", (int)o, (unsigned long long)sum, (unsigned long long)mx);
+  }
+  std::printf("num_patterns: %d\n", (int)nc);
+  for (size_t i = 0; i < nc; ++i) std::printf("pattern %d: %llu\n", (int)i, (unsigned long long)counts[i]);
 
 #elif GM_APP == GM_SGL6
   std::printf("Subgraph Listing/Counting (undirected graph only)\n");

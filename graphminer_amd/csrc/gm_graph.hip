@@ -277,6 +277,7 @@ int finish_handle(gm_graph *g) {
     gm_touch_wtri();
     gm_touch_wrect();
     gm_touch_rect_local();
+    gm_touch_orbit_local();
     gm_touch_local();
     gm_touch_list();
     gm_touch_kcl_local();

@@ -571,6 +571,10 @@ struct gm_graph {
     // local 4-cycle counts, on the graph the walk runs on: the credits of every entry (zeroed by every call).  On the SYMMETRIC handle the
     // counts in the caller's entry order are ent64's, as for the k-cliques
     DevOwn<unsigned long long> racc;
+    // local motif counts: on the DAG the credit pass runs on, the rim credits of every entry (zeroed by every call); on the SYMMETRIC
+    // handle five vertex arrays of the call's own -- T_v, R_v, K_v, half the row sums of the credits, e1 -- and eight column sums
+    DevOwn<unsigned long long> wacc;
+    DevOwn<unsigned long long> orb;
   } local;
   struct MapWork {  // the global counter maps of run_rect_acc / run_house_acc (rectangle, pentagon, house by wedge accumulation)
     DevOwn<unsigned> rect_acc;
@@ -724,6 +728,7 @@ void gm_touch_sup();
 void gm_touch_wtri();
 void gm_touch_wrect();
 void gm_touch_rect_local();
+void gm_touch_orbit_local();
 void gm_touch_local();
 void gm_touch_list();
 void gm_touch_kcl_local();

@@ -11,6 +11,8 @@ struct PatternReq {
   unsigned long long fin_base = 0;  // FIN_MOTIF3_FORMULA: sum_v C(d, 2)
   unsigned *sup_out = nullptr;      // PAT_SUPPORT_PART's buffer
   bool wtri_tri = false, wtri_vert = false;  // PAT_WTRI: the second pass over the triangles (A, B) / the per-vertex sums (H, S) are wanted
+  const unsigned *credit_sup = nullptr;      // PAT_ORBIT: the complete supports of the handle's entries ...
+  unsigned long long *credit_w = nullptr;    // ... and the per-entry accumulator of the rim credits (zeroed inside the timed region)
 };
 int run_pattern(const PatternReq &rq, const gm_graph *cg, const gm_launch *la, uint64_t *h_out, int nout, gm_stats *st);
 

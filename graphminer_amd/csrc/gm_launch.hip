@@ -791,14 +791,16 @@ static int launch_classes(PatternRun &r) {
 
 // The tables of the task-list kernels, one after the other on the launch stream.  support: the edge supports' kernel (launch_sup / sup_per_cu,
 // gm_sup.hip) instead of the triangle count's (launch_tch / tch_per_cu, gm_tch.hip).
-enum TaskKernel : int { TK_TC = 0, TK_SUPPORT = 1, TK_WTRI = 2 };
+enum TaskKernel : int { TK_TC = 0, TK_SUPPORT = 1, TK_WTRI = 2, TK_CREDIT = 3 };
 static int launch_task_tables(PatternRun &r, int kind) {
   gm_graph *g = r.ctx.g;
   hipStream_t stream = r.ctx.stream;
   const PatternPlan &pl = r.pl;
   const MineParams &p = r.p;
   const WtriParams wp = {g->w5.sup, g->w5.ed, g->w5deg->deg};
+  const CreditParams crp = {r.rq.credit_sup, r.rq.credit_w};
   auto launch = [&](const MineParams &q, int stage, long long dequeues) {
+    if (kind == TK_CREDIT) return launch_credit(q, crp, stage, grid_for(dequeues, g->cu_count, credit_per_cu(stage)), stream);
     const int grid = grid_for(dequeues, g->cu_count, kind == TK_WTRI ? wtri_per_cu(stage) : kind == TK_SUPPORT ? sup_per_cu(stage) : tch_per_cu(stage));
     return kind == TK_WTRI ? launch_wtri(q, wp, stage, grid, stream) : kind == TK_SUPPORT ? launch_sup(q, stage, grid, stream) : launch_tch(q, stage, grid, stream);
   };
@@ -961,6 +963,29 @@ static int launch_weighted(PatternRun &r) {
   return GM_OK;
 }
 
+// The diamond-rim credits of gm_motif_local (gm_orbit_local.hip): the weighted pass's walk -- the task tables, then the out-edges no task
+// list holds -- adding into rq.credit_w from the supports rq.credit_sup.  All inside the timed region, the zeroing included.
+static int launch_credits(PatternRun &r) {
+  gm_graph *g = r.ctx.g;
+  hipStream_t stream = r.ctx.stream;
+  const PatternPlan &pl = r.pl;
+  HIP_TRY(hipMemsetAsync(r.rq.credit_w, 0, sizeof(unsigned long long) * (size_t)std::max<long long>(g->ne, 1), stream));
+  if (int rc = launch_task_tables(r, TK_CREDIT)) return rc;
+  const CreditParams crp = {r.rq.credit_sup, r.rq.credit_w};
+  WtriEdgeParams we;
+  memset(&we, 0, sizeof we);
+  we.rp = g->d_rp; we.col = g->d_col; we.nv = g->nv; we.ne = g->ne;
+  we.topo = tails_trimmed(g) ? 1 : 0;
+  if (pl.tct_long && g->long_rows->n > 0) {
+    we.rows = g->long_rows->rows; we.prefix = g->long_rows->prefix; we.nrows = g->long_rows->n; we.total = g->long_rows->edges;
+    HIP_TRY(launch_credit_edges(we, crp, g->cu_count, stream));
+  } else if (pl.corner_from < g->nv) {
+    we.v0 = pl.corner_from; we.total = g->ne;
+    HIP_TRY(launch_credit_edges(we, crp, g->cu_count, stream));
+  }
+  return GM_OK;
+}
+
 int run_pattern(const PatternReq &rq, const gm_graph *cg, const gm_launch *la, uint64_t *h_out, int nout, gm_stats *st) {
   PatternRun r;
   r.rq = rq;
@@ -971,7 +996,9 @@ int run_pattern(const PatternReq &rq, const gm_graph *cg, const gm_launch *la, u
   // (PAT_SUPPORT_PART: the share of a rank -- any world -- of the supports only, added into the caller's zeroed buffer: the ranks' arrays
   // are summed by a reduce-scatter and gm_diamond_support_finish takes sum C(t, 2) of a slice)
   pl.sup_part = rq.pat == PAT_SUPPORT_PART;
-  pl.wtri = rq.pat == PAT_WTRI;  // (the weighted pass of the 5-vertex closed forms: the same tables and task lists, gm_wtri.hip)
+  const bool credit = rq.pat == PAT_ORBIT;  // (the rim credits of gm_motif_local: planned exactly as the weighted pass, gm_orbit_local.hip)
+  if (credit && (!rq.credit_sup || !rq.credit_w)) return GM_ERR_INVALID;
+  pl.wtri = rq.pat == PAT_WTRI || credit;  // (the weighted pass of the 5-vertex closed forms: the same tables and task lists, gm_wtri.hip)
   pl.support = rq.pat == PAT_SUPPORT || pl.sup_part || pl.wtri;
   if (pl.sup_part && !rq.sup_out) return GM_ERR_INVALID;
   pl.pat = pl.support ? PAT_TC : rq.pat;
@@ -994,7 +1021,8 @@ int run_pattern(const PatternReq &rq, const gm_graph *cg, const gm_launch *la, u
   if (pl.use_classes)
     if (int rc = launch_classes(r)) return rc;
   int rc = GM_OK;
-  if (pl.wtri) rc = launch_weighted(r);
+  if (credit) rc = launch_credits(r);
+  else if (pl.wtri) rc = launch_weighted(r);
   else if (pl.support) rc = launch_supports(r);
   else if (pl.use_tct) rc = launch_tc(r);
   else if (r.p.count > 0) HIP_TRY(launch_mine(pl.pat, r.p, r.grid, stream));

@@ -133,7 +133,8 @@ enum Pattern : int { PAT_TC = 0, PAT_DIAMOND = 1, PAT_MOTIF3 = 2, PAT_CLIQUE4 = 
                      PAT_SUPPORT = 7 /* edge supports from the DAG's triangles + sum C(t, 2): the diamond count (gm_sup.hip) */,
                      PAT_SUPPORT_PART = 8 /* ... a rank's share of the supports only, into the caller's buffer (gm_diamond_support_partial) */,
                      PAT_CLIQUEK_DEEP = 9 /* kernel side only: the instance of the mining kernel PAT_CLIQUEK launches for k = 9..12 (gm_chunk.h) */,
-                     PAT_WTRI = 10 /* the support-weighted second pass over the triangles + the per-entry / per-vertex sums (gm_wtri.hip) */ };
+                     PAT_WTRI = 10 /* the support-weighted second pass over the triangles + the per-entry / per-vertex sums (gm_wtri.hip) */,
+                     PAT_ORBIT = 11 /* the diamond-rim credit pass over the triangles of gm_motif_local (gm_orbit_local.hip): PAT_WTRI's walk */ };
 
 // Symmetric-graph patterns stage up to 3072 entries: on skewed graphs thousands of rows have 1-3 K neighbours; with a
 // 1024-entry stage they are SPLIT rows whose keys are bisected in HBM, otherwise ordinary staged chunks behind
@@ -747,6 +748,30 @@ hipError_t launch_local_vertices(int nv, const int *rp, const unsigned *sup, uns
 // ... the 64-bit forms (gm_clique_local): the k-clique count of every entry, and per vertex the sum of its row / div (div = k - 1)
 hipError_t launch_local_map(const LocalMapParams64 &p, int cu_count, hipStream_t stream);
 hipError_t launch_local_vertices(int nv, const int *rp, const unsigned long long *cnt, unsigned div, unsigned long long *kv, int cu_count, hipStream_t stream);
+// local motif counts (gm_orbit_local.hip, gm_motif_local): the diamond-rim credits of every DAG entry -- wtri_kernel's walk over the
+// triangles with three adds per match instead of a sum -- and the two row kernels on the caller's symmetric CSR that gather the
+// neighbour sums and turn the non-induced counts into the 15 orbits (gm_orbit.h).  Exported through gm_constant ("orbit_wave_row").
+constexpr int kOrbitWaveRow = 32;  // the row kernels: a row of more entries is summed by the whole wave
+struct CreditParams {
+  const unsigned *sup;       // per DAG entry: its support, complete
+  unsigned long long *w;     // per DAG entry (zeroed by the caller): += the x of the other two edges of every triangle of the entry
+};
+struct OrbitFinishParams {
+  int nv;
+  const int *rp, *col;                // the caller's symmetric CSR
+  const unsigned *ent;                // k = 4: per caller's entry, the support of its edge
+  const unsigned long long *tv;       // per vertex: T_v
+  const unsigned long long *rv, *kv;  // k = 4: R_v, K_v
+  const unsigned long long *w2;       // k = 4: half the row sum of the rim credits
+  const unsigned long long *e1;       // k = 4: sum of d(a) - 1 over the row (orbit_e1_kernel)
+  unsigned long long *orbits;         // nullptr, or orbit-major: orbit o of vertex v at [o * nv + v] (k = 3: 4 orbits, k = 4: 15)
+  unsigned long long *sums;           // zeroed by the caller: k = 3 [sum o2, sum o3]; k = 4 [sum o7, o4, o9, o8, o13, o14]
+};
+int credit_per_cu(int stage);
+hipError_t launch_credit(const MineParams &p, const CreditParams &cp, int stage, int grid_blocks, hipStream_t stream);
+hipError_t launch_credit_edges(const WtriEdgeParams &p, const CreditParams &cp, int cu_count, hipStream_t stream);
+hipError_t launch_orbit_e1(int nv, const int *rp, const int *col, unsigned long long *e1, int cu_count, hipStream_t stream);
+hipError_t launch_orbit_finish(const OrbitFinishParams &p, int k, int cu_count, hipStream_t stream);  // k = 3 | 4
 // local k-clique counts (gm_kcl_local.hip): the k-cliques on every entry of the DAG.  Rows of up to kKclLocalLdsRow entries keep the
 // adjacency matrix of the row in LDS -- a candidate set of a descent takes 2 registers for rows of up to kKclLocalRegs2Row entries, 8 up
 // to kKclLocalRegs8Row, 12 up to kKclLocalRegs12Row, 16 beyond; longer rows are listed by that kernel and taken by the second one out of a global scratch slot per

@@ -1,7 +1,8 @@
 // gm_solve_local.hip -- local counts, the k-truss, the triangle listing, the local k-clique and 4-cycle counts over the launch layer (gm_launch.h):
-// gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_rect_local.  Host code only: the kernels are gm_local.hip's,
-// gm_list.hip's, gm_kcl_local.hip's and gm_rect_local.hip's, so this unit has no code object and no warm-up.
+// gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_rect_local, gm_motif_local.  Host code only: the kernels are
+// gm_local.hip's, gm_list.hip's, gm_kcl_local.hip's, gm_rect_local.hip's and gm_orbit_local.hip's, so this unit has no code object and no warm-up.
 #include "gm_launch.h"
+#include "gm_orbit.h"
 
 // ---- local counts and the k-truss (gm_local.hip; DESIGN.md "Local counts and k-truss") ----------------------------------------------------
 // the arrays of the symmetric handle, in the caller's entry order (peel: also the marks, the frontier list and the round counters)
@@ -259,6 +260,104 @@ extern "C" int gm_rect_local(const gm_graph *sym, const gm_launch *la, uint64_t 
     st->chunks = (uint64_t)p.count;
     st->grid = (uint32_t)grid;
   }
+  return GM_OK;
+}
+
+// ---- local motif counts (gm_orbit_local.hip; DESIGN.md "Local motif counts") ---------------------------------------------------------------
+// The graphlet-degree orbits of every vertex, put together from the three local counts above on the same handle -- gm_tc_local leaves the
+// supports in the caller's entry order in g->local.ent and T_v in the call's own array, gm_rect_local R_v, gm_clique_local(4) K_v -- and
+// from the one input none of them has: the diamond-rim credits W of the DAG entries (PAT_ORBIT: the weighted pass's walk over the triangles
+// of run_on, reading run_on->local.sup as gm_tc_local left it).  W goes back the k-cliques' way -- the 64-bit mapping kernel into
+// g->local.ent64, half the row sums per vertex -- and is reduced to its vertex array BEFORE the rectangles and the k-cliques overwrite
+// ent64.  k = 3 stops after gm_tc_local: one gather.  One kernel_ms covers every sub-launch.
+extern "C" int gm_motif_local(const gm_graph *sym, int k, const gm_launch *la, uint64_t *d_orbits, uint64_t *counts, int ncounts, gm_stats *st) {
+  if (!sym || (k != 3 && k != 4)) return GM_ERR_INVALID;
+  const int nc = k == 3 ? 2 : 6, no = k == 3 ? kOrbits3 : kOrbits4;
+  if (counts && ncounts != nc) return GM_ERR_INVALID;
+  if (counts) for (int i = 0; i < nc; ++i) counts[i] = 0;
+  if (int rc = local_refusals(sym, la)) return rc;
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, 256);
+  uint64_t unused = 0;
+  {
+    LaunchCtx ctx;
+    if (int rc = begin_launch(sym, &l2, &unused, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+    if (sym->ne == 0) {
+      if (d_orbits && sym->nv > 0) HIP_TRY(hipMemsetAsync(d_orbits, 0, sizeof(uint64_t) * (size_t)no * (size_t)sym->nv, ctx.stream));
+      HIP_TRY(hipStreamSynchronize(ctx.stream));
+      return GM_OK;
+    }
+  }
+  const size_t nvz = (size_t)std::max(g->nv, 1);
+  {
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (!g->local.orb) HIP_TRY(g->local.orb.alloc(sizeof(unsigned long long) * (5 * nvz + 8)));
+  }
+  unsigned long long *tv = g->local.orb, *rv = tv + nvz, *kv = rv + nvz, *w2 = kv + nvz, *e1 = w2 + nvz, *sums = e1 + nvz;
+  SubLaunches sub;
+  if (int rc = sub.run([&](gm_stats *s) { return gm_tc_local(sym, &l2, (uint64_t *)tv, nullptr, nullptr, s); })) return rc;
+  if (k == 4) {
+    gm_graph *run_on = nullptr;
+    if (int rc = diamond_run_on(g, &l2, &run_on)) return rc;  // (the copy gm_tc_local's supports were counted on)
+    const gm_graph *dag = g->dag_cache;
+    if (!run_on->local.sup || (run_on != dag && !run_on->d_newid)) return GM_ERR_INVALID;
+    {
+      std::lock_guard<std::mutex> lk(run_on->mu);
+      HIP_TRY(hipSetDevice(run_on->device));
+      if (!run_on->local.wacc) HIP_TRY(run_on->local.wacc.alloc(sizeof(unsigned long long) * (size_t)std::max<long long>(run_on->ne, 1)));
+    }
+    PatternReq credits{PAT_ORBIT, 3};
+    credits.credit_sup = run_on->local.sup;
+    credits.credit_w = run_on->local.wacc;
+    if (int rc = sub.run([&](gm_stats *s) { return run_pattern(credits, run_on, &l2, &unused, 1, s); })) return rc;
+    {
+      std::lock_guard<std::mutex> lk(g->mu);
+      if (!g->local.ent64) HIP_TRY(g->local.ent64.alloc(sizeof(unsigned long long) * (size_t)g->ne));
+    }
+    LaunchCtx ctx;
+    if (int rc = begin_launch(sym, &l2, &unused, ctx)) return rc;
+    if (int rc = start_timer(ctx)) return rc;
+    LocalMapParams64 mp;
+    memset(&mp, 0, sizeof mp);
+    mp.nv = g->nv; mp.ne = g->ne; mp.rp = g->d_rp; mp.col = g->d_col;
+    mp.newid = run_on != dag ? run_on->d_newid.get() : nullptr;
+    mp.drp = run_on->d_rp; mp.dcol = run_on->d_col; mp.dsup = run_on->local.wacc;
+    mp.topo = *run_on->facts.topological ? 1 : 0;
+    mp.out = g->local.ent64; mp.sum = g->d_counters;
+    HIP_TRY(launch_local_map(mp, g->cu_count, ctx.stream));
+    // (the row sum of W is even: N12 + N13 = half of it)
+    HIP_TRY(launch_local_vertices(g->nv, g->d_rp, g->local.ent64, 2u, w2, g->cu_count, ctx.stream));
+    if (int rc = sub.run([&](gm_stats *s) { return end_launch(ctx, FIN_COPY, 0, &unused, 1, s); })) return rc;
+    if (int rc = sub.run([&](gm_stats *s) { return gm_rect_local(sym, &l2, (uint64_t *)rv, nullptr, nullptr, s); })) return rc;
+    if (int rc = sub.run([&](gm_stats *s) { return gm_clique_local(sym, 4, &l2, (uint64_t *)kv, nullptr, nullptr, s); })) return rc;
+  }
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, &unused, ctx)) return rc;
+  if (int rc = start_timer(ctx)) return rc;
+  HIP_TRY(hipMemsetAsync(sums, 0, sizeof(unsigned long long) * 8, ctx.stream));
+  OrbitFinishParams fp;
+  memset(&fp, 0, sizeof fp);
+  fp.nv = g->nv; fp.rp = g->d_rp; fp.col = g->d_col; fp.tv = tv;
+  fp.orbits = (unsigned long long *)d_orbits; fp.sums = sums;
+  if (k == 4) {
+    fp.ent = g->local.ent; fp.rv = rv; fp.kv = kv; fp.w2 = w2; fp.e1 = e1;
+    HIP_TRY(launch_orbit_e1(g->nv, g->d_rp, g->d_col, e1, g->cu_count, ctx.stream));
+  }
+  HIP_TRY(launch_orbit_finish(fp, k, g->cu_count, ctx.stream));
+  unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, ctx.stream));
+  if (int rc = sub.run([&](gm_stats *s) { return end_launch(ctx, FIN_COPY, 0, &unused, 1, s); })) return rc;  // (synchronises the stream)
+  if (counts) {
+    if (k == 3) {
+      counts[0] = h[0];
+      counts[1] = h[1] / 3ull;
+    } else {  // [3-star, 4-path, tailed triangle, 4-cycle, diamond, 4-clique]: sum o7, o4 / 2, o9, o8 / 4, o13 / 2, o14 / 4
+      const unsigned long long div[6] = {1, 2, 1, 4, 2, 4};
+      for (int i = 0; i < 6; ++i) counts[i] = h[i] / div[i];
+    }
+  }
+  if (st) st->kernel_ms = sub.ms;
   return GM_OK;
 }
 

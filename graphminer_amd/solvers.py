@@ -333,6 +333,24 @@ def rect_local(g: DeviceGraph, *, vertex=True, entries=True, chunk=0, return_sta
     return (*res, _stats(st)) if return_stats else res
 
 
+# ---- local motif counts (include/graphminer_amd.h: gm_motif_local) ------------------------------------------------------------------------
+def motif_local(g: DeviceGraph, k: int, *, orbits=True, chunk=0, return_stats=False, **kw):
+    """(counts, orbits as np.uint64[n_orbits, nv] or None) of a SYMMETRIC graph: the graphlet-degree orbits of every vertex in the caller's
+    numbering -- row o = orbit o in Przulj's numbering, 4 rows for k = 3, 15 for k = 4 -- and the list MotifSolver(g, k) returns, here
+    from the column sums.  One GPU."""
+    import torch
+
+    k = int(k)
+    la, st = _launch(0, 1, chunk, **kw), gm_stats()
+    n = num_possible_patterns[k] if k in (3, 4) else 1
+    no = 4 if k == 3 else 15
+    out = (C.c_uint64 * n)()
+    orb = _dev_array(g, no * g.nv, torch.int64) if orbits else None
+    _lib.check(_lib.load().gm_motif_local(g.handle, k, C.byref(la), orb.data_ptr() if orbits else None, out, n, C.byref(st)), "gm_motif_local")
+    res = ([int(x) for x in out], _to_numpy(orb, no * g.nv, "uint64").reshape(no, g.nv) if orbits else None)
+    return (*res, _stats(st)) if return_stats else res
+
+
 # ---- triangle listing (include/graphminer_amd.h: gm_tc_list) ------------------------------------------------------------------------------
 def tc_list(g: DeviceGraph, *, first=0, cap=None, chunk=0, return_stats=False, **kw):
     """(total, triangles as np.int32[n_written, 3]) of a SYMMETRIC graph: rows a < b < c in the caller's numbering, every triangle once, in

@@ -439,6 +439,33 @@ int gm_clique_local(const gm_graph *sym, int k, const gm_launch *launch, uint64_
 int gm_rect_local(const gm_graph *sym, const gm_launch *launch, uint64_t *d_vertex_cnt, uint64_t *d_entry_cnt, uint64_t *total,
                   gm_stats *stats);
 
+/* ---- local motif counts (csrc/gm_orbit_local.hip, csrc/gm_orbit.h; DESIGN.md "Local motif counts") ----------------------------------------
+ * The per-vertex form of the 3- and 4-motif: the graphlet degree vector, the vertex-induced orbit counts of every vertex in Przulj's /
+ * ORCA's numbering (the input of network alignment, role features, higher-order clustering).  SYMMETRIC graph with ascending rows, as for
+ * the local triangle counts.
+ *   k = 3: orbits 0 .. 3 (n_orbits = 4), counts[2];  k = 4: orbits 0 .. 14 (n_orbits = 15), counts[6].
+ *   d_orbits: DEVICE uint64[n_orbits * nv] or NULL -- orbit-major in the CALLER's numbering: orbit o of vertex v at d_orbits[o * nv + v].
+ *     0 edge (the degree)          1 2-path, end              2 2-path, middle            3 triangle
+ *     4 4-path, end                5 4-path, inner            6 3-star, leaf              7 3-star, centre
+ *     8 4-cycle                    9 tailed triangle, the tail's end (degree 1)           10 tailed triangle, a triangle vertex of degree 2
+ *     11 tailed triangle, the vertex carrying the tail        12 diamond, degree-2 vertex 13 diamond, degree-3 (chord) vertex
+ *     14 4-clique
+ *   counts (may be NULL; else ncounts must be 2 for k = 3, 6 for k = 4 -> GM_ERR_INVALID): exactly what gm_motif(k) returns, in its order,
+ *     here from the column sums: k = 3 [sum o2, sum o3 / 3]; k = 4 [sum o7, sum o4 / 2, sum o9, sum o8 / 4, sum o13 / 2, sum o14 / 4] =
+ *     [3-star, 4-path, tailed triangle, 4-cycle, diamond, 4-clique].
+ * All arithmetic is uint64 modulo 2^64 and integer: the results do not depend on the launch or on the order in which the workgroups arrive.
+ * The call obtains t(e) and T_v, R_v and K_v through gm_tc_local, gm_rect_local and gm_clique_local(4) on the same handle, adds one pass
+ * over the triangles that credits every diamond to its rim edges (two 64-bit atomics per triangle and one per task), gathers the neighbour
+ * sums per vertex and turns the non-induced counts into induced orbits (gm_orbit.h).  k = 3 runs the support pass and one gather only: no
+ * rectangle plan is built, no k-clique kernel runs.  launch->tune[6] & GM_T6_AS_NUMBERED is passed on to the three input calls and the
+ * new pass (the oriented copy and the graph as numbered, no renumbered copies).  The counts are the same either way.
+ * The contract of the local counts above: one GPU, synchronous; a null handle or k not in {3, 4} -> GM_ERR_INVALID, >= 2^31 entries ->
+ * GM_ERR_TOO_LARGE, world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED, unsorted rows -> GM_ERR_INVALID, ne == 0 -> GM_OK with zeros
+ * (d_orbits is zeroed when given); launch->stream is honoured; stats->kernel_ms covers every kernel of the call, the three input
+ * computations included, stats->tasks = the directed entries; before or after any other solver on the handle, whose arrays it leaves
+ * alone; ONE such call at a time per handle; every array it keeps on the handle is freed with the handle. */
+int gm_motif_local(const gm_graph *sym, int k, const gm_launch *launch, uint64_t *d_orbits, uint64_t *counts, int ncounts, gm_stats *stats);
+
 /* MotifSolver on the SYMMETRIC graph. k = 3: counts[0] = wedges, counts[1] = triangles
  * (the CPU order, src/motif/cpu_kernels/automine_base.h:13,18; NOT the swapped order of
  * src/motif/gpu_kernels/motif3_edge_warp.cuh:19-22). ncounts must be
