@@ -1,8 +1,9 @@
 // gm_cli.cc -- one source for the whole command-line surface of the HIP solvers.
 //
-// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL|RECTLOCAL|MOTIFLOCAL> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
+// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL|RECTLOCAL|MOTIFLOCAL|CLIQUELIST> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
 //   tc_gpu_base tc_multigpu tc_multigpu_base | sgl_gpu_base sgl_multigpu | clique_gpu_base clique_multigpu kcl_gpu_base |
-//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base | cliquelocal_gpu_base | rectlocal_gpu_base | motiflocal_gpu_base
+//   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base | cliquelocal_gpu_base | rectlocal_gpu_base | motiflocal_gpu_base |
+//   cliquelist_gpu_base
 // The observable behaviour -- positional argv, defaults, usage text, banner and FINAL result lines -- is that of the
 // reference mains (src/triangle/main.cc:7-27, src/sgl/main.cc:9-35, src/clique/main.cc:8-28, src/motif/main.cc:9-31,
 // Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.  truss_gpu_base <graph prefix> [k] has no
@@ -19,6 +20,9 @@
 // motiflocal_gpu_base <graph prefix> <k> [out prefix] counts the graphlet-degree orbits of every vertex (gm_motif_local, k = 3 | 4): one line
 // `orbit <o>: sum = S max = M` per orbit, then `pattern <i>: <count>` as motif_gpu_base's last lines; with an out prefix the orbits go to
 // <out>.orbits.u64 as raw little-endian uint64, orbit-major.
+// cliquelist_gpu_base <graph prefix> <k> [out.bin [first [cap]]] lists the k-cliques (gm_clique_list, 3 <= k <= 8): `total_num_cliques = N`
+// in kcl_gpu_base's spelling, then `cliques_written = M`; with out.bin the M rows of the window go there as raw little-endian int32, k ids
+// ascending per row.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -38,11 +42,13 @@
 #define GM_CLIQUELOCAL 8
 #define GM_RECTLOCAL 9
 #define GM_MOTIFLOCAL 10
-#if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL)
+#define GM_CLIQUELIST 11
+#if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL || \
+                        GM_APP == GM_CLIQUELIST)
 #include <hip/hip_runtime_api.h>
 #endif
 #ifndef GM_APP
-#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL|GM_RECTLOCAL|GM_MOTIFLOCAL"
+#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL|GM_RECTLOCAL|GM_MOTIFLOCAL|GM_CLIQUELIST"
 #endif
 
 namespace {
@@ -55,7 +61,7 @@ struct Cli {
   int adj_sorted = 1;  // [adj_sorted(1)] (tc only)
 };
 
-#if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_CLIQUELOCAL && GM_APP != GM_RECTLOCAL && GM_APP != GM_MOTIFLOCAL
+#if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_CLIQUELOCAL && GM_APP != GM_RECTLOCAL && GM_APP != GM_MOTIFLOCAL && GM_APP != GM_CLIQUELIST
 // positional layout: TC has no <second>; the others do
 Cli parse(int argc, char **argv, bool has_second) {
   Cli c;
@@ -88,6 +94,9 @@ void usage_and_exit(const char *self) {
 #elif GM_APP == GM_TCLIST
   std::printf("Usage: %s <graph prefix> [out.bin [first [cap]]]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph triangles.bin 0 1000000\n", self);
+#elif GM_APP == GM_CLIQUELIST
+  std::printf("Usage: %s <graph prefix> <k> [out.bin [first [cap]]]\n", self);
+  std::printf("Example: %s /graph_inputs/mico/graph 4 cliques.bin 0 1000000\n", self);
 #elif GM_APP == GM_CLIQUELOCAL
   std::printf("Usage: %s <graph prefix> <k> [out prefix]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4 cliques\n", self);
@@ -131,7 +140,7 @@ int main(int argc, char **argv) {
   argc = strip_dev_options(argc, argv);
   const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_RECTLOCAL);
   if (argc < (has_second ? 3 : 2)) usage_and_exit(argv[0]);
-#if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL
+#if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL || GM_APP == GM_CLIQUELIST
   Cli c;
   c.graph = argv[1];
   if (argc > 2) c.second = argv[2];  // [k] / [out.bin] / <k> / [out prefix]
@@ -241,6 +250,45 @@ int main(int argc, char **argv) {
   }
   std::printf("total_num_triangles = %llu\n", (unsigned long long)total);
   std::printf("triangles_written = %llu\n", (unsigned long long)written);
+
+#elif GM_APP == GM_CLIQUELIST
+  std::printf("k-clique Listing (undirected graph only)\n");
+  std::fflush(stdout);
+  Graph g(c.graph);
+  g.print_meta_data();
+  const gm_csr csr = g.csr();
+  const int k = std::atoi(c.second.c_str());
+  const std::string out = argc > 3 ? argv[3] : "";
+  const uint64_t first = argc > 4 ? std::strtoull(argv[4], nullptr, 10) : 0;
+  gm_graph *h = nullptr;
+  int rc = gm_graph_upload(&csr, 0, &h);
+  uint64_t total = 0, written = 0;
+  if (rc == GM_OK) rc = gm_clique_list(h, k, nullptr, 0, 0, nullptr, &total, nullptr, nullptr);  // (count only: sizes the buffer)
+  if (rc == GM_OK && !out.empty()) {
+    uint64_t cap = first < total ? total - first : 0;
+    if (argc > 5) cap = std::min<uint64_t>(cap, std::strtoull(argv[5], nullptr, 10));
+    std::vector<int32_t> rows((size_t)k * (size_t)cap);
+    int32_t *d_rows = nullptr;
+    if (cap > 0 && hipMalloc(reinterpret_cast<void **>(&d_rows), sizeof(int32_t) * rows.size()) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && cap > 0) rc = gm_clique_list(h, k, nullptr, first, cap, d_rows, &total, &written, nullptr);
+    if (rc == GM_OK && written > 0 && hipMemcpy(rows.data(), d_rows, sizeof(int32_t) * (size_t)k * (size_t)written, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = GM_ERR_HIP;
+    if (d_rows) (void)hipFree(d_rows);
+    if (rc == GM_OK) {  // (the hosts this runs on are little-endian: the ints go out as they lie in memory)
+      FILE *f = std::fopen(out.c_str(), "wb");
+      const size_t n = (size_t)k * (size_t)written;
+      const bool ok = f && std::fwrite(rows.data(), sizeof(int32_t), n, f) == n;
+      if (f && std::fclose(f) != 0) rc = GM_ERR_IO;
+      if (!ok) rc = GM_ERR_IO;
+    }
+  }
+  gm_graph_free(h);
+  if (rc != GM_OK) {
+    std::fprintf(stderr, "%s: %s %s\n", argv[0], gm_strerror(rc), gm_last_error());
+    return 1;
+  }
+  std::printf("total_num_cliques = %llu\n", (unsigned long long)total);
+  std::printf("cliques_written = %llu\n", (unsigned long long)written);
 
 #elif GM_APP == GM_CLIQUELOCAL
   std::printf("local k-clique counts (undirected graph only)\n");

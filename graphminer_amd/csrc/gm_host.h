@@ -6,7 +6,7 @@
 //   gm_launch.hip  the launch layer (interface: gm_launch.h, for the three solver units only): launch prologue / epilogue, run_pattern,
 //                  gm_kernel_times, gm_tc / gm_clique / gm_motif, and every kernel of the layer
 //   gm_solve_sgl.hip    the SgL family: gm_sgl, the rectangle / house / pentagon map solvers, gm_diamond_support_*, gm_sgl4 / 5 / 6   (host code only)
-//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_rect_local                                     (host code only)
+//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_clique_list, gm_rect_local                                   (host code only)
 //   gm_tools.hip   set-op batch, R-MAT generator, PMC / issue-rate calibration kernels, self test
 // Host-side counterparts in the reference:
 //   GraphGPU::init / init_edgelist          include/graph_gpu.h:69-194
@@ -491,6 +491,10 @@ struct ListOffsets {  // triangle listing (gm_tc_list): the first slot of every 
   DevOwn<unsigned long long> off;  // the last one T), counted and scanned by the first call and kept for the windows that follow
   unsigned long long total = 0;
 };
+struct CliqueListOffsets {  // k-clique listing (gm_clique_list), one per k: the first slot of every entry of the oriented copy (entries + 1
+  DevOwn<unsigned long long> off;  // values, the last one the total), counted and scanned by the first call of that k
+  unsigned long long total = 0;
+};
 
 struct gm_graph {
   int device = 0;
@@ -526,9 +530,10 @@ struct gm_graph {
   Once<SymDegrees> w5deg;
   Once<RevIndex> lrev;
   Once<ListOffsets> list_off;
+  Once<CliqueListOffsets> clique_list_off[6];  // k = 3 .. 8
   // gm_graph_sort_neighbors rewrites the rows: it refuses a handle on which one of these describes them already.  NOT checked (the list
   // predates them): core, core_blocks, long_rows, sup_corner, sup_masks, kst_entries, facts other than sum_c2, rect_lds, house_lds, wrect, rect_local,
-  // w5deg, lrev, list_off, relabel_cache[2], clique_plans -- most of them cannot exist without one that is
+  // w5deg, lrev, list_off, clique_list_off, relabel_cache[2], clique_plans -- most of them cannot exist without one that is
   bool rows_in_use() const {
     return !tables.empty() || edesc.built() || tasklists.built() || kst.built() || dag_cache || relabel_cache[0] || relabel_cache[1] || rect_idx.built() ||
            wedge_blocks.built() || rect_tasks.built() || house_tables.built() || house_tasks.built() || house_blocks.built() || !bitmap_sets.empty() ||
@@ -568,6 +573,9 @@ struct gm_graph {
     DevOwn<unsigned> kcl_scratch;
     size_t kcl_scratch_bytes = 0;
     DevOwn<unsigned long long> ent64; // per entry of the symmetric graph
+    // k-clique listing, on the SYMMETRIC handle: the scratch slots of the rows beyond the LDS matrix (the local counts' slots are left alone)
+    DevOwn<unsigned> kcl_list_scratch;
+    size_t kcl_list_scratch_bytes = 0;
     // local 4-cycle counts, on the graph the walk runs on: the credits of every entry (zeroed by every call).  On the SYMMETRIC handle the
     // counts in the caller's entry order are ent64's, as for the k-cliques
     DevOwn<unsigned long long> racc;
@@ -732,6 +740,7 @@ void gm_touch_orbit_local();
 void gm_touch_local();
 void gm_touch_list();
 void gm_touch_kcl_local();
+void gm_touch_clique_list();
 void gm_touch_cbuild();
 void gm_touch_cmma();
 void gm_touch_cgather();

@@ -19,12 +19,10 @@
 //                             slot of a global scratch; a wave per row i, every lane owns the words w = lane (mod 64) of a set, so a lane
 //                             reads back only what it wrote itself.  Slow and exact.
 // Plain vector loads and stores, atomicOr on the matrices, atomicAdd(unsigned long long) on the counts.
-#include "gm_setops.h"
-#include "gm_mine.h"
+#include "gm_kcl.h"
 
 namespace gm {
 
-constexpr int kKclWords = kKclLocalLdsRow / 32;  // words of a row of the LDS matrix
 constexpr int kKclGrab = 8;                      // roots per dequeue of kcl_local_kernel
 constexpr int kKclParts = 16;                    // workgroups per split root
 
@@ -65,50 +63,6 @@ __device__ __forceinline__ int kcl_wave_entry(const int *__restrict__ rp, const 
   return pos >= 0 ? r0 + pos : -1;
 }
 
-// C_M of a set of up to 32 KW positions held in KW registers.  The next member is found with compile-time indices only (the set stays in
-// registers) and every level has ONE call site of the level below it: the code grows linearly in M.
-template <int M, int KW>
-struct KclSmall {
-  static __device__ __forceinline__ unsigned long long run(const unsigned (&S)[KW], const unsigned *__restrict__ msym, const int stride) {
-    unsigned R[KW];  // the members not visited yet
-#pragma unroll
-    for (int w = 0; w < KW; ++w) R[w] = S[w];
-    unsigned long long c = 0;
-    for (;;) {
-      int w = -1;
-      unsigned x = 0;
-#pragma unroll
-      for (int ww = KW - 1; ww >= 0; --ww)
-        if (R[ww]) { w = ww; x = R[ww]; }
-      if (w < 0) break;
-      const int bit = __ffs((int)x) - 1;
-      const unsigned *Mj = msym + (w * 32 + bit) * stride;
-      unsigned T[KW];
-#pragma unroll
-      for (int w2 = 0; w2 < KW; ++w2) {
-        if (w2 == w) R[w2] = x & (x - 1u);
-        unsigned t = (w2 >= w && w2 < stride) ? (S[w2] & Mj[w2]) : 0u;
-        if (w2 == w) t &= 0xFFFFFFFEu << bit;  // the positions above j
-        T[w2] = t;
-      }
-      c += KclSmall<M - 1, KW>::run(T, msym, stride);
-    }
-    return c;
-  }
-};
-template <int KW>
-struct KclSmall<1, KW> {
-  static __device__ __forceinline__ unsigned long long run(const unsigned (&S)[KW], const unsigned *, int) {
-    unsigned c = 0;
-#pragma unroll
-    for (int w = 0; w < KW; ++w) c += (unsigned)__popc(S[w]);
-    return c;
-  }
-};
-template <int KW>
-struct KclSmall<0, KW> {
-  static __device__ __forceinline__ unsigned long long run(const unsigned (&)[KW], const unsigned *, int) { return 1ull; }
-};
 // the value of the pair (i, l) by a whole WAVE, M >= 2: every lane holds the pair's set, the members j are dealt to the lanes 64 at a time
 // and every lane descends below its own -- C_{M-1}(S & Msym_j & {positions above j}) -- at the same time as the others.  The wave's sum.
 template <int M, int KW>
@@ -177,27 +131,7 @@ __device__ __forceinline__ void kcl_root_lds(const KclLocalParams &p, const int 
   }
   if (tid == 0) *next_word = 0;
   __syncthreads();
-  // Msym: a wave per position i -- N+(L[i]) is streamed against L in LDS, or, when it is much the longer list, L against it
-  for (int i = wave; i < d; i += 4) {
-    const int v = Ls[i], rv = p.rp[v], b = p.rp[v + 1] - rv;
-    const bool stream_row = b <= 4 * d;
-    const int n = stream_row ? b : d;
-    for (int t = lane; t < n; t += GM_WAVE) {
-      int pos = 0;
-      bool hit;
-      if (stream_row) {
-        hit = contains(Ls, d, p.col[rv + t], &pos);
-      } else {
-        int at = 0;
-        hit = contains(p.col + rv, b, Ls[t], &at);
-        pos = t;
-      }
-      if (hit) {
-        atomicOr(&msym[i * stride + (pos >> 5)], 1u << (pos & 31));
-        atomicOr(&msym[pos * stride + (i >> 5)], 1u << (i & 31));
-      }
-    }
-  }
+  kcl_build_msym_lds(p.rp, p.col, Ls, d, stride, msym, wave, lane);  // (gm_kcl.h)
   __syncthreads();
   // a grain: a word of the matrix, or (k >= 5, where a pair is a long descent) 4 bits of one
   constexpr int kSlices = K >= 5 ? 8 : 1;
@@ -304,51 +238,7 @@ __global__ __launch_bounds__(256) void kcl_local_fold_kernel(const long long ne,
   }
 }
 
-// C_M of a set of `stride` words in memory, one wave: lane t owns the words t, t + 64, ... of every set (it alone writes and reads them);
-// the members are walked wave-uniformly through readlane.  `stk`: the sets of the levels below, `stride` words each.  Per-lane partial.
-template <int M>
-struct KclAny {
-  static __device__ __forceinline__ unsigned long long run(const unsigned *S, unsigned *stk, const unsigned *msym, const int stride, const int lane) {
-    unsigned long long c = 0;
-    for (int w0 = 0; w0 < stride; w0 += GM_WAVE) {
-      const unsigned mine = (w0 + lane < stride) ? S[w0 + lane] : 0u;
-      unsigned long long nz = __ballot(mine != 0u);
-      while (nz) {  // wave-uniform
-        const int ww = readfirst((int)__builtin_ctzll(nz));
-        nz &= nz - 1ull;
-        const int w = w0 + ww;
-        unsigned x = (unsigned)readlane((int)mine, ww);
-        while (x) {
-          const int bit = __ffs((int)x) - 1;
-          x &= x - 1u;
-          const unsigned *Mj = msym + (size_t)(w * 32 + bit) * stride;
-          for (int w2 = lane; w2 < stride; w2 += GM_WAVE) {
-            unsigned t = (w2 >= w) ? (S[w2] & Mj[w2]) : 0u;
-            if (w2 == w) t &= 0xFFFFFFFEu << bit;
-            stk[w2] = t;
-          }
-          c += KclAny<M - 1>::run(stk, stk + stride, msym, stride, lane);
-        }
-      }
-    }
-    return c;
-  }
-};
-template <>
-struct KclAny<1> {
-  static __device__ __forceinline__ unsigned long long run(const unsigned *S, unsigned *, const unsigned *, const int stride, const int lane) {
-    unsigned c = 0;
-    for (int w = lane; w < stride; w += GM_WAVE) c += (unsigned)__popc(S[w]);
-    return c;
-  }
-};
-template <>
-struct KclAny<0> {
-  static __device__ __forceinline__ unsigned long long run(const unsigned *, unsigned *, const unsigned *, int, const int lane) { return lane == 0 ? 1ull : 0ull; }
-};
-
 // the workgroup's scratch slot: the spoke sums (max_deg uint64), the matrix (max_deg rows), the four waves' set stacks (kKclMaxLevels sets each)
-constexpr int kKclMaxLevels = 5;  // k <= 8: the pair's own set and the sets of C_4 .. C_2
 unsigned long long kcl_local_scratch_words(int max_deg) {
   const unsigned long long D = (unsigned long long)std::max(max_deg, 1), S = (D + 31) >> 5;
   return (2ull * D + D * S + 4ull * kKclMaxLevels * S + 1ull) & ~1ull;  // (even: the slots stay 8-byte aligned)
@@ -387,16 +277,7 @@ __global__ __launch_bounds__(256) void kcl_local_wide_kernel(const KclLocalParam
     for (int i = tid; i < d; i += 256) acc[i] = 0ull;
     __threadfence();
     __syncthreads();
-    for (int i = wave; i < d; i += 4) {
-      const int v = L[i], rv = p.rp[v], b = p.rp[v + 1] - rv;
-      for (int t = lane; t < b; t += GM_WAVE) {
-        int pos = 0;
-        if (contains(L, d, p.col[rv + t], &pos)) {
-          atomicOr(&msym[(size_t)i * stride + (pos >> 5)], 1u << (pos & 31));
-          atomicOr(&msym[(size_t)pos * stride + (i >> 5)], 1u << (i & 31));
-        }
-      }
-    }
+    kcl_build_msym_wide(p.rp, p.col, L, d, stride, msym, wave, lane);  // (gm_kcl.h)
     __threadfence();
     __syncthreads();
     for (;;) {  // a wave per row i, taken dynamically: the first rows hold the most pairs

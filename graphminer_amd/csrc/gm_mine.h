@@ -814,6 +814,27 @@ struct ListParams {
 };
 hipError_t list_count_scan(const ListParams &p, int cu_count, hipStream_t stream);  // fills p.off; synchronises the stream
 hipError_t launch_list_fill(const ListParams &p, int cu_count, hipStream_t stream);
+// k-clique listing (gm_clique_list.hip): every root's out-list is walked over its adjacency matrix (gm_kcl.h) twice -- count per entry, then
+// fill.  Rows of up to kKclLocalLdsRow entries keep the matrix in LDS and the pair values of the count and of the fill's scan in registers:
+// 2 per set for rows of up to kKclListRegs2Row entries, 8 up to kKclListRegs8Row, 16 beyond; longer rows take a global scratch slot per
+// workgroup.  Exported through gm_constant ("kcl_list_regs2_row", "kcl_list_regs8_row"; "kcl_local_lds_row" is the third boundary).
+constexpr int kKclListRegs2Row = 64, kKclListRegs8Row = 256;
+struct KclListParams {
+  int nv, k, max_deg;               // max_deg: the longest row (sizes the scratch slot)
+  long long ne;
+  const int *rp, *col;              // the oriented copy as numbered: it keeps the caller's ids
+  unsigned long long *cnt;          // count: per entry (u, L[i]) the k-cliques rooted at u whose lowest out-list position is i (one plain store each)
+  const unsigned long long *off;    // fill: ne + 1 values, the exclusive scan of cnt ([ne] = the total)
+  unsigned long long first, nw;     // fill: the window of slots [first, first + nw)
+  int *out;                         // fill: k ints per slot of the window
+  unsigned *queue, *queue_wide;     // zeroed by the caller: the dequeue words of the LDS kernel and of the scratch kernel
+  unsigned *scratch;                // rows beyond kKclLocalLdsRow: gridDim.x slots of scratch_words (kcl_local_scratch_words(max_deg)) words
+  unsigned long long scratch_words;
+};
+// count + scan: off[0 .. ne] = the first slot of every entry, off[ne] = the total.  grid_wide = 0: no row needs the scratch kernel.
+// Synchronises the stream (the temporaries go back).
+hipError_t kcl_list_count_scan(const KclListParams &p, unsigned long long *off, int grid, int grid_wide, hipStream_t stream);
+hipError_t launch_kcl_list_fill(const KclListParams &p, int grid, int grid_wide, hipStream_t stream);
 size_t mine_lds_bytes(Pattern pat);
 // the big-LDS classes (gm_mine_wide.hip): cls = 1 (mid rows) or 2 (big rows); DIAMOND, MOTIF3, MOTIF4E only
 hipError_t launch_mine_wide(Pattern pat, int cls, const MineParams &p, int grid_blocks, hipStream_t stream);

@@ -1,6 +1,6 @@
-// gm_solve_local.hip -- local counts, the k-truss, the triangle listing, the local k-clique and 4-cycle counts over the launch layer (gm_launch.h):
-// gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_rect_local, gm_motif_local.  Host code only: the kernels are
-// gm_local.hip's, gm_list.hip's, gm_kcl_local.hip's, gm_rect_local.hip's and gm_orbit_local.hip's, so this unit has no code object and no warm-up.
+// gm_solve_local.hip -- local counts, the k-truss, the triangle and k-clique listings, the local k-clique and 4-cycle counts over the launch layer (gm_launch.h):
+// gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_list, gm_clique_local, gm_rect_local, gm_motif_local.  Host code only: the kernels are
+// gm_local.hip's, gm_list.hip's, gm_clique_list.hip's, gm_kcl_local.hip's, gm_rect_local.hip's and gm_orbit_local.hip's, so this unit has no code object and no warm-up.
 #include "gm_launch.h"
 #include "gm_orbit.h"
 
@@ -481,5 +481,76 @@ extern "C" int gm_tc_list(const gm_graph *sym, const gm_launch *la, uint64_t fir
   if (total) *total = T;
   if (n_written) *n_written = nw;
   if (st) st->kernel_ms = s.kernel_ms;
+  return GM_OK;
+}
+
+// ---- k-clique listing (gm_clique_list.hip; DESIGN.md "k-clique listing") -----------------------------------------------------------------
+// On the oriented copy as numbered, for gm_tc_list's reason: it keeps the caller's ids, so a row is written as it is found.  The count
+// stage runs once per (handle, k) -- every entry's first slot stays on the SYMMETRIC handle -- and a window is one fill launch (two when a
+// row is longer than the LDS matrix) that walks only the roots, entries and pairs it meets.
+extern "C" int gm_clique_list(const gm_graph *sym, int k, const gm_launch *la, uint64_t first, uint64_t cap, int32_t *d_cliques, uint64_t *total,
+                              uint64_t *n_written, gm_stats *st) {
+  if (total) *total = 0;
+  if (n_written) *n_written = 0;
+  if (!sym || k < 3 || k > GM_MAX_CLIQUE_K) return GM_ERR_INVALID;
+  if (int rc = local_refusals(sym, la)) return rc;
+  if (k > 8) {
+    g_last_error = "gm_clique_list: k = 9 .. " + std::to_string(GM_MAX_CLIQUE_K) + " is not supported yet (3 <= k <= 8)";
+    return GM_ERR_UNSUPPORTED;
+  }
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  uint64_t unused = 0;
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, &unused, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+  if (sym->ne == 0) return GM_OK;
+  if (const int rc_dag = ensure_dag_cache(g)) return rc_dag;  // (the oriented copy, cached on the handle)
+  const gm_graph *dag = g->dag_cache;
+  if (int rc = reject_big(dag)) return rc;
+  const bool wide = dag->max_deg > kKclLocalLdsRow;
+  const unsigned long long slot_words = kcl_local_scratch_words(dag->max_deg);
+  const size_t slot_bytes = sizeof(unsigned) * (size_t)slot_words;
+  const int grid = grid_for(((long long)dag->nv + 7) / 8, g->cu_count, 3);
+  const int grid_wide = wide ? clamp_grid((long long)(kKclScratchBudget / slot_bytes), (long long)g->cu_count * 2) : 0;
+  if (wide) {  // (a slot that does not fit the device: the allocation fails and the call is refused)
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (int rc = grow_dev(g->local.kcl_list_scratch, &g->local.kcl_list_scratch_bytes, slot_bytes * (size_t)grid_wide)) return rc;
+  }
+  KclListParams kp;
+  memset(&kp, 0, sizeof kp);
+  kp.nv = dag->nv; kp.ne = dag->ne; kp.k = k; kp.max_deg = std::max(dag->max_deg, 1);
+  kp.rp = dag->d_rp; kp.col = dag->d_col;
+  kp.queue = queue_word(g, QW_MAIN); kp.queue_wide = queue_word(g, QW_CLASS1);
+  kp.scratch = g->local.kcl_list_scratch; kp.scratch_words = slot_words;
+  HIP_TRY(hipMemsetAsync(g->d_counters, 0, kCounterBlockBytes, ctx.stream));  // (a first call oriented the graph since begin_launch)
+  if (int rc = start_timer(ctx)) return rc;
+  Once<CliqueListOffsets> &state = g->clique_list_off[k - 3];
+  if (int rc = state.ensure(g->mu, [&](CliqueListOffsets &lo) {  // (once per handle and k)
+        if (dag->ne > 0) {
+          const size_t ne = (size_t)dag->ne;
+          HIP_TRY(lo.off.alloc(sizeof(unsigned long long) * (ne + 1)));
+          HIP_TRY(kcl_list_count_scan(kp, lo.off, grid, grid_wide, ctx.stream));
+          HIP_TRY(hipMemcpyAsync(&lo.total, lo.off + ne, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx.stream));
+          HIP_TRY(hipMemsetAsync(g->d_counters, 0, kCounterBlockBytes, ctx.stream));  // (the fill dequeues from the same words)
+          HIP_TRY(hipStreamSynchronize(ctx.stream));
+        }
+        return kOnceBuilt;
+      })) return rc;
+  const uint64_t T = state->total;
+  const uint64_t nw = (d_cliques && first < T) ? std::min<uint64_t>(cap, T - first) : 0;
+  if (nw > 0) {
+    kp.off = state->off; kp.first = first; kp.nw = nw; kp.out = d_cliques;
+    HIP_TRY(launch_kcl_list_fill(kp, grid, grid_wide, ctx.stream));
+  }
+  gm_stats s;
+  memset(&s, 0, sizeof s);
+  if (int rc = end_launch(ctx, FIN_COPY, 0, &unused, 1, &s)) return rc;
+  if (total) *total = T;
+  if (n_written) *n_written = nw;
+  if (st) {
+    st->kernel_ms = s.kernel_ms;
+    st->grid = (uint32_t)grid;
+  }
   return GM_OK;
 }

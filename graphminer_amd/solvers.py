@@ -373,3 +373,29 @@ def tc_list(g: DeviceGraph, *, first=0, cap=None, chunk=0, return_stats=False, *
         tri = _to_numpy(buf, 3 * int(written.value), "int32").reshape(-1, 3)
         stats.kernel_ms += st.kernel_ms
     return (int(total.value), tri, stats) if return_stats else (int(total.value), tri)
+
+
+# ---- k-clique listing (include/graphminer_amd.h: gm_clique_list) --------------------------------------------------------------------------
+def clique_list(g: DeviceGraph, k, *, first=0, cap=None, chunk=0, return_stats=False, **kw):
+    """(k-cliques as np.int32[n_written, k], total) of a SYMMETRIC graph, 3 <= k <= 8: rows strictly ascending in the caller's numbering,
+    every k-clique once, in the fixed listing order of (handle, k); the window is the `cap` rows from index `first` (cap=None: all of
+    them).  A count-only call sizes the buffer, a second call fills it; the stats add the two up.  One GPU."""
+    import numpy as np
+    import torch
+
+    lib = _lib.load()
+    k = int(k)
+    la, st, total, written = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0), C.c_uint64(0)
+    _lib.check(lib.gm_clique_list(g.handle, k, C.byref(la), 0, 0, None, C.byref(total), None, C.byref(st)), "gm_clique_list")
+    stats = _stats(st)
+    first = int(first)
+    n = max(int(total.value) - first, 0) if first >= 0 else 0
+    n = n if cap is None else min(n, int(cap))
+    rows = np.empty((0, k), dtype=np.int32)
+    if n > 0:
+        buf = _dev_array(g, k * n, torch.int32)
+        _lib.check(lib.gm_clique_list(g.handle, k, C.byref(la), first, n, buf.data_ptr(), C.byref(total), C.byref(written), C.byref(st)),
+                   "gm_clique_list")
+        rows = _to_numpy(buf, k * int(written.value), "int32").reshape(-1, k)
+        stats.kernel_ms += st.kernel_ms
+    return (rows, int(total.value), stats) if return_stats else (rows, int(total.value))

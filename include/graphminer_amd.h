@@ -416,6 +416,30 @@ int gm_clique(const gm_graph *dag, int k, const gm_launch *launch, uint64_t *tot
 int gm_clique_local(const gm_graph *sym, int k, const gm_launch *launch, uint64_t *d_vertex_cnt, uint64_t *d_entry_cnt, uint64_t *total,
                     gm_stats *stats);
 
+/* ---- k-clique listing (csrc/gm_clique_list.hip; DESIGN.md "k-clique listing") ----------------------------------------------------------
+ * Every k-clique of a SYMMETRIC graph exactly once, 3 <= k <= 8, as k ids of the CALLER's numbering, strictly ascending, 4 k bytes per row.
+ *   d_cliques DEVICE int32[k * cap], or NULL (then cap is ignored: count only)
+ *   first     index of the first row wanted in the listing order of (handle, k);  cap: at most this many are written
+ *   total     (may be NULL) the k-clique count of the whole graph, whatever the window: gm_clique(k) of the oriented copy
+ *   n_written (may be NULL) min(cap, total - first), 0 when first >= total or d_cliques == NULL
+ * The listing order is fixed for a (handle, k): calls with windows [0,c), [c,2c), ... write, concatenated, exactly the sequence one call
+ * with first = 0, cap >= total writes.  Nothing is written beyond k * n_written ints.  The order: ascending ROOT -- the clique's lowest
+ * vertex in the order of gm_graph_orient, by degree and then by id -- and within a root lexicographic on the other k - 1 members taken as
+ * their ascending positions in N+(root) of the oriented copy as numbered (which are ascending ids).  At k = 3 the SET of rows is
+ * gm_tc_list's, the order is not.
+ * The first call of a k on a handle counts, per entry (root, L[i]) of the oriented copy, the cliques whose lowest out-list position is i,
+ * and scans the counts (kept on the handle per k); every call with a buffer then walks only the roots, entries and pairs whose slots meet
+ * its window.  The call runs on the oriented copy as numbered -- it keeps the caller's ids -- so launch->tune[6] is ignored.  Rows of any
+ * length are exact: those beyond 512 entries take a scratch slot per workgroup (sized by the longest row; a slot that does not fit the
+ * device refuses the call).
+ * The contract of the local counts and of gm_tc_list: one GPU, synchronous; a null handle -> GM_ERR_INVALID, >= 2^31 entries ->
+ * GM_ERR_TOO_LARGE, world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED, unsorted rows -> GM_ERR_INVALID, k < 3 or k > GM_MAX_CLIQUE_K ->
+ * GM_ERR_INVALID, 9 <= k <= GM_MAX_CLIQUE_K -> GM_ERR_UNSUPPORTED, ne == 0 -> GM_OK with zeros; launch->stream is honoured;
+ * stats->kernel_ms covers every kernel of the call; before or after any other solver on the handle, whose arrays it leaves alone; ONE
+ * such call at a time per handle; what it keeps on the handle is freed with the handle. */
+int gm_clique_list(const gm_graph *sym, int k, const gm_launch *launch, uint64_t first, uint64_t cap, int32_t *d_cliques, uint64_t *total,
+                   uint64_t *n_written, gm_stats *stats);
+
 /* ---- local 4-cycle counts (csrc/gm_rect_local.hip; DESIGN.md "Local 4-cycle counts") --------------------------------------------------
  * The 4-cycles (edge-induced, as the `rectangle` of gm_sgl counts them: src/sgl/cpu_kernels/rectangle.h) at every vertex and on every
  * edge, in the CALLER's numbering and entry order: the input of square clustering coefficients, of butterfly supports on bipartite data,
