@@ -183,7 +183,7 @@ int ensure_core_bitmap(gm_graph *g) {
   if (rc) return rc;
   return g->core.ensure(g->mu, [&](HubCore &c) {
     long long want = kCoreHDefault;
-    if (const char *e = gm_sweep_env("GM_CORE_H")) want = atoll(e);  // (sweeps; 0 switches the gathered build off)
+    if (const char *e = gm_opt("GM_CORE_H")) want = atoll(e);  // (tests, sweeps: the core's base inside a planted row; 0 switches the gathered build off)
     if (!topo || g->d_rp == nullptr || g->nv < 64 || want < 64) return kOnceNotApplicable;
     SetupTimer timer;
     HIP_TRY(hipSetDevice(g->device));

@@ -1456,6 +1456,47 @@ extern "C" int gm_clique4_gather_info(const gm_graph *dag, int64_t info[4]) {
   return GM_OK;
 }
 
+// tooling (tests): what the whole-graph 4-clique plan of this handle holds, on the copy the count ran on -- the handle itself
+// (as_numbered: a call under GM_T6_AS_NUMBERED; a DAG that is numbered topologically), else its topological copy.  Read-only: nothing is
+// built here, no device pass (GM_ERR_INVALID: no such call yet).
+//   out[0] topo   [1] stage   [2] core_base (-1: no core)   [3] rounds   [4] wide vertices   [5 .. 7] ... per matrix-core class 0 / 1 / 2
+//   [8] build tasks (all rounds)   [9] gather units   [10] gather items   [11] chunks and [12] entries of the rows left to the mining
+//   kernel's arena path (> kCbMaxDeg; the table of that launch, -1 / -1: none was built)
+extern "C" int gm_clique_plan_info(const gm_graph *dag, int as_numbered, int64_t *out, int n) {
+  if (!dag || !out || n < 13) return GM_ERR_INVALID;
+  auto plan_of = [](gm_graph *g) -> const CliquePlan * {
+    if (!g) return nullptr;
+    for (auto &pl : g->clique_plans)
+      if (pl.world == 1) return &pl;
+    return nullptr;
+  };
+  gm_graph *self = const_cast<gm_graph *>(dag), *g = self;
+  if (!as_numbered && self->relabel_cache[2]) g = self->relabel_cache[2];
+  std::lock_guard<std::mutex> lk(g->mu);
+  const CliquePlan *pl = plan_of(g);
+  if (!pl) return GM_ERR_INVALID;
+  for (int i = 0; i < 13; ++i) out[i] = 0;
+  out[0] = pl->topo ? 1 : 0;
+  out[1] = pl->stage;
+  out[2] = pl->core_base;
+  out[3] = (int64_t)pl->rounds.size();
+  out[4] = (int64_t)pl->verts.size();
+  for (const auto &rd : pl->rounds) {
+    for (int c = 0; c < 3; ++c) out[5 + c] += (int64_t)(rd.mcls_begin[c + 1] - rd.mcls_begin[c]);
+    out[8] += (int64_t)rd.n_tasks;
+    out[9] += (int64_t)rd.n_gunits;
+    out[10] += (int64_t)rd.n_gitems;
+  }
+  out[11] = out[12] = -1;
+  for (const auto &t : g->tables)
+    if (t.rf.only_lo == kCbMaxDeg && t.rf.skip_clique_wide == 0 && t.bit_words == kBitWords && t.rf.tct == 0) {
+      out[11] = (int64_t)t.n;
+      out[12] = (int64_t)t.total_edges;
+      break;
+    }
+  return GM_OK;
+}
+
 // (module warm-up, gm_graph.hip finish_handle: HIP loads the code object of a translation unit when one of its kernels is first launched)
 __global__ void gm_touch_launch_kernel() {}
 void gm_touch_launch() { hipLaunchKernelGGL(gm_touch_launch_kernel, dim3(1), dim3(1), 0, 0); }

@@ -8,7 +8,7 @@
 // DEVELOPER OPTIONS.  The shipped library reads NO algorithm switch from the environment (a drop-in behind someone
 // else's main must not change what it runs on an ambient variable).  What tests need to reach a path on a small graph, and the documented
 // fallbacks, are named options set through the C ABI -- gm_dev_option(name, value), include/graphminer_amd.h -- and read with gm_opt():
-//   GM_DIAMOND_PER_EDGE, GM_SUP_STREAM / GM_SUP_NO_MASKS / GM_SUP_MASK_MIN (edge supports), GM_TC_CORE_H / GM_SUP_CORE_H (hub corner),
+//   GM_DIAMOND_PER_EDGE, GM_SUP_STREAM / GM_SUP_NO_MASKS / GM_SUP_MASK_MIN (edge supports), GM_TC_CORE_H / GM_SUP_CORE_H (hub corner), GM_CORE_H (the 4-clique's core bitmap),
 //   GM_BIG_NE, GM_KST_MAX_KEYS, GM_TOPO_MIN_ROW, GM_WIDE_ARENA_MB, GM_TCT_SPLIT_ALWAYS, GM_TCH_WIDE_NE, GM_RECT_LDS_MIN / GM_RECT_LDS_RANGES / GM_WRECT_RANGE / GM_RECT_LOCAL_RANGE (limits lowered for tests), GM_ORIENT_TWO_GATHERS,
 //   GM_RELABEL_GLOBAL_SORT (the previous setup paths, compared in tests), GM_NO_TEMP_POOL, and the n-GPU runner's GM_FORCE_RCCL_PATH /
 //   GM_DIAMOND_SUPPORTS_MAX_WORLD (host/multi.cc).  Only GM_SETUP_TRACE (setup steps on stderr: diagnostics, no algorithm) is an

@@ -126,6 +126,18 @@ def map_plan_info(g: DeviceGraph, pattern: str) -> dict:
     return info
 
 
+def clique_plan_info(dag: DeviceGraph, as_numbered: bool = False) -> dict:
+    """what the plan of a whole-graph CliqueSolver(dag, 4) holds (gm_clique_plan_info; after a first such call on this handle), on the copy
+    that call ran on (as_numbered: a call with tune[6] & 0x200): "topo", "stage", "core_base" (-1: no core), "rounds", "wide" vertices and
+    "wide_by_class" (matrix-core classes 0 / 1 / 2), build "tasks", "gather_units", "gather_items", and the "arena_chunks" / "arena_entries"
+    of the rows beyond cb_max_deg that stay with the mining kernel (-1: that launch built no table)"""
+    out = (C.c_int64 * 13)()
+    _lib.check(_lib.load().gm_clique_plan_info(dag.handle, 1 if as_numbered else 0, out, 13), "gm_clique_plan_info")
+    return {"topo": bool(out[0]), "stage": int(out[1]), "core_base": int(out[2]), "rounds": int(out[3]), "wide": int(out[4]),
+            "wide_by_class": [int(out[5]), int(out[6]), int(out[7])], "tasks": int(out[8]), "gather_units": int(out[9]),
+            "gather_items": int(out[10]), "arena_chunks": int(out[11]), "arena_entries": int(out[12])}
+
+
 def CliqueSolver(g: DeviceGraph, k: int, *, rank=0, world=1, chunk=0, return_stats=False, **kw):
     """k-clique count on the ORIENTED graph."""
     lib = _lib.load()

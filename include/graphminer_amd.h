@@ -557,6 +557,14 @@ int gm_clique4_level2_bytes(const gm_graph *dag, uint64_t *bytes);
  * row, the 16-bit column table from the unit's first row on), info[2] = work items, info[3] = blocks of the core.  All 0: the row-major gather. */
 int gm_clique4_gather_info(const gm_graph *dag, int64_t info[4]);
 
+/* Tooling (tests): after a whole-graph gm_clique(dag, 4) -- what the plan of that call holds, on the copy it ran on: the handle itself
+ * (as_numbered != 0: a call under GM_T6_AS_NUMBERED; a DAG numbered topologically), else its topological copy.  Read-only, no device pass;
+ * GM_ERR_INVALID: no such call yet, or n_out < 13.  out[0] = the copy is topological, [1] = LDS stage of the build kernel, [2] = first vertex
+ * of the core bitmap (-1: no core), [3] = rounds, [4] = wide vertices, [5 .. 7] = ... per matrix-core class 0 / 1 / 2, [8] = build tasks,
+ * [9] = gather units, [10] = gather items, [11] / [12] = chunks / entries of the rows beyond "cb_max_deg", left to the mining kernel's arena
+ * path (-1 / -1: that launch built no table). */
+int gm_clique_plan_info(const gm_graph *dag, int as_numbered, int64_t *out, int n_out);
+
 /* PMC calibration (tooling): one pass of dword-per-lane coalesced loads over d_buf[0..n), sum -> *d_out.
  * Exactly 4n bytes are read once; run under `rocprofv3 --pmc FETCH_SIZE` to get the counter scale for the
  * access width the mining kernels use (MI355X_MICROARCH.md: FETCH_SIZE is calibrated only for 16 B/lane). */

@@ -121,3 +121,19 @@ def kcl_row_constants():
         _lib.check(lib.gm_constant(name.encode(), C.byref(v)), "gm_constant")
         out[key] = int(v.value)
     return out
+
+
+def clique_count_constants():
+    """the constants that place a DAG row on its path of the global k-clique count (gm_constant: a host call, no GPU), by the names the
+    cells of tests/planted_count_cells.py use"""
+    import ctypes as C
+
+    from graphminer_amd import _lib
+    from planted_count_cells import CONST_NAMES
+
+    lib, out = _lib.load(), {}
+    for name in CONST_NAMES:
+        v = C.c_int64(0)
+        _lib.check(lib.gm_constant(name.encode(), C.byref(v)), "gm_constant")
+        out[name] = int(v.value)
+    return out

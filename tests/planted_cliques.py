@@ -7,8 +7,9 @@ gm_clique_local (csrc/gm_kcl_local.hip) attributes cliques: a pair of positions 
 on the right entry of the right row.  On a complete graph every entry carries the same value, so a wrong position passes; a random graph
 with a row of 2049 entries has no plain reference that finishes.  These graphs have long rows AND a different value on nearly every entry:
 
-  H      d vertices that hold disjoint BLOCKS, each a small graph on its own vertex set: `complete` (a clique, closed forms) or `random`
-         (a seeded G(b, p), another graph per block)
+  H      d vertices that hold disjoint BLOCKS, each a small graph on its own vertex set: `complete` (a clique, closed forms), `random`
+         (a seeded G(b, p), another graph per block) or `hub` (its first vertex joined to all the others, those a disjoint union of
+         random blocks: one long matrix row over a sparse sub-matrix, for the global count's cells)
   I      an independent set; every member is joined to a chosen union of WHOLE blocks
   leaves every H vertex is padded with private degree-1 leaves to one common degree D (above every degree of a root), as the probe graphs
          do (tests/probe_graphs.py)
@@ -43,7 +44,7 @@ VARIANTS = 32  # a random block is G(b, p) of seed (b, its index mod VARIANTS): 
 
 @dataclass(frozen=True)
 class Block:
-    kind: str       # "complete" | "random"
+    kind: str       # "complete" | "random" | "hub" (one vertex joined to all of a disjoint union of random blocks: tests/planted_count_cells.py)
     size: int
     p: float = 1.0  # random: the edge probability
     seed: int = 0   # random: the variant
@@ -70,9 +71,25 @@ def _csr(n: int, s: np.ndarray, t: np.ndarray):
     return rp, t[order], order
 
 
+def hub_parts(blk: Block) -> tuple:
+    """the random blocks under the hub (vertex 0) of a "hub" block, in id order"""
+    return random_blocks(blk.size - 1, LOW[0], LOW[1], blk.p, seed=blk.seed)
+
+
 @functools.lru_cache(maxsize=None)
 def block_pairs(blk: Block):
     """the edges a < b of a block on local ids 0 .. size - 1, as two arrays"""
+    if blk.kind == "hub":  # vertex 0 joined to every other vertex; those: disjoint random blocks of the LOW sizes (hub_parts), p and seed the block's
+        a, b, off = [np.zeros(blk.size - 1, dtype=np.int64)], [np.arange(1, blk.size, dtype=np.int64)], 1
+        for part in hub_parts(blk):
+            pa, pb = block_pairs(part)
+            a.append(pa + off)
+            b.append(pb + off)
+            off += part.size
+        a, b = np.concatenate(a), np.concatenate(b)  # (rows ascending, then ids: the order block_values relies on)
+        a.setflags(write=False)
+        b.setflags(write=False)
+        return a, b
     a, b = np.triu_indices(blk.size, 1)
     if blk.kind == "random":
         rng = np.random.default_rng([blk.size, blk.seed, int(round(blk.p * 1000))])
