@@ -96,6 +96,7 @@ SYMBOLS = [
     ("gm_sgl4_partial", C.c_int, [_P, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
     ("gm_sgl4_finish", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("gm_sgl5_raw", C.c_int, [_P, C.c_char_p, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
+    ("gm_sgl5_raw_need", C.c_int, [_P, C.c_uint32, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
     ("gm_sgl5_finish", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("gm_sgl6_need", C.c_int, [C.c_char_p, C.POINTER(C.c_uint32)]),
     ("gm_sgl6_raw", C.c_int, [_P, C.c_uint32, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),

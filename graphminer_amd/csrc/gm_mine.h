@@ -636,6 +636,9 @@ struct WtriEntryParams {
   unsigned long long *tv2;  // per vertex: twice its triangles (zeroed by the caller)
   unsigned long long *out;  // [0] += sum t, [1] += sum C(t,2), [2] += sum C(t,2) (d(u) + d(v) - 6)
 };
+// chouse_kernel keeps S = N(u) ^ N(v) in LDS while the shorter of the two lists has at most kChouseCap keys, else in the wave's slot of the
+// global scratch.  Exported through gm_constant ("chouse_lds_keys"): the tests place spine edges on both sides.
+constexpr int kChouseCap = 1024;
 struct ChouseParams {
   int nv;
   long long ne;

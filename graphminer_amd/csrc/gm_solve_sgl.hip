@@ -709,6 +709,11 @@ extern "C" int gm_sgl5_raw(const gm_graph *sym, const char *pattern, const gm_la
   if (!sym || !pattern || !raw) return GM_ERR_INVALID;
   return sgl5_raw_needs(sym, strcmp(pattern, "all") == 0 ? (1u << GM_SGL5_NRAW) - 1u : sgl5_needs(pattern), la, raw, st);
 }
+// the same by bit mask (bit i: raw[i]), as gm_sgl6_raw takes its sums: A or B of a dense graph without its 4-cliques
+extern "C" int gm_sgl5_raw_need(const gm_graph *sym, uint32_t need, const gm_launch *la, uint64_t raw[GM_SGL5_NRAW], gm_stats *st) {
+  if (!sym || !raw || !need || (need >> GM_SGL5_NRAW)) return GM_ERR_INVALID;
+  return sgl5_raw_needs(sym, need, la, raw, st);
+}
 
 extern "C" int gm_sgl(const gm_graph *sym, const char *pattern, const gm_launch *la, uint64_t *total, gm_stats *st) {
   if (!pattern) return GM_ERR_INVALID;

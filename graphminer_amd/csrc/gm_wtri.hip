@@ -269,7 +269,6 @@ __global__ __launch_bounds__(256) void path5_kernel(int nv, const int *__restric
 // Q: one wave per undirected edge {u, v}, v < u, of the symmetric graph: S = N(u) ^ N(v) materialised (LDS up to kChouseCap keys of the
 // shorter list, else the wave's slot of the global scratch), then for every member c the keys of S ^ N(c) -- the shorter streamed, the
 // longer bisected (gm_setops.h) -- times (|S| - 2).
-constexpr int kChouseCap = 1024;
 __global__ __launch_bounds__(256) void chouse_kernel(const ChouseParams p) {
   __shared__ int sets[4][kChouseCap];
   const long long wave0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((long long)gridDim.x * blockDim.x) >> 6;

@@ -182,10 +182,15 @@ SGL5_PATTERNS = ("hourglass", "taileddiamond", "taileddiamond2", "closedhouse", 
 SGL5_RAW = ("T", "D", "W", "A", "B", "H", "S", "P", "K4", "R", "Q")
 
 
-def sgl5_raw(g: DeviceGraph, pattern: str = "all", *, chunk=0, return_stats=False, **kw):
-    """the raw sums `pattern` (one of SGL5_PATTERNS, or "all") needs, in the order of SGL5_RAW; the others are 0.  One GPU."""
+def sgl5_raw(g: DeviceGraph, pattern="all", *, chunk=0, return_stats=False, **kw):
+    """the raw sums `pattern` needs -- one of SGL5_PATTERNS, "all", an iterable of names of SGL5_RAW, or a bit mask -- in the order of
+    SGL5_RAW; the others are 0.  One GPU."""
     la, st, raw = _launch(0, 1, chunk, **kw), gm_stats(), (C.c_uint64 * len(SGL5_RAW))()
-    _lib.check(_lib.load().gm_sgl5_raw(g.handle, pattern.encode(), C.byref(la), raw, C.byref(st)), "gm_sgl5_raw")
+    if isinstance(pattern, str):
+        _lib.check(_lib.load().gm_sgl5_raw(g.handle, pattern.encode(), C.byref(la), raw, C.byref(st)), "gm_sgl5_raw")
+    else:
+        need = pattern if isinstance(pattern, int) else sum(1 << SGL5_RAW.index(k) for k in set(pattern))
+        _lib.check(_lib.load().gm_sgl5_raw_need(g.handle, need, C.byref(la), raw, C.byref(st)), "gm_sgl5_raw_need")
     res = [int(x) for x in raw]
     return (res, _stats(st)) if return_stats else res
 

@@ -265,9 +265,12 @@ int gm_sgl4_finish(const char *pattern, const uint64_t raw[4], uint64_t *total);
  * oriented copy and one more pass over its triangles (csrc/gm_wtri.hip), K4 and R from gm_clique / gm_sgl("rectangle"), P and Q from one
  * kernel each on the symmetric graph.  stats->kernel_ms covers every kernel of the call, stats->tasks = the graph's directed entries.
  * One GPU, synchronous: world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED (the closed forms are applied on the host), a handle of
- * >= 2^31 entries -> GM_ERR_TOO_LARGE, any other name -> GM_ERR_INVALID.  gm_sgl5_finish is host-only (no device). */
+ * >= 2^31 entries -> GM_ERR_TOO_LARGE, any other name -> GM_ERR_INVALID.  gm_sgl5_finish is host-only (no device).
+ * gm_sgl5_raw_need: the same with the sums named by a bit mask (bit i = raw[i]) instead of a pattern -- A or B without the 4-clique count
+ * of a dense graph; need == 0 or bits beyond GM_SGL5_NRAW -> GM_ERR_INVALID. */
 #define GM_SGL5_NRAW 11
 int gm_sgl5_raw(const gm_graph *sym, const char *pattern, const gm_launch *launch, uint64_t raw[GM_SGL5_NRAW], gm_stats *stats);
+int gm_sgl5_raw_need(const gm_graph *sym, uint32_t need, const gm_launch *launch, uint64_t raw[GM_SGL5_NRAW], gm_stats *stats);
 int gm_sgl5_finish(const char *pattern, const uint64_t raw[GM_SGL5_NRAW], uint64_t *total);
 
 /* The two 6-vertex patterns of the reference's dispatcher (src/sgl/omp_base.cc:46-50; cpu_kernels/6path.h, dumbbell.h) as closed forms of
@@ -589,7 +592,8 @@ int gm_issue_calib(int kind, int waves_per_simd, int iters, double *cycles_per_w
  * of bench.py needs to know about the kernels, read from the headers they are compiled with -- and the sizes at which the map kernels of
  * the rectangle / the house change path, for the tests that place graphs on both sides: "map_rect_block" (ids of a block of 32-bit
  * counters), "map_one_task_rows", "map_long_row", "map_tile_group", "map_mark_window", "map_house_ids", "map_house_wg_row",
- * "map_house_wg_queue", "map_heavy_centre", "map_house_fw16_rows", "map_lds_min_default", "map_house_walk_min_default".  GM_ERR_INVALID for an unknown name. */
+ * "map_house_wg_queue", "map_heavy_centre", "map_house_fw16_rows", "map_lds_min_default", "map_house_walk_min_default"; "chouse_lds_keys": the
+ * keys of the shorter list up to which closedhouse keeps an edge's common neighbours in LDS.  GM_ERR_INVALID for an unknown name. */
 int gm_constant(const char *name, int64_t *value);
 
 /* Developer / test options (tooling).  The library reads NO algorithm switch from the environment; the named switches that tests and A/B

@@ -103,6 +103,29 @@ def list_windows(sym, size, upto, sentinel=-7):
     return host[:3 * upto].reshape(-1, 3)
 
 
+def gm_constant(name: str) -> int:
+    """a kernel constant of the library by name (a host call, no GPU)"""
+    import ctypes as C
+
+    from graphminer_amd import _lib
+
+    v = C.c_int64(0)
+    _lib.check(_lib.load().gm_constant(name.encode(), C.byref(v)), "gm_constant")
+    return int(v.value)
+
+
+def sup_core_info(sym) -> dict:
+    """the hub corner the support pass of this SYMMETRIC handle leaves to the matrix cores and to the wave-per-edge kernels of the weighted
+    passes (gm_sup_core_info; after a first call that built the task lists): "vertices" (0: no corner) and the DAG "entries" inside it"""
+    import ctypes as C
+
+    from graphminer_amd import _lib
+
+    info = (C.c_int64 * 4)()
+    _lib.check(_lib.load().gm_sup_core_info(sym.handle, info), "gm_sup_core_info")
+    return {"vertices": int(info[0]), "entries": int(info[1])}
+
+
 KCL_ROW_CONSTANTS = {"regs2": "kcl_local_regs2_row", "split": "kcl_local_split_row", "regs8": "kcl_local_regs8_row", "regs12": "kcl_local_regs12_row",
                      "lds": "kcl_local_lds_row"}
 

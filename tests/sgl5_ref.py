@@ -102,6 +102,9 @@ def _c2(x: int) -> int:
     return x * (x - 1) // 2
 
 
+SPARSE_MAX_ROWS = 10**8  # rows of several int64 arrays each: beyond this the enumeration below is killed for memory, not merely slow
+
+
 def raw_sums(g, need=RAW) -> dict:
     """the raw sums named in `need` as exact Python integers modulo 2^64 (the others 0)"""
     rp, ci = np.asarray(g.row_ptr).astype(np.int64), np.asarray(g.col_idx).astype(np.int64)
@@ -119,6 +122,9 @@ def raw_sums(g, need=RAW) -> dict:
         short_is_u = deg[eu] <= deg[ev]
         s_end, l_end = np.where(short_is_u, eu, ev), np.where(short_is_u, ev, eu)
         cnt = deg[s_end]
+        if int(cnt.sum()) > SPARSE_MAX_ROWS:
+            raise ValueError(f"sgl5_ref.raw_sums: {int(cnt.sum())} (edge, key of the shorter list) rows are beyond the sparse enumeration "
+                             f"(limit {SPARSE_MAX_ROWS}); a dense graph of a few thousand vertices goes through dense_graded.dense_raw5")
         eid = np.repeat(np.arange(ne, dtype=np.int64), cnt)
         off = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
         w = ci[np.repeat(rp[s_end], cnt) + off]  # every key of the shorter list

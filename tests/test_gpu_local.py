@@ -2,7 +2,8 @@
 caller's numbering and entry order, against the plain Python forms of tests/truss_ref.py -- entry by entry, vertex by vertex -- and the
 total against TCSolver, through every path of the support pass at the smallest shape that reaches it: as numbered, the hash sets' fallback
 lookup, the 2048-entry stage, rows beyond the stage, a support past 16 bits, the hub corner on the matrix cores, a shuffled numbering.
-Every value is printed before it is asserted."""
+On the stage and beyond it the K_n cells (every support n - 2) stand beside the graded dense cells of tests/dense_graded.py, whose supports
+differ from entry to entry and come from a dense float64 reference.  Every value is printed before it is asserted."""
 import ctypes as C
 import functools
 import json
@@ -12,9 +13,11 @@ from math import comb
 import numpy as np
 import pytest
 
+import dense_graded as DG
+import planted_squares as P
 import truss_ref as TR
 import twin_graphs as T
-from common import GOLDEN, ROOT, load_graph
+from common import GOLDEN, ROOT, gm_constant, load_graph
 from graphminer_amd import SglSolver, TCSolver, _lib, tc_local
 
 pytestmark = pytest.mark.gpu
@@ -111,6 +114,60 @@ def test_complete_graphs_on_the_big_stage_and_beyond(dev, n):
     check(f"K_{n} T_v", np.unique(tv).tolist(), [comb(n - 1, 2)])
     check(f"K_{n} total", total, comb(n, 3))
     assert sup.shape == (g.E(),) and tv.shape == (n,)
+
+
+@pytest.mark.parametrize("name", ["stage", "beyond"])
+def test_graded_cells_entry_by_entry(dev, name):
+    """the graded dense cells of tests/dense_graded.py beside the two K_n above, whose supports are all n - 2: 322 / 173 distinct supports
+    on DAG rows of the 2048-entry stage (graded(1500, 0.90)) and beyond it (graded(2200, 0.975): sup_long_kernel), every entry and every
+    vertex against the dense reference -- on the default copy, as numbered, and with shuffled ids"""
+    g, ref = DG.cell(name), DG.reference(name)
+    f = DG.row_facts(g, gm_constant("tct_stage_max"))
+    print(f"{name} cell: longest DAG row {f['longest']}, rows in (1024, stage] {f['stage']}, beyond {f['beyond']}, distinct supports {f['supports']}", flush=True)
+    assert (f["stage"] >= 64 and f["beyond"] == 0) if name == "stage" else f["beyond"] >= 64
+    total_want = int(ref["tv"].sum()) // 3
+    with g.to_device(dev) as sym:
+        for tune in (None, t6(AS_NUMBERED)):
+            total, tv, sup = tc_local(sym, tune=tune)
+            check_arrays(f"{name} cell tune={tune} supports", sup, ref["sup"])
+            check_arrays(f"{name} cell tune={tune} T_v", tv, ref["tv"])
+            check(f"{name} cell tune={tune} total", total, total_want)
+    h, newid = P.shuffled(g, seed=17)
+    want_tv = np.empty_like(ref["tv"])
+    want_tv[newid] = ref["tv"]
+    with h.to_device(dev) as sym:
+        total, tv, sup = tc_local(sym)
+        check_arrays(f"{name} cell shuffled supports", sup, P.entries_to(g, newid, ref["sup"]))
+        check_arrays(f"{name} cell shuffled T_v", tv, want_tv)
+        check(f"{name} cell shuffled total", total, total_want)
+
+
+def test_graded_stage_cell_rank_shares_and_diamond(dev):
+    """the stage cell: the shares of two and of three ranks of the support pass add up, entry by entry, to the one-rank array (the idiom of
+    tests/test_gpu_supcorner.py), whose multiset is the dense reference's; the diamond count is sum C(t, 2) of the dense supports"""
+    import torch
+
+    from graphminer_amd.solvers import diamond_support_partial, diamond_support_size
+
+    def supports(s, world):
+        n = diamond_support_size(s, world)
+        bufs = [torch.full((n,), 5, dtype=torch.int32, device=f"cuda:{dev}") for _ in range(world)]
+        for r in range(world):
+            diamond_support_partial(s, bufs[r].data_ptr(), n, rank=r, world=world)
+        return torch.stack(bufs).sum(0, dtype=torch.int64)
+
+    g, ref = DG.cell("stage"), DG.reference("stage")
+    t = ref["sup"].astype(np.int64)
+    with g.to_device(dev) as sym:
+        one = supports(sym, 1)
+        for world in (2, 3):
+            diff = int((supports(sym, world)[: one.numel()] != one).sum())
+            print(f"stage cell world {world}: {diff} of {one.numel()} entries differ from the one-rank array", flush=True)
+            assert diff == 0, world
+        got = np.sort(one.cpu().numpy()[: g.E() // 2])  # one entry per undirected edge, in the DAG's order: compared as a multiset
+        src = np.repeat(np.arange(g.V()), np.diff(g.row_ptr))
+        check_arrays("stage cell one-rank supports, sorted", got, np.sort(t[src < g.col_idx]))
+        check("stage cell diamond", SglSolver(sym, "diamond"), int((t * (t - 1) // 2).sum()) // 2)
 
 
 def test_support_beyond_16_bits(dev):

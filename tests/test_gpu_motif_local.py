@@ -3,7 +3,7 @@ every orbit against the numpy composition of tests/motif_local_ref.py (b) -- its
 closed forms in tests/test_motif_local_host.py -- and `counts` against the goldens' motif3 / motif4 and MotifSolver.  Every cell runs on
 the default copy and under GM_T6_AS_NUMBERED.  The cells: the small goldens (citeseer and rmat10 also on the hashed set's global-memory
 lookup); K_1300 and K_2060 with satellites -- the 2048-entry stage of the credit pass (also with both stages in one launch) and its
-wave-per-edge form; rows on both sides of the gather kernels' split and one of 5,200 entries; K_{1,3000} and the book B_70000 past 2^32
+wave-per-edge form; the hub-corner branch of the credit pass (rmat10, the last 512 rows left to the matrix cores); rows on both sides of the gather kernels' split and one of 5,200 entries; K_{1,3000} and the book B_70000 past 2^32
 and 2^16; a triangle-free graph with hubs inside sentinels; k = 3; outputs left out; the other solvers of the handle; the device blocks;
 the refusals.
 The two dense cells are NOT a K_n with 1-2 % of its edges removed: clique_local_ref cannot enumerate the 4-cliques of such a graph in
@@ -23,7 +23,7 @@ import oracle as O
 import planted_squares as P
 import rect_local_ref as RR
 import truss_ref as TR
-from common import GOLDEN, load_graph, random_graph
+from common import GOLDEN, load_graph, random_graph, sup_core_info
 from graphminer_amd import MotifSolver, SglSolver, _lib, clique_local, motif_local, rect_local, tc_local
 
 pytestmark = pytest.mark.gpu
@@ -216,6 +216,22 @@ def test_rows_beyond_the_stage(dev):
     assert row > 2048
     distinct_enough("beyond-stage", want)
     compare("K_2060 + satellites", g, dev, want)
+
+
+def test_hub_corner(dev, devopt):
+    """the branch `corner_from < nv` of the credit pass: the task lists leave the rows of the last 512 vertices out (the set-up of
+    tests/test_gpu_supcorner.py), and the wave-per-edge credit kernel walks their out-edges from the rows themselves -- no row list, the tail
+    of N+(u) beyond v.  gm_sup_core_info proves that the handle has that corner (a fresh handle: the options are read when its tables are built)"""
+    devopt("GM_TOPO_MIN_ROW", "0")
+    devopt("GM_SUP_CORE_H", "512")
+    name = "rmat10_ef16_s42"
+    g, want = case(name)
+    distinct_enough(name, want)
+    with g.to_device(dev) as sym:
+        compare(f"{name} corner 512", g, dev, want, sym=sym)
+        info = sup_core_info(sym)
+        check("corner vertices", info["vertices"], 512)
+        assert info["entries"] > 0
 
 
 def test_gather_rows_on_both_sides_of_the_split(dev):

@@ -2,7 +2,10 @@
 semihouse, 5path) on the GPU: closed forms of eleven raw sums (gm_sgl5_raw / gm_sgl5_finish, csrc/gm_wtri.hip) against
 tests/golden/sgl5.json (the reference's sgl_omp_base) and against the numpy forms of tests/sgl5_ref.py, through every path of the
 support-weighted triangle pass: both LDS stage sizes, rows beyond the 2048-entry stage, the numbering switch, supports past 16 bits,
-closedhouse sets past their LDS capacity.  Every value is printed before it is asserted."""
+closedhouse sets past their LDS capacity.  The K_n cells prove that every triangle is visited once; the graded dense cells beside them
+(tests/dense_graded.py: supports and degrees that differ from entry to entry, a dense float64 reference) prove that every support and degree
+is read at its own entry -- on both stages, beyond the stage, in the hub-corner branch -- and closedhouse sits on both sides of its LDS cap.
+Every value is printed before it is asserted."""
 import functools
 import json
 import os
@@ -11,9 +14,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import dense_graded as DG
+import planted_squares as P
 import sgl5_ref as R5
 import twin_graphs as T
-from common import GOLDEN, ROOT, load_graph
+from common import GOLDEN, ROOT, gm_constant, load_graph, sup_core_info
 from graphminer_amd import SglSolver, _lib
 from graphminer_amd.solvers import sgl5_finish, sgl5_raw
 
@@ -126,6 +131,112 @@ def test_rows_beyond_the_stage(dev):
         check(f"K_{n} {pat}", SglSolver(sym, pat), R5.finish(pat, want))
 
 
+# ---- the graded dense cells (tests/dense_graded.py): the same paths with supports and degrees that differ from entry to entry ---------------
+WEIGHTED = ("T", "D", "W", "A", "B", "H", "S")  # the seven sums of the support pass and the weighted pass
+STAGE_VARIANTS = {"default": (None, None, DG.DENSE5), "as-numbered": (t6(AS_NUMBERED), None, DG.DENSE5), "set-fallback": (t6(HSET_FALLBACK), None, ("A", "B")),
+                  "split-always": (None, "1", WEIGHTED)}
+
+
+@functools.lru_cache(maxsize=None)
+def cell_rows(name):
+    f = DG.row_facts(DG.cell(name), gm_constant("tct_stage_max"))
+    print(f"{name} graded{DG.CELLS[name]}: longest DAG row {f['longest']}, rows in (1024, stage] {f['stage']}, beyond {f['beyond']}", flush=True)
+    return f
+
+
+def check_sums(label, sym, keys, want, tune=None):
+    got = dict(zip(R5.RAW, sgl5_raw(sym, keys, tune=tune)))
+    for k in keys:
+        check(f"{label} raw {k}", got[k], want[k])
+    assert all(got[k] == 0 for k in R5.RAW if k not in keys), label
+
+
+@pytest.mark.parametrize("variant", list(STAGE_VARIANTS))
+def test_graded_stage_cell(dev, devopt, variant):
+    """graded(1500, 0.90): 344 DAG rows of 1025 .. 1263 entries on the 2048-entry stage, 322 distinct supports, 173 distinct degrees --
+    beside K_1300 above, whose sums do not change when a support or a degree is read at a wrong entry.  The sums are asked for by name:
+    the 4-cliques, the rectangles and closedhouse's sets of a graph this dense are not this test's business.  A fresh handle each."""
+    tune, split, keys = STAGE_VARIANTS[variant]
+    f = cell_rows("stage")
+    assert f["stage"] >= 64 and f["beyond"] == 0
+    devopt("GM_TCT_SPLIT_ALWAYS", split)
+    with DG.cell("stage").to_device(dev) as sym:
+        check_sums(f"stage cell {variant}", sym, keys, DG.reference("stage")["raw5"], tune=tune)
+
+
+def test_graded_beyond_cell(dev):
+    """graded(2200, 0.975): 69 DAG rows beyond the 2048-entry stage -- their out-edges are the wave-per-edge kernels' (sup_long_kernel,
+    wtri_edge_kernel with its row list); beside K_2060 above"""
+    f = cell_rows("beyond")
+    assert f["beyond"] >= 64
+    with DG.cell("beyond").to_device(dev) as sym:
+        check_sums("beyond cell", sym, WEIGHTED, DG.reference("beyond")["raw5"])
+
+
+@pytest.mark.parametrize("name,keys", [("stage", DG.DENSE5), ("beyond", WEIGHTED)])
+def test_graded_cells_with_shuffled_ids(dev, name, keys):
+    """the sums do not depend on the numbering; the DAG the pass builds from a shuffled graph breaks its degree ties elsewhere"""
+    h, _ = P.shuffled(DG.cell(name), seed=13)
+    with h.to_device(dev) as sym:
+        check_sums(f"{name} cell shuffled", sym, keys, DG.reference(name)["raw5"])
+
+
+@pytest.mark.parametrize("name,h", [("rmat10_ef16_s42", 512), ("corner", 1024)])
+def test_hub_corner(dev, devopt, name, h):
+    """the branch `corner_from < nv` of the weighted pass: the task lists leave the rows of the last h vertices out, the supports of their
+    edges come from the matrix cores, and wtri_edge_kernel walks their out-edges from the rows themselves (no row list, the tail of N+(u)
+    beyond v).  gm_sup_core_info proves that the handle has that corner.  On the stage cell itself the library declines a corner: it takes
+    whole 512-vertex chunks that start at a word of the core bitmap's rows, so nv - h must be a multiple of 32; the "corner" cell is the
+    stage cell's recipe on 1504 vertices (longest DAG row 1,266: everything on the 2048-entry stage)."""
+    devopt("GM_TOPO_MIN_ROW", "0")
+    devopt("GM_SUP_CORE_H", str(h))
+    if name in DG.CELLS:
+        f = cell_rows(name)
+        assert f["stage"] >= 64 and f["beyond"] == 0
+        g, want = DG.cell(name), DG.reference(name)["raw5"]
+    else:
+        g, want = load_graph(name), numpy_raw(name)
+    with g.to_device(dev) as sym:  # (a fresh handle: the options are read when its tables are built)
+        check_sums(f"{name} corner {h}", sym, WEIGHTED, want)
+        info = sup_core_info(sym)
+        check(f"{name} corner vertices", info["vertices"], h)
+        print(f"{name} corner entries {info['entries']}", flush=True)
+        assert info["entries"] > 0
+        check_sums(f"{name} corner {h} again", sym, ("A", "B"), want)
+
+
+def spine_graph(du, dv, seed):
+    """two adjacent spine vertices 0 and 1 of du <= dv neighbours: du - 1 common pages, dv - du pages of vertex 1 alone, and 3 du seeded
+    random edges among the common pages"""
+    assert 3 <= du <= dv
+    pages = np.arange(2, du + 1, dtype=np.int64)
+    own = np.arange(du + 1, dv + 1, dtype=np.int64)
+    rng = np.random.default_rng(seed)
+    a, b = rng.integers(2, du + 1, 6 * du), rng.integers(2, du + 1, 6 * du)
+    keys = np.unique(np.minimum(a, b)[a != b] * (dv + 1) + np.maximum(a, b)[a != b])
+    keys = keys[rng.permutation(keys.size)[:3 * du]]
+    assert keys.size == 3 * du
+    s = np.concatenate([[0], np.zeros(pages.size, np.int64), np.ones(pages.size + own.size, np.int64), keys // (dv + 1)])
+    return P._graph(dv + 1, s, np.concatenate([[1], pages, pages, own, keys % (dv + 1)]))
+
+
+@pytest.mark.parametrize("du,dv,in_lds", [(-1, -1, True), (0, 0, True), (1, 1, False), (1, 400, False)])
+def test_closedhouse_at_the_lds_cap(dev, du, dv, in_lds):
+    """chouse_kernel keeps S = N(u) ^ N(v) in LDS while min(d(u), d(v)) <= chouse_lds_keys and in the global scratch beyond: spine edges
+    with cap - 1, cap, cap + 1 keys on both sides, and one of cap + 1 and cap + 400 -- the shorter list decides.  The pages' own edges put
+    hundreds of keys inside S"""
+    cap = gm_constant("chouse_lds_keys")
+    du, dv = cap + du, cap + dv
+    g = spine_graph(du, dv, seed=du)
+    deg = np.diff(g.row_ptr)
+    want = R5.raw_sums(g, need=("Q",))["Q"]
+    print(f"spine degrees {int(deg[0])}, {int(deg[1])} against the cap {cap}; largest page degree {int(deg[2:].max())}", flush=True)
+    assert (int(deg[0]), int(deg[1])) == (du, dv) and int(deg[2:].max()) < cap - 1
+    assert (min(int(deg[0]), int(deg[1])) <= cap) is in_lds and want > 0
+    with g.to_device(dev) as sym:
+        check(f"closedhouse spine {du}, {dv}", SglSolver(sym, "closedhouse"), want)
+
+
 def test_closedhouse_beyond_lds_capacity(dev):
     """B_1500 with a path among four pages: the spine edge's common neighbours (1500 > the 1024-key LDS set) go to the global scratch"""
     from graphminer_amd.rmat import csr_from_pairs
@@ -163,6 +274,11 @@ def test_refusals(dev, capsys):
     assert lib.gm_sgl(sym.handle, b"hourglass", C.byref(la), C.byref(total), None) == _lib.GM_ERR_UNSUPPORTED and total.value == 0
     assert lib.gm_sgl5_raw(sym.handle, b"all", C.byref(la), raw, None) == _lib.GM_ERR_UNSUPPORTED
     assert lib.gm_sgl5_raw(sym.handle, b"diamond", None, raw, None) == _lib.GM_ERR_INVALID
+    assert lib.gm_sgl5_raw_need(sym.handle, 0b11000, C.byref(la), raw, None) == _lib.GM_ERR_UNSUPPORTED  # the same by bit mask
+    assert lib.gm_sgl5_raw_need(sym.handle, 0, None, raw, None) == _lib.GM_ERR_INVALID
+    assert lib.gm_sgl5_raw_need(sym.handle, 1 << 11, None, raw, None) == _lib.GM_ERR_INVALID
+    assert lib.gm_sgl5_raw_need(None, 1, None, raw, None) == _lib.GM_ERR_INVALID
+    assert sgl5_raw(sym, ("A", "B", "P")) == [v if k in "ABP" else 0 for k, v in numpy_raw("citeseer").items()]
     for pat in (b"6path", b"dumbbell"):
         total = C.c_uint64(5)
         assert lib.gm_sgl(sym.handle, pat, None, C.byref(total), None) == _lib.GM_ERR_UNSUPPORTED and total.value == 0

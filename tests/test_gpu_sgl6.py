@@ -1,7 +1,8 @@
 """6path and dumbbell on the GPU (gm_sgl6_need / gm_sgl6_raw / gm_sgl6_finish / gm_sgl6, csrc/gm_wrect.hip) against tests/golden/sgl6.json (the
 reference's sgl_omp_base) and against the numpy forms of tests/sgl6_ref.py: the nine raw sums one by one, the degree-weighted 4-cycle kernel
-across several LDS ranges and on the graph as numbered, counters past 16 and 32 bits, rows beyond the workgroup's threads, the neighbours'
-arrays, the refusals and the app.  Every value is printed before it is asserted."""
+across several LDS ranges and on the graph as numbered, counters past 16 and 32 bits, rows beyond the workgroup's threads (K_n, and the
+graded dense stage cell of tests/dense_graded.py with unequal degrees and supports), the hub corner, the neighbours' arrays, the refusals
+and the app.  Every value is printed before it is asserted."""
 import ctypes as C
 import functools
 import json
@@ -10,9 +11,10 @@ import subprocess
 
 import pytest
 
+import dense_graded as DG
 import sgl6_ref as R6
 import twin_graphs as T
-from common import GOLDEN, ROOT, load_graph
+from common import GOLDEN, ROOT, load_graph, sup_core_info
 from graphminer_amd import SglSolver, _lib
 from graphminer_amd.solvers import sgl6, sgl6_finish, sgl6_need, sgl6_raw, tc_local
 
@@ -135,6 +137,40 @@ def test_long_rows(dev, devopt):
     got = named(sgl6_raw(g.to_device(dev), ("Z", "R")))
     for k in ("Z", "R"):
         check(f"K_{n} 16 ids per range raw {k}", got[k], want[k])
+
+
+def test_graded_stage_cell(dev, devopt):
+    """graded(1500, 0.90) of tests/dense_graded.py beside K_1100 above, where every degree and support is the same: rows beyond 1024 entries
+    with 173 distinct degrees and 322 distinct supports -- the degree-weighted Z and the per-entry X, M, Y against the dense reference, on
+    the default copy and as numbered; Z, R again with 16 ids per LDS range (94 ranges share the 64 bits of a row's mask)"""
+    keys = ("Z", "R", "M", "X", "Y")
+    g, want = DG.cell("stage"), DG.reference("stage")["raw6"]
+    with g.to_device(dev) as sym:
+        for tune in (None, t6(AS_NUMBERED)):
+            got = named(sgl6_raw(sym, keys, tune=tune))
+            for k in R6.RAW:
+                check(f"stage cell tune {tune} raw {k}", got[k], want[k] if k in keys else 0)
+    devopt("GM_WRECT_RANGE", "16")
+    with g.to_device(dev) as sym:  # (a fresh handle: the option is read when the plan is built)
+        got = named(sgl6_raw(sym, ("Z", "R")))
+        for k in ("Z", "R"):
+            check(f"stage cell 16 ids per range raw {k}", got[k], want[k])
+
+
+def test_hub_corner(dev, devopt):
+    """X, M, Y read the supports, 2 T_v and the degrees the 5-vertex pass leaves on the DAG: here on a handle whose task lists leave the
+    rows of the last 512 vertices to the matrix cores (the set-up of tests/test_gpu_supcorner.py; gm_sup_core_info proves the corner)"""
+    devopt("GM_TOPO_MIN_ROW", "0")
+    devopt("GM_SUP_CORE_H", "512")
+    name = "rmat10_ef16_s42"
+    want = numpy_raw(name)
+    with load_graph(name).to_device(dev) as sym:
+        got = named(sgl6_raw(sym, ("M", "X", "Y")))
+        info = sup_core_info(sym)
+        check("corner vertices", info["vertices"], 512)
+        assert info["entries"] > 0
+        for k in ("M", "X", "Y"):
+            check(f"{name} corner raw {k}", got[k], want[k])
 
 
 def test_neighbours_unharmed(dev):

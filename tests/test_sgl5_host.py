@@ -26,7 +26,9 @@ def numpy_raw(name):
 
 def test_exports_and_order():
     lib = _lib.load()
-    assert lib.gm_sgl5_raw and lib.gm_sgl5_finish
+    assert lib.gm_sgl5_raw and lib.gm_sgl5_finish and lib.gm_sgl5_raw_need
+    raw = (C.c_uint64 * len(R5.RAW))()
+    assert lib.gm_sgl5_raw_need(None, 1, None, raw, None) == _lib.GM_ERR_INVALID  # (the refusals with a handle: tests/test_gpu_sgl5.py)
     assert tuple(SGL5_RAW) == R5.RAW and set(SGL5_PATTERNS) == set(R5.PATTERNS)
 
 
