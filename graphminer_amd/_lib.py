@@ -63,6 +63,13 @@ class gm_setup_times(C.Structure):
 GM_OK, GM_ERR_INVALID, GM_ERR_NO_DEVICE, GM_ERR_HIP, GM_ERR_TOO_LARGE, GM_ERR_UNSUPPORTED, GM_ERR_IO, GM_ERR_FORMAT = range(8)
 GM_PART_ROUND_ROBIN, GM_PART_RANGE, GM_PART_VERTEX = 0, 1, 2
 GM_TRUSS_REMOVED = 0xFFFFFFFF
+GM_CORE_REMOVED = 0xFFFFFFFFFFFFFFFF
+
+
+class gm_core_dense(C.Structure):
+    _fields_ = [("round", C.c_int32), ("vertices", C.c_uint64), ("cliques", C.c_uint64)]
+
+
 (GM_OP_INTERSECT_NUM, GM_OP_INTERSECT_NUM_UPPER, GM_OP_INTERSECT_SET, GM_OP_DIFFERENCE_NUM,
  GM_OP_DIFFERENCE_NUM_UPPER, GM_OP_DIFFERENCE_SET, GM_OP_INTERSECT_SET_UPPER, GM_OP_DIFFERENCE_SET_UPPER, GM_OP_COUNT_SMALLER) = range(9)
 
@@ -112,6 +119,10 @@ SYMBOLS = [
                              C.POINTER(gm_stats)]),
     ("gm_clique_list", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), C.c_uint64, C.c_uint64, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                  C.POINTER(gm_stats)]),
+    ("gm_clique_kcore", C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(gm_launch), _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                  C.POINTER(gm_stats)]),
+    ("gm_clique_core_decompose", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                           C.POINTER(gm_core_dense), C.POINTER(gm_stats)]),
     ("gm_motif_formula", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.c_int, C.POINTER(gm_stats)]),
     ("gm_setop_batch", C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("gm_rmat_keys", C.c_int, [C.c_int, C.c_int64, C.c_uint64, _P, _P]),

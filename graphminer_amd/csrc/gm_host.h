@@ -6,7 +6,7 @@
 //   gm_launch.hip  the launch layer (interface: gm_launch.h, for the three solver units only): launch prologue / epilogue, run_pattern,
 //                  gm_kernel_times, gm_tc / gm_clique / gm_motif, and every kernel of the layer
 //   gm_solve_sgl.hip    the SgL family: gm_sgl, the rectangle / house / pentagon map solvers, gm_diamond_support_*, gm_sgl4 / 5 / 6   (host code only)
-//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_clique_list, gm_rect_local                                   (host code only)
+//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_clique_list, gm_rect_local, gm_clique_kcore, gm_clique_core_decompose                                 (host code only)
 //   gm_tools.hip   set-op batch, R-MAT generator, PMC / issue-rate calibration kernels, self test
 // Host-side counterparts in the reference:
 //   GraphGPU::init / init_edgelist          include/graph_gpu.h:69-194
@@ -583,6 +583,16 @@ struct gm_graph {
     // handle five vertex arrays of the call's own -- T_v, R_v, K_v, half the row sums of the credits, e1 -- and eight column sums
     DevOwn<unsigned long long> wacc;
     DevOwn<unsigned long long> orb;
+    // k-clique cores (gm_kcl_core.hip), on the SYMMETRIC handle: K_v while peeling, the marks and the frontier list of the vertices (the
+    // k-truss keeps its own, per entry), the 64 bytes of round words, the list of the frontier vertices of more than kKclLocalLdsRow
+    // survivors and the wide kernel's scratch slots.  Core numbers and rounds go straight to the caller's arrays
+    DevOwn<unsigned long long> core_cnt;
+    DevOwn<unsigned char> core_mark;
+    DevOwn<int> core_front;            // nv vertices
+    DevOwn<unsigned long long> core_words;
+    DevOwn<int> core_heavy;            // ne / (kKclLocalLdsRow + 1) + 1 vertices
+    DevOwn<unsigned> core_scratch;
+    size_t core_scratch_bytes = 0;
   } local;
   struct MapWork {  // the global counter maps of run_rect_acc / run_house_acc (rectangle, pentagon, house by wedge accumulation)
     DevOwn<unsigned> rect_acc;
@@ -740,6 +750,7 @@ void gm_touch_orbit_local();
 void gm_touch_local();
 void gm_touch_list();
 void gm_touch_kcl_local();
+void gm_touch_kcl_core();
 void gm_touch_clique_list();
 void gm_touch_cbuild();
 void gm_touch_cmma();

@@ -797,6 +797,36 @@ struct KclLocalParams {
   unsigned long long scratch_words;
   unsigned long long *err;          // += 1 for what cannot happen (an adjacent pair without an entry, a row beyond max_deg)
 };
+// k-clique cores (gm_kcl_core.hip): the rounds that peel the per-vertex counts on the caller's SYMMETRIC graph.  A frontier vertex takes its
+// path by the number of its SURVIVING neighbours, with the boundaries of the local counts: up to kKclLocalRegs2Row a wave, up to
+// kKclLocalLdsRow a workgroup (the matrix in LDS), beyond them the wide kernel out of a scratch slot of kcl_local_scratch_words(max_deg) words.
+enum CoreWord : int { CW_ERR = 0, CW_DESTROYED = 1, CW_FRONT = 2, CW_LEAST = 3, CW_ALIVE = 6, CW_SUM = 7 };  // 64-bit words of KclCoreParams::words
+enum CoreQueue : int { CQ_MAIN = 0, CQ_HEAVY = 1, CQ_WIDE = 2 };                                           // 32-bit words behind the first four
+struct KclCoreParams {
+  int nv, k, max_deg;               // max_deg: the longest row (sizes the scratch slot)
+  const int *rp, *col;              // the caller's symmetric CSR
+  unsigned long long *cnt;          // per vertex: K_v among the vertices not removed (not maintained once v is in the frontier)
+  unsigned char *mark;              // LocalMark of the vertex
+  int *front;                       // this round's frontier (nv ints)
+  unsigned long long *core;         // nullptr, or per vertex: `level` is written when the vertex enters the frontier
+  unsigned *round;                  // nullptr, or per vertex: `round_no` is written then
+  unsigned long long thr, level;    // an alive vertex of count < thr enters the frontier
+  unsigned round_no;
+  // 64 bytes.  [CW_ERR] += 1 for what cannot happen; [CW_DESTROYED] += the cliques a round destroys; [CW_FRONT] the frontier's size and
+  // [CW_LEAST] ~0 - the smallest count that stays alive (0: none), zeroed per round with the three queue words (the peel's dequeue head, the
+  // heavy list's length, the wide kernel's dequeue head); [CW_ALIVE], [CW_SUM]: core_out_kernel's survivors and the sum of their counts
+  unsigned long long *words;
+  int *heavy;                       // the frontier vertices of more than kKclLocalLdsRow survivors, in order of arrival
+  unsigned heavy_cap;
+  unsigned *scratch;                // wide: gridDim.x slots of scratch_words words
+  unsigned long long scratch_words;
+};
+hipError_t launch_core_init(const KclCoreParams &p, int cu_count, hipStream_t stream);  // marks alive, k = 2: the row lengths; [CW_LEAST] of all
+hipError_t launch_core_mark(const KclCoreParams &p, int cu_count, hipStream_t stream);
+hipError_t launch_core_peel(const KclCoreParams &p, unsigned n_front, int cu_count, hipStream_t stream);
+hipError_t launch_core_peel_wide(const KclCoreParams &p, int grid_blocks, hipStream_t stream);
+// out[v] (may be nullptr): K_v inside the core or GM_CORE_REMOVED; [CW_ALIVE] += the survivors, [CW_SUM] += their counts
+hipError_t launch_core_out(const KclCoreParams &p, unsigned long long *out, int cu_count, hipStream_t stream);
 unsigned long long kcl_local_scratch_words(int max_deg);
 hipError_t launch_kcl_local(const KclLocalParams &p, int stage, int grid_blocks, hipStream_t stream);  // stage: KclStage
 hipError_t launch_local_rev(int nv, long long ne, const int *rp, const int *col, int *rev, int cu_count, hipStream_t stream);

@@ -1,6 +1,7 @@
 // gm_solve_local.hip -- local counts, the k-truss, the triangle and k-clique listings, the local k-clique and 4-cycle counts over the launch layer (gm_launch.h):
-// gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_list, gm_clique_local, gm_rect_local, gm_motif_local.  Host code only: the kernels are
-// gm_local.hip's, gm_list.hip's, gm_clique_list.hip's, gm_kcl_local.hip's, gm_rect_local.hip's and gm_orbit_local.hip's, so this unit has no code object and no warm-up.
+// gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_list, gm_clique_local, gm_rect_local, gm_motif_local, gm_clique_kcore,
+// gm_clique_core_decompose.  Host code only: the kernels are
+// gm_local.hip's, gm_list.hip's, gm_clique_list.hip's, gm_kcl_local.hip's, gm_kcl_core.hip's, gm_rect_local.hip's and gm_orbit_local.hip's, so this unit has no code object and no warm-up.
 #include "gm_launch.h"
 #include "gm_orbit.h"
 
@@ -434,6 +435,134 @@ extern "C" int gm_truss_decompose(const gm_graph *sym, const gm_launch *la, uint
   if (!sym || !d_entry_truss) return GM_ERR_INVALID;
   if (int rc = local_refusals(sym, la)) return rc;
   return run_truss(sym, true, 0, la, d_entry_truss, nullptr, k_max, rounds, st);
+}
+
+// ---- k-clique cores (gm_kcl_core.hip; DESIGN.md "k-clique cores") ------------------------------------------------------------------------
+// gm_clique_kcore (decompose = false) and gm_clique_core_decompose: K_v from gm_clique_local on the same handle (k = 2: the row lengths),
+// then whole-frontier rounds as run_truss runs them.  24 bytes come back per round: the cliques destroyed so far, the frontier's size and
+// the smallest count that stays alive; the densities of the states are compared here.
+static int run_clique_core(const gm_graph *sym, bool decompose, int k, uint64_t c_in, const gm_launch *la, uint64_t *d_cnt_out, uint64_t *d_core,
+                           uint32_t *d_round, uint64_t *n_vertices, uint64_t *n_cliques, uint64_t *c_max, int32_t *rounds_out, gm_core_dense *dense,
+                           gm_stats *st) {
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  if (n_vertices) *n_vertices = 0;
+  if (n_cliques) *n_cliques = 0;
+  if (c_max) *c_max = 0;
+  if (rounds_out) *rounds_out = 0;
+  if (dense) *dense = gm_core_dense{1, 0, 0};
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  uint64_t unused = 0;
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, &unused, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+  const size_t nvz = (size_t)std::max(g->nv, 1);
+  const bool wide = k >= 3 && g->max_deg > kKclLocalLdsRow;  // (a frontier vertex of more than kKclLocalLdsRow survivors needs a row that long)
+  const unsigned long long slot_words = kcl_local_scratch_words(g->max_deg);
+  const size_t slot_bytes = sizeof(unsigned) * (size_t)slot_words;
+  const int grid_wide = wide ? clamp_grid((long long)(kKclScratchBudget / slot_bytes), (long long)g->cu_count * 2) : 0;
+  const size_t heavy_cap = (size_t)(g->ne / (kKclLocalLdsRow + 1)) + 1;
+  {
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (!g->local.core_cnt) HIP_TRY(g->local.core_cnt.alloc(sizeof(unsigned long long) * nvz));
+    if (!g->local.core_mark) HIP_TRY(g->local.core_mark.alloc(nvz));
+    if (!g->local.core_front) HIP_TRY(g->local.core_front.alloc(sizeof(int) * nvz));
+    if (!g->local.core_words) HIP_TRY(g->local.core_words.alloc(64));
+    if (k >= 3 && !g->local.core_heavy) HIP_TRY(g->local.core_heavy.alloc(sizeof(int) * heavy_cap));
+    if (wide)  // (a slot that does not fit the device: the allocation fails and the call is refused)
+      if (int rc = grow_dev(g->local.core_scratch, &g->local.core_scratch_bytes, slot_bytes * (size_t)grid_wide)) return rc;
+  }
+  SubLaunches sub;
+  uint64_t total = (uint64_t)(sym->ne / 2);  // (k = 2: a clique is an edge)
+  if (k >= 3)
+    if (int rc = sub.run([&](gm_stats *s) { return gm_clique_local(sym, k, &l2, (uint64_t *)g->local.core_cnt.get(), nullptr, &total, s); })) return rc;
+  if (int rc = start_timer(ctx)) return rc;
+  hipStream_t stream = ctx.stream;
+  KclCoreParams pp;
+  memset(&pp, 0, sizeof pp);
+  pp.nv = g->nv; pp.k = k; pp.max_deg = std::max(g->max_deg, 1); pp.rp = g->d_rp; pp.col = g->d_col;
+  pp.cnt = g->local.core_cnt; pp.mark = g->local.core_mark; pp.front = g->local.core_front; pp.words = g->local.core_words;
+  pp.core = decompose ? (unsigned long long *)d_core : nullptr;
+  pp.round = decompose ? (unsigned *)d_round : nullptr;
+  pp.heavy = g->local.core_heavy; pp.heavy_cap = (unsigned)heavy_cap;
+  pp.scratch = g->local.core_scratch; pp.scratch_words = slot_words;
+  unsigned long long h[3] = {0ull, 0ull, 0ull};  // [0] destroyed so far, [1] the frontier's size, [2] ~0 - the smallest count that stays (0: none)
+  HIP_TRY(hipMemsetAsync(pp.words, 0, 64, stream));
+  HIP_TRY(launch_core_init(pp, g->cu_count, stream));
+  unsigned long long level = 0, cmax = 0;
+  if (decompose) {  // the level the first round runs at: the smallest count of the graph
+    HIP_TRY(hipMemcpyAsync(&h[2], pp.words + CW_LEAST, sizeof h[2], hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    level = h[2] ? ~0ull - h[2] : 0ull;
+  }
+  int rounds = 0;
+  uint64_t removed = 0;
+  gm_core_dense best{1, 0, 0};
+  for (;;) {
+    pp.thr = decompose ? level + 1 : (unsigned long long)c_in;
+    pp.level = level;
+    pp.round_no = (unsigned)(rounds + 1);
+    HIP_TRY(hipMemsetAsync(pp.words + CW_FRONT, 0, 32, stream));  // (the frontier's size, the smallest count, the three queue words)
+    HIP_TRY(launch_core_mark(pp, g->cu_count, stream));
+    HIP_TRY(hipMemcpyAsync(h, pp.words + CW_DESTROYED, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    ++rounds;
+    if (h[0] > total || h[1] > (uint64_t)g->nv - removed) {
+      g_last_error = "gm_clique_core: a round's counters left their range (internal error)";
+      return GM_ERR_INVALID;
+    }
+    const uint64_t vertices = (uint64_t)g->nv - removed, cliques = total - h[0];  // the state at the start of this round
+    if (vertices > 0 && (best.vertices == 0 || (unsigned __int128)cliques * best.vertices > (unsigned __int128)best.cliques * vertices))
+      best = gm_core_dense{(int32_t)rounds, vertices, cliques};
+    if (h[1] == 0ull) {
+      if (!decompose || h[2] == 0ull) break;  // (decompose: nothing is alive any more)
+      level = ~0ull - h[2];                   // every alive vertex has a count >= this: the first level that removes one
+      continue;
+    }
+    removed += h[1];
+    cmax = level;
+    HIP_TRY(launch_core_peel(pp, (unsigned)h[1], g->cu_count, stream));
+    if (wide) HIP_TRY(launch_core_peel_wide(pp, grid_wide, stream));
+  }
+  HIP_TRY(launch_core_out(pp, decompose ? nullptr : (unsigned long long *)d_cnt_out, g->cu_count, stream));
+  unsigned long long w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(w, pp.words, sizeof w, hipMemcpyDeviceToHost, stream));
+  if (int rc = sub.run([&](gm_stats *s) { return end_launch(ctx, FIN_COPY, 0, &unused, 1, s); })) return rc;  // (synchronises the stream)
+  const uint64_t left = total - w[CW_DESTROYED];
+  if (w[CW_ERR] != 0 || w[CW_DESTROYED] > total || w[CW_SUM] != left * (uint64_t)k || w[CW_ALIVE] != (uint64_t)g->nv - removed) {
+    g_last_error = "gm_clique_core: " + std::to_string(w[CW_ERR]) + " kernel errors, " + std::to_string(left) + " cliques left against the counts' sum " +
+                   std::to_string(w[CW_SUM]) + " / k (internal error)";
+    return GM_ERR_INVALID;
+  }
+  if (n_vertices) *n_vertices = w[CW_ALIVE];
+  if (n_cliques) *n_cliques = left;
+  if (c_max) *c_max = cmax;
+  if (rounds_out) *rounds_out = rounds;
+  if (dense) *dense = best;
+  if (st) st->kernel_ms = sub.ms;
+  return GM_OK;
+}
+
+static int clique_core_refusals(const gm_graph *sym, int k, const gm_launch *la, const char *who) {
+  if (!sym || k < 2 || k > GM_MAX_CLIQUE_K) return GM_ERR_INVALID;
+  if (int rc = local_refusals(sym, la)) return rc;
+  if (k > 8) {
+    g_last_error = std::string(who) + ": k = 9 .. " + std::to_string(GM_MAX_CLIQUE_K) + " is not supported yet (2 <= k <= 8)";
+    return GM_ERR_UNSUPPORTED;
+  }
+  return GM_OK;
+}
+
+extern "C" int gm_clique_kcore(const gm_graph *sym, int k, uint64_t c, const gm_launch *la, uint64_t *d_vertex_cnt, uint64_t *n_vertices,
+                               uint64_t *n_cliques, int32_t *rounds, gm_stats *st) {
+  if (int rc = clique_core_refusals(sym, k, la, "gm_clique_kcore")) return rc;
+  return run_clique_core(sym, false, k, c, la, d_vertex_cnt, nullptr, nullptr, n_vertices, n_cliques, nullptr, rounds, nullptr, st);
+}
+
+extern "C" int gm_clique_core_decompose(const gm_graph *sym, int k, const gm_launch *la, uint64_t *d_vertex_core, uint32_t *d_vertex_round,
+                                        uint64_t *c_max, int32_t *rounds, gm_core_dense *dense, gm_stats *st) {
+  if (!d_vertex_core) return GM_ERR_INVALID;
+  if (int rc = clique_core_refusals(sym, k, la, "gm_clique_core_decompose")) return rc;
+  return run_clique_core(sym, true, k, 0, la, nullptr, d_vertex_core, d_vertex_round, nullptr, nullptr, c_max, rounds, dense, st);
 }
 
 // ---- triangle listing (gm_list.hip; DESIGN.md "Triangle listing") -----------------------------------------------------------------------

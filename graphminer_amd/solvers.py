@@ -334,6 +334,37 @@ def clique_local(g: DeviceGraph, k: int, *, vertex=True, entries=True, chunk=0, 
     return (*res, _stats(st)) if return_stats else res
 
 
+# ---- k-clique cores (include/graphminer_amd.h: gm_clique_kcore / gm_clique_core_decompose) -----------------------------------------------
+CORE_REMOVED = _lib.GM_CORE_REMOVED
+
+
+def clique_kcore(g: DeviceGraph, k: int, c: int, *, chunk=0, return_stats=False, **kw):
+    """(vertices of the (k, c)-core, its k-cliques, per vertex K_v inside the core or CORE_REMOVED as np.uint64[nv], peeling rounds) of a
+    SYMMETRIC graph: the largest vertex set in which every vertex lies in >= c k-cliques OF THAT SET.  2 <= k <= 8.  One GPU."""
+    import torch
+
+    la, st, nvert, ncl, rounds = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+    cnt = _dev_array(g, g.nv, torch.int64)
+    _lib.check(_lib.load().gm_clique_kcore(g.handle, int(k), int(c), C.byref(la), cnt.data_ptr(), C.byref(nvert), C.byref(ncl), C.byref(rounds),
+                                           C.byref(st)), "gm_clique_kcore")
+    res = (int(nvert.value), int(ncl.value), _to_numpy(cnt, g.nv, "uint64"), int(rounds.value))
+    return (*res, _stats(st)) if return_stats else res
+
+
+def clique_core_decompose(g: DeviceGraph, k: int, *, chunk=0, return_stats=False, **kw):
+    """(k-clique core number of every vertex as np.uint64[nv], the 1-based round whose frontier held it as np.uint32[nv], the largest core
+    number, peeling rounds, (round, vertices, cliques) of the densest of the rounds' states) of a SYMMETRIC graph.  2 <= k <= 8.  One GPU."""
+    import torch
+
+    la, st, cmax, rounds, dense = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0), C.c_int32(0), _lib.gm_core_dense()
+    core, rnd = _dev_array(g, g.nv, torch.int64), _dev_array(g, g.nv, torch.int32)
+    _lib.check(_lib.load().gm_clique_core_decompose(g.handle, int(k), C.byref(la), core.data_ptr(), rnd.data_ptr(), C.byref(cmax), C.byref(rounds),
+                                                    C.byref(dense), C.byref(st)), "gm_clique_core_decompose")
+    res = (_to_numpy(core, g.nv, "uint64"), _to_numpy(rnd, g.nv, "uint32"), int(cmax.value), int(rounds.value),
+           (int(dense.round), int(dense.vertices), int(dense.cliques)))
+    return (*res, _stats(st)) if return_stats else res
+
+
 # ---- local 4-cycle counts (include/graphminer_amd.h: gm_rect_local) -----------------------------------------------------------------------
 def rect_local(g: DeviceGraph, *, vertex=True, entries=True, chunk=0, return_stats=False, **kw):
     """(total, R_v as np.uint64[nv] or None, R_uv per entry as np.uint64[ne] or None) of a SYMMETRIC graph, in the caller's numbering and

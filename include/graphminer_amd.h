@@ -443,6 +443,50 @@ int gm_clique_local(const gm_graph *sym, int k, const gm_launch *launch, uint64_
 int gm_clique_list(const gm_graph *sym, int k, const gm_launch *launch, uint64_t first, uint64_t cap, int32_t *d_cliques, uint64_t *total,
                    uint64_t *n_written, gm_stats *stats);
 
+/* ---- k-clique cores (csrc/gm_kcl_core.hip; DESIGN.md "k-clique cores") ------------------------------------------------------------------
+ * The first consumer of the local k-clique counts: the (1,k)-nuclei.  SYMMETRIC graph with ascending rows and no self loops, 2 <= k <= 8.
+ * K_v(H) = the k-cliques of the vertex-induced subgraph H that contain v (k = 2: the degree).
+ *   The (k, c)-core is the largest vertex set H with K_v(H) >= c for every v of H (k = 2: the ordinary c-core).
+ *   The core number kappa_k(v) is the largest c whose (k, c)-core holds v; it does not depend on the peeling order.
+ *   The densest prefix: the rounds of the decomposition define nested vertex sets; the one with the most k-cliques per vertex is returned.
+ *   The c_max-core is one of them and holds at least 1/k of the optimum k-clique density (Tsourakakis 2015): a 1/k-approximation of the
+ *   k-clique densest subgraph.
+ * Rounds, the k-truss's scheme with vertices in place of edges: a round's frontier is every alive vertex whose count is below the
+ * threshold; the host reads back 24 bytes -- the frontier's size, the smallest count that stays alive, the cliques destroyed so far --,
+ * the peel kernel runs, and the frontier becomes removed when the next round marks.  The round that finds an empty frontier ends the level
+ * and is counted.  Decomposition: the level starts at the smallest count of the graph, the threshold is level + 1, a vertex that enters
+ * the frontier gets kappa = level and round = the 1-based index of that round, from an empty frontier the level goes to the smallest alive
+ * count; the call ends with the empty frontier that leaves nothing alive.
+ * The rule of the decrements: a k-clique counts only if none of its members was removed before the round began.  Such a clique with at
+ * least one frontier member is destroyed in this round: accounted once, by its frontier member of the smallest id, and every member
+ * outside the frontier loses one (the counts of frontier members are not maintained).  So frontier vertex v works on S_v = the members of
+ * N(v) that are not removed, without the frontier vertices of an id below v: it subtracts the (k-1)-cliques of G[S_v] that hold w from
+ * every w of S_v outside the frontier, and adds their sum / (k - 1) to the destroyed total: one 64-bit atomic per member of S_v and one per
+ * frontier vertex, nothing per clique.  The path follows |S_v|: up to 64 survivors a wave, up to 512 a workgroup with the matrix in LDS,
+ * beyond that a scratch slot per workgroup (sized by the longest row; a slot that does not fit the device refuses the call).
+ *
+ * gm_clique_kcore: n_vertices / n_cliques (may be NULL) = the vertices and the k-cliques of the (k, c)-core (the graph's total minus the
+ *   destroyed; the call checks it against sum K_v / k over the core), rounds (may be NULL) = the rounds run (>= 1).  c = 0 removes nothing.
+ * gm_clique_core_decompose: c_max = max kappa, rounds over all levels; dense (may be NULL): the state at the start of round r is the set
+ *   {v : round[v] >= r} -- round 1 is the whole graph --; of the states with a vertex the one with the largest cliques / vertices (exact:
+ *   cross products in 128 bits; a tie goes to the earliest round) as (round, vertices, cliques).  Isolated vertices: kappa 0, round 1.
+ * The contract of gm_clique_local: one GPU, synchronous; a null handle -> GM_ERR_INVALID, k < 2 or k > GM_MAX_CLIQUE_K -> GM_ERR_INVALID,
+ * 9 <= k <= GM_MAX_CLIQUE_K -> GM_ERR_UNSUPPORTED, >= 2^31 entries -> GM_ERR_TOO_LARGE, world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED,
+ * unsorted rows -> GM_ERR_INVALID; ne == 0 -> GM_OK, every vertex kappa 0 and round 1, the arrays written when given; launch->stream is
+ * honoured; launch->tune[6] & GM_T6_AS_NUMBERED is passed on to the initial count (gm_clique_local on the same handle; k = 2: the row
+ * lengths) and to nothing else; stats->kernel_ms covers every kernel and the per-round read-backs, stats->tasks = the directed entries;
+ * before or after any other solver on the handle, whose arrays it leaves alone; state is initialised per call; ONE such call at a time per
+ * handle; everything it keeps on the handle is freed with the handle. */
+#define GM_CORE_REMOVED 0xFFFFFFFFFFFFFFFFull
+typedef struct gm_core_dense { int32_t round; uint64_t vertices, cliques; } gm_core_dense;
+int gm_clique_kcore(const gm_graph *sym, int k, uint64_t c, const gm_launch *launch,
+                    uint64_t *d_vertex_cnt,     /* DEVICE uint64[nv] or NULL: K_v inside the (k,c)-core, GM_CORE_REMOVED outside it */
+                    uint64_t *n_vertices, uint64_t *n_cliques, int32_t *rounds, gm_stats *stats);
+int gm_clique_core_decompose(const gm_graph *sym, int k, const gm_launch *launch,
+                    uint64_t *d_vertex_core,    /* DEVICE uint64[nv], NULL -> GM_ERR_INVALID: kappa_k(v) */
+                    uint32_t *d_vertex_round,   /* DEVICE uint32[nv] or NULL: the round whose frontier held v (>= 1) */
+                    uint64_t *c_max, int32_t *rounds, gm_core_dense *dense /* may be NULL */, gm_stats *stats);
+
 /* ---- local 4-cycle counts (csrc/gm_rect_local.hip; DESIGN.md "Local 4-cycle counts") --------------------------------------------------
  * The 4-cycles (edge-induced, as the `rectangle` of gm_sgl counts them: src/sgl/cpu_kernels/rectangle.h) at every vertex and on every
  * edge, in the CALLER's numbering and entry order: the input of square clustering coefficients, of butterfly supports on bipartite data,
