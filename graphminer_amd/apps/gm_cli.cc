@@ -1,9 +1,9 @@
 // gm_cli.cc -- one source for the whole command-line surface of the HIP solvers.
 //
-// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL|RECTLOCAL|MOTIFLOCAL|CLIQUELIST|CLIQUECORE> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
+// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL|RECTLOCAL|MOTIFLOCAL|CLIQUELIST|CLIQUECORE|CLIQUETRUSS> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
 //   tc_gpu_base tc_multigpu tc_multigpu_base | sgl_gpu_base sgl_multigpu | clique_gpu_base clique_multigpu kcl_gpu_base |
 //   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base | cliquelocal_gpu_base | rectlocal_gpu_base | motiflocal_gpu_base |
-//   cliquelist_gpu_base | cliquecore_gpu_base
+//   cliquelist_gpu_base | cliquecore_gpu_base | cliquetruss_gpu_base
 // The observable behaviour -- positional argv, defaults, usage text, banner and FINAL result lines -- is that of the
 // reference mains (src/triangle/main.cc:7-27, src/sgl/main.cc:9-35, src/clique/main.cc:8-28, src/motif/main.cc:9-31,
 // Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.  truss_gpu_base <graph prefix> [k] has no
@@ -27,6 +27,10 @@
 // (gm_clique_kcore): `core_vertices = N`, `core_cliques = M`, `rounds = R`.  Without it the decomposition (gm_clique_core_decompose):
 // `rounds = R`, `dense_round = r`, `dense_vertices = N`, `dense_cliques = M`, `dense_density = M / N`, last line `max_core = C`; with an out
 // prefix the core numbers go to <out>.core.bin as raw little-endian uint64 and the rounds to <out>.round.bin as uint32.
+// cliquetruss_gpu_base <graph prefix> <k> [c] [out prefix] peels the per-edge k-clique counts (3 <= k <= 8).  With c (a number) the (k, c)-truss
+// (gm_clique_ktruss): `truss_edges = N`, `truss_cliques = M`, `rounds = R`; with an out prefix the per-entry counts go to <out>.cnt.bin as raw
+// little-endian uint64.  Without c the decomposition (gm_clique_truss_decompose): `rounds = R`, last line `max_truss = C`; with an out prefix
+// the per-entry theta goes to <out>.theta.bin as uint64 and the rounds to <out>.round.bin as uint32.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -48,12 +52,13 @@
 #define GM_MOTIFLOCAL 10
 #define GM_CLIQUELIST 11
 #define GM_CLIQUECORE 12
+#define GM_CLIQUETRUSS 13
 #if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL || \
-                        GM_APP == GM_CLIQUELIST || GM_APP == GM_CLIQUECORE)
+                        GM_APP == GM_CLIQUELIST || GM_APP == GM_CLIQUECORE || GM_APP == GM_CLIQUETRUSS)
 #include <hip/hip_runtime_api.h>
 #endif
 #ifndef GM_APP
-#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL|GM_RECTLOCAL|GM_MOTIFLOCAL|GM_CLIQUELIST|GM_CLIQUECORE"
+#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL|GM_RECTLOCAL|GM_MOTIFLOCAL|GM_CLIQUELIST|GM_CLIQUECORE|GM_CLIQUETRUSS"
 #endif
 
 namespace {
@@ -67,7 +72,7 @@ struct Cli {
 };
 
 #if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_CLIQUELOCAL && GM_APP != GM_RECTLOCAL && GM_APP != GM_MOTIFLOCAL && GM_APP != GM_CLIQUELIST && \
-    GM_APP != GM_CLIQUECORE
+    GM_APP != GM_CLIQUECORE && GM_APP != GM_CLIQUETRUSS
 // positional layout: TC has no <second>; the others do
 Cli parse(int argc, char **argv, bool has_second) {
   Cli c;
@@ -106,6 +111,9 @@ void usage_and_exit(const char *self) {
 #elif GM_APP == GM_CLIQUECORE
   std::printf("Usage: %s <graph prefix> <k> [c] [out prefix]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4 cores\n", self);
+#elif GM_APP == GM_CLIQUETRUSS
+  std::printf("Usage: %s <graph prefix> <k> [c] [out prefix]\n", self);
+  std::printf("Example: %s /graph_inputs/mico/graph 4 trusses\n", self);
 #elif GM_APP == GM_CLIQUELOCAL
   std::printf("Usage: %s <graph prefix> <k> [out prefix]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4 cliques\n", self);
@@ -150,7 +158,7 @@ int main(int argc, char **argv) {
   const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_RECTLOCAL);
   if (argc < (has_second ? 3 : 2)) usage_and_exit(argv[0]);
 #if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL || GM_APP == GM_CLIQUELIST || \
-    GM_APP == GM_CLIQUECORE
+    GM_APP == GM_CLIQUECORE || GM_APP == GM_CLIQUETRUSS
   Cli c;
   c.graph = argv[1];
   if (argc > 2) c.second = argv[2];  // [k] / [out.bin] / <k> / [out prefix]
@@ -398,6 +406,61 @@ int main(int argc, char **argv) {
     std::printf("dense_cliques = %llu\n", (unsigned long long)dense.cliques);
     std::printf("dense_density = %.6f\n", dense.vertices ? (double)dense.cliques / (double)dense.vertices : 0.0);
     std::printf("max_core = %llu\n", (unsigned long long)c_max);
+  }
+
+#elif GM_APP == GM_CLIQUETRUSS
+  std::printf("k-clique trusses (undirected graph only)\n");
+  std::fflush(stdout);
+  Graph g(c.graph);
+  g.print_meta_data();
+  const gm_csr csr = g.csr();
+  const int k = std::atoi(c.second.c_str());
+  // [c] is a number, [out prefix] is not
+  const bool with_c = argc > 3 && argv[3][0] != '\0' && std::string(argv[3]).find_first_not_of("0123456789") == std::string::npos;
+  const uint64_t cc = with_c ? std::strtoull(argv[3], nullptr, 10) : 0;
+  const std::string out = argc > (with_c ? 4 : 3) ? argv[with_c ? 4 : 3] : "";
+  const size_t ne = (size_t)csr.ne;
+  gm_graph *h = nullptr;
+  int rc = gm_graph_upload(&csr, 0, &h);
+  uint64_t n_edges = 0, n_cliques = 0, c_max = 0;
+  int32_t rounds = 0;
+  std::vector<uint64_t> wide(ne);   // K_e inside the truss, or theta
+  std::vector<uint32_t> round(ne);
+  if (rc == GM_OK) {
+    // (the arrays are the call's results and the caller's buffers)
+    uint64_t *d_wide = nullptr;
+    uint32_t *d_round = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&d_wide), sizeof(uint64_t) * (ne > 0 ? ne : 1)) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && hipMalloc(reinterpret_cast<void **>(&d_round), sizeof(uint32_t) * (ne > 0 ? ne : 1)) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && with_c) rc = gm_clique_ktruss(h, k, cc, nullptr, d_wide, &n_edges, &n_cliques, &rounds, nullptr);
+    if (rc == GM_OK && !with_c) rc = gm_clique_truss_decompose(h, k, nullptr, d_wide, d_round, &c_max, &rounds, nullptr);
+    if (rc == GM_OK && ne > 0 && hipMemcpy(wide.data(), d_wide, sizeof(uint64_t) * ne, hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && !with_c && ne > 0 && hipMemcpy(round.data(), d_round, sizeof(uint32_t) * ne, hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+    if (d_wide) (void)hipFree(d_wide);
+    if (d_round) (void)hipFree(d_round);
+  }
+  gm_graph_free(h);
+  if (rc == GM_OK && !out.empty()) {  // (the hosts this runs on are little-endian: the values go out as they lie in memory)
+    const struct { std::string path; const void *data; size_t size; } files[2] = {{out + (with_c ? ".cnt.bin" : ".theta.bin"), wide.data(), sizeof(uint64_t)},
+                                                                                 {out + ".round.bin", round.data(), sizeof(uint32_t)}};
+    for (int i = 0; i < (with_c ? 1 : 2); ++i) {
+      FILE *f = std::fopen(files[i].path.c_str(), "wb");
+      const bool ok = f && std::fwrite(files[i].data, files[i].size, ne, f) == ne;
+      if (f && std::fclose(f) != 0) rc = GM_ERR_IO;
+      if (!ok) rc = GM_ERR_IO;
+    }
+  }
+  if (rc != GM_OK) {
+    std::fprintf(stderr, "%s: %s %s\n", argv[0], gm_strerror(rc), gm_last_error());
+    return 1;
+  }
+  if (with_c) {
+    std::printf("truss_edges = %llu\n", (unsigned long long)n_edges);
+    std::printf("truss_cliques = %llu\n", (unsigned long long)n_cliques);
+    std::printf("rounds = %d\n", (int)rounds);
+  } else {
+    std::printf("rounds = %d\n", (int)rounds);
+    std::printf("max_truss = %llu\n", (unsigned long long)c_max);
   }
 
 #elif GM_APP == GM_RECTLOCAL

@@ -6,7 +6,7 @@
 //   gm_launch.hip  the launch layer (interface: gm_launch.h, for the three solver units only): launch prologue / epilogue, run_pattern,
 //                  gm_kernel_times, gm_tc / gm_clique / gm_motif, and every kernel of the layer
 //   gm_solve_sgl.hip    the SgL family: gm_sgl, the rectangle / house / pentagon map solvers, gm_diamond_support_*, gm_sgl4 / 5 / 6   (host code only)
-//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_clique_list, gm_rect_local, gm_clique_kcore, gm_clique_core_decompose                                 (host code only)
+//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_clique_list, gm_rect_local, gm_clique_kcore, gm_clique_core_decompose, gm_clique_ktruss, gm_clique_truss_decompose                                 (host code only)
 //   gm_tools.hip   set-op batch, R-MAT generator, PMC / issue-rate calibration kernels, self test
 // Host-side counterparts in the reference:
 //   GraphGPU::init / init_edgelist          include/graph_gpu.h:69-194
@@ -593,6 +593,16 @@ struct gm_graph {
     DevOwn<int> core_heavy;            // ne / (kKclLocalLdsRow + 1) + 1 vertices
     DevOwn<unsigned> core_scratch;
     size_t core_scratch_bytes = 0;
+    // k-clique trusses (gm_kcl_truss.hip), on the SYMMETRIC handle: K_e per entry while peeling, the marks and the frontier list of the
+    // canonical entries (the k-truss keeps its own over 32-bit supports), the 64 bytes of round words, the list of the frontier edges of
+    // more than kKclLocalLdsRow survivors and the wide kernel's scratch slots.  theta and the rounds go straight to the caller's arrays
+    DevOwn<unsigned long long> ktr_cnt;
+    DevOwn<unsigned char> ktr_mark;
+    DevOwn<int> ktr_front;             // ne / 2 + 1 entries
+    DevOwn<unsigned long long> ktr_words;
+    DevOwn<int> ktr_heavy;             // ne / 2 + 1 entries on a handle with a row beyond kKclLocalLdsRow, else one
+    DevOwn<unsigned> ktr_scratch;
+    size_t ktr_scratch_bytes = 0;
   } local;
   struct MapWork {  // the global counter maps of run_rect_acc / run_house_acc (rectangle, pentagon, house by wedge accumulation)
     DevOwn<unsigned> rect_acc;
@@ -751,6 +761,7 @@ void gm_touch_local();
 void gm_touch_list();
 void gm_touch_kcl_local();
 void gm_touch_kcl_core();
+void gm_touch_kcl_truss();
 void gm_touch_clique_list();
 void gm_touch_cbuild();
 void gm_touch_cmma();

@@ -827,6 +827,33 @@ hipError_t launch_core_peel(const KclCoreParams &p, unsigned n_front, int cu_cou
 hipError_t launch_core_peel_wide(const KclCoreParams &p, int grid_blocks, hipStream_t stream);
 // out[v] (may be nullptr): K_v inside the core or GM_CORE_REMOVED; [CW_ALIVE] += the survivors, [CW_SUM] += their counts
 hipError_t launch_core_out(const KclCoreParams &p, unsigned long long *out, int cu_count, hipStream_t stream);
+// k-clique trusses (gm_kcl_truss.hip): the rounds that peel the per-edge counts on the caller's SYMMETRIC graph, the state of an edge at its
+// canonical entry min(e, rev[e]) as in LocalPeelParams.  A frontier edge takes its path by the number of the SURVIVING common neighbours of
+// its ends, with the boundaries of the local counts and of the cores.  The words and the queues are the cores' (CoreWord, CoreQueue).
+struct KclTrussParams {
+  int nv, k, max_deg;               // max_deg: the longest row (sizes the scratch slot)
+  long long ne;
+  const int *rp, *col, *rev;        // the caller's symmetric CSR and the reverse entries
+  unsigned long long *cnt;          // per canonical entry: K_e among the edges not removed (not maintained once e is in the frontier)
+  unsigned char *mark;              // per canonical entry: LocalMark of the edge (the other entries: removed from the start)
+  int *front;                       // this round's frontier, canonical entries (ne / 2 + 1 ints)
+  unsigned long long *theta;        // nullptr, or per entry: `level` is written at the canonical entry when the edge enters the frontier
+  unsigned *round;                  // nullptr, or per entry: `round_no` is written then
+  unsigned long long thr, level;    // an alive edge of count < thr enters the frontier
+  unsigned round_no;
+  unsigned long long *words;        // 64 bytes, as KclCoreParams::words
+  int *heavy;                       // the frontier edges of more than kKclLocalLdsRow survivors, in order of arrival
+  unsigned heavy_cap;
+  unsigned *scratch;                // wide: gridDim.x slots of scratch_words words
+  unsigned long long scratch_words;
+};
+hipError_t launch_ktr_init(const KclTrussParams &p, int cu_count, hipStream_t stream);  // the marks; [CW_LEAST] of all edges
+hipError_t launch_ktr_mark(const KclTrussParams &p, int cu_count, hipStream_t stream);
+hipError_t launch_ktr_peel(const KclTrussParams &p, unsigned n_front, int cu_count, hipStream_t stream);
+hipError_t launch_ktr_peel_wide(const KclTrussParams &p, int grid_blocks, hipStream_t stream);
+// theta set: theta and round go from the canonical entries to their reverses (not an edge: 0).  Else out[e] (may be nullptr): K_e inside the
+// truss or GM_CORE_REMOVED, both directions; [CW_ALIVE] += the surviving edges, [CW_SUM] += their counts
+hipError_t launch_ktr_out(const KclTrussParams &p, unsigned long long *out, int cu_count, hipStream_t stream);
 unsigned long long kcl_local_scratch_words(int max_deg);
 hipError_t launch_kcl_local(const KclLocalParams &p, int stage, int grid_blocks, hipStream_t stream);  // stage: KclStage
 hipError_t launch_local_rev(int nv, long long ne, const int *rp, const int *col, int *rev, int cu_count, hipStream_t stream);

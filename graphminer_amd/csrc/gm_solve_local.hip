@@ -1,7 +1,7 @@
 // gm_solve_local.hip -- local counts, the k-truss, the triangle and k-clique listings, the local k-clique and 4-cycle counts over the launch layer (gm_launch.h):
 // gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_list, gm_clique_local, gm_rect_local, gm_motif_local, gm_clique_kcore,
-// gm_clique_core_decompose.  Host code only: the kernels are
-// gm_local.hip's, gm_list.hip's, gm_clique_list.hip's, gm_kcl_local.hip's, gm_kcl_core.hip's, gm_rect_local.hip's and gm_orbit_local.hip's, so this unit has no code object and no warm-up.
+// gm_clique_core_decompose, gm_clique_ktruss, gm_clique_truss_decompose.  Host code only: the kernels are
+// gm_local.hip's, gm_list.hip's, gm_clique_list.hip's, gm_kcl_local.hip's, gm_kcl_core.hip's, gm_kcl_truss.hip's, gm_rect_local.hip's and gm_orbit_local.hip's, so this unit has no code object and no warm-up.
 #include "gm_launch.h"
 #include "gm_orbit.h"
 
@@ -563,6 +563,141 @@ extern "C" int gm_clique_core_decompose(const gm_graph *sym, int k, const gm_lau
   if (!d_vertex_core) return GM_ERR_INVALID;
   if (int rc = clique_core_refusals(sym, k, la, "gm_clique_core_decompose")) return rc;
   return run_clique_core(sym, true, k, 0, la, nullptr, d_vertex_core, d_vertex_round, nullptr, nullptr, c_max, rounds, dense, st);
+}
+
+// ---- k-clique trusses (gm_kcl_truss.hip; DESIGN.md "k-clique trusses") -----------------------------------------------------------------------
+// gm_clique_ktruss (decompose = false) and gm_clique_truss_decompose: K_e per entry from gm_clique_local on the same handle, then the rounds
+// of run_clique_core with the canonical entries in place of the vertices.  24 bytes come back per round: the cliques destroyed so far, the
+// frontier's size and the smallest count that stays alive.
+static int run_clique_truss(const gm_graph *sym, bool decompose, int k, uint64_t c_in, const gm_launch *la, uint64_t *d_cnt_out, uint64_t *d_theta,
+                            uint32_t *d_round, uint64_t *n_edges, uint64_t *n_cliques, uint64_t *c_max, int32_t *rounds_out, gm_stats *st) {
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  if (n_edges) *n_edges = 0;
+  if (n_cliques) *n_cliques = 0;
+  if (c_max) *c_max = 0;
+  if (rounds_out) *rounds_out = 0;
+  fill_stats(st, (uint64_t)sym->ne, 0, 0, kWavesPerBlock * GM_WAVE);
+  uint64_t unused = 0;
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, &unused, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+  if (sym->ne == 0) {
+    if (rounds_out) *rounds_out = 1;  // (the round that finds the frontier empty)
+    return GM_OK;
+  }
+  const size_t nez = (size_t)g->ne, edges = (size_t)(g->ne / 2);
+  const bool wide = g->max_deg > kKclLocalLdsRow;  // (a frontier edge of more than kKclLocalLdsRow survivors needs two rows that long)
+  const unsigned long long slot_words = kcl_local_scratch_words(g->max_deg);
+  const size_t slot_bytes = sizeof(unsigned) * (size_t)slot_words;
+  const int grid_wide = wide ? clamp_grid((long long)(kKclScratchBudget / slot_bytes), (long long)g->cu_count * 2) : 0;
+  const size_t heavy_cap = wide ? edges + 1 : 1;
+  {
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (!g->local.ktr_cnt) HIP_TRY(g->local.ktr_cnt.alloc(sizeof(unsigned long long) * nez));
+    if (!g->local.ktr_mark) HIP_TRY(g->local.ktr_mark.alloc(nez));
+    if (!g->local.ktr_front) HIP_TRY(g->local.ktr_front.alloc(sizeof(int) * (edges + 1)));
+    if (!g->local.ktr_words) HIP_TRY(g->local.ktr_words.alloc(64));
+    if (!g->local.ktr_heavy) HIP_TRY(g->local.ktr_heavy.alloc(sizeof(int) * heavy_cap));
+    if (wide)  // (a slot that does not fit the device: the allocation fails and the call is refused)
+      if (int rc = grow_dev(g->local.ktr_scratch, &g->local.ktr_scratch_bytes, slot_bytes * (size_t)grid_wide)) return rc;
+  }
+  SubLaunches sub;
+  uint64_t total = 0;
+  if (int rc = sub.run([&](gm_stats *s) { return gm_clique_local(sym, k, &l2, nullptr, (uint64_t *)g->local.ktr_cnt.get(), &total, s); })) return rc;
+  if (int rc = start_timer(ctx)) return rc;
+  hipStream_t stream = ctx.stream;
+  // (once per handle, shared with the k-truss; filled on this call's stream, in front of its first reader)
+  if (int rc = g->lrev.ensure(g->mu, [&](RevIndex &ri) {
+        HIP_TRY(ri.rev.alloc(sizeof(int) * (size_t)std::max<long long>(g->ne, 1)));
+        HIP_TRY(launch_local_rev(g->nv, g->ne, g->d_rp, g->d_col, ri.rev, g->cu_count, stream));
+        return kOnceBuilt;
+      })) return rc;
+  KclTrussParams pp;
+  memset(&pp, 0, sizeof pp);
+  pp.nv = g->nv; pp.k = k; pp.max_deg = std::max(g->max_deg, 1); pp.ne = g->ne; pp.rp = g->d_rp; pp.col = g->d_col; pp.rev = g->lrev->rev;
+  pp.cnt = g->local.ktr_cnt; pp.mark = g->local.ktr_mark; pp.front = g->local.ktr_front; pp.words = g->local.ktr_words;
+  pp.theta = decompose ? (unsigned long long *)d_theta : nullptr;
+  pp.round = decompose ? (unsigned *)d_round : nullptr;
+  pp.heavy = g->local.ktr_heavy; pp.heavy_cap = (unsigned)heavy_cap;
+  pp.scratch = g->local.ktr_scratch; pp.scratch_words = slot_words;
+  unsigned long long h[3] = {0ull, 0ull, 0ull};  // [0] destroyed so far, [1] the frontier's size, [2] ~0 - the smallest count that stays (0: none)
+  HIP_TRY(hipMemsetAsync(pp.words, 0, 64, stream));
+  HIP_TRY(launch_ktr_init(pp, g->cu_count, stream));
+  unsigned long long level = 0, cmax = 0;
+  if (decompose) {  // the level the first round runs at: the smallest count of the graph
+    HIP_TRY(hipMemcpyAsync(&h[2], pp.words + CW_LEAST, sizeof h[2], hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    level = h[2] ? ~0ull - h[2] : 0ull;
+  }
+  int rounds = 0;
+  uint64_t removed = 0;
+  for (;;) {
+    pp.thr = decompose ? level + 1 : (unsigned long long)c_in;
+    pp.level = level;
+    pp.round_no = (unsigned)(rounds + 1);
+    HIP_TRY(hipMemsetAsync(pp.words + CW_FRONT, 0, 32, stream));  // (the frontier's size, the smallest count, the three queue words)
+    HIP_TRY(launch_ktr_mark(pp, g->cu_count, stream));
+    HIP_TRY(hipMemcpyAsync(h, pp.words + CW_DESTROYED, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    ++rounds;
+    if (h[0] > total || h[1] > (uint64_t)edges - removed) {
+      g_last_error = "gm_clique_truss: a round's counters left their range (internal error)";
+      return GM_ERR_INVALID;
+    }
+    if (h[1] == 0ull) {
+      if (!decompose || h[2] == 0ull) break;  // (decompose: nothing is alive any more)
+      level = ~0ull - h[2];                   // every alive edge has a count >= this: the first level that removes one
+      continue;
+    }
+    removed += h[1];
+    cmax = level;
+    HIP_TRY(launch_ktr_peel(pp, (unsigned)h[1], g->cu_count, stream));
+    if (wide) HIP_TRY(launch_ktr_peel_wide(pp, grid_wide, stream));
+  }
+  HIP_TRY(launch_ktr_out(pp, decompose ? nullptr : (unsigned long long *)d_cnt_out, g->cu_count, stream));
+  unsigned long long w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(w, pp.words, sizeof w, hipMemcpyDeviceToHost, stream));
+  if (int rc = sub.run([&](gm_stats *s) { return end_launch(ctx, FIN_COPY, 0, &unused, 1, s); })) return rc;  // (synchronises the stream)
+  const uint64_t left = total - w[CW_DESTROYED], per_clique = (uint64_t)(k * (k - 1) / 2);
+  const bool sums_ok = decompose ? left == 0 : w[CW_SUM] == left * per_clique && w[CW_ALIVE] <= (uint64_t)edges - removed;  // (the decomposition destroys all)
+  if (w[CW_ERR] != 0 || w[CW_DESTROYED] > total || !sums_ok) {
+    g_last_error = "gm_clique_truss: " + std::to_string(w[CW_ERR]) + " kernel errors, " + std::to_string(left) + " cliques left against the counts' sum " +
+                   std::to_string(w[CW_SUM]) + " / C(k, 2) (internal error)";
+    return GM_ERR_INVALID;
+  }
+  if (n_edges) *n_edges = w[CW_ALIVE];
+  if (n_cliques) *n_cliques = left;
+  if (c_max) *c_max = cmax;
+  if (rounds_out) *rounds_out = rounds;
+  if (st) st->kernel_ms = sub.ms;
+  return GM_OK;
+}
+
+static int clique_truss_refusals(const gm_graph *sym, int k, const gm_launch *la, const char *who) {
+  if (!sym || k < 3 || k > GM_MAX_CLIQUE_K) return GM_ERR_INVALID;
+  if (int rc = local_refusals(sym, la)) return rc;
+  if (k > 8) {
+    g_last_error = std::string(who) + ": k = 9 .. " + std::to_string(GM_MAX_CLIQUE_K) + " is not supported yet (3 <= k <= 8)";
+    return GM_ERR_UNSUPPORTED;
+  }
+  if (sym->d_symdeg) {  // (an oriented copy has no reverse entries: every edge state sits at the smaller of an entry and its reverse)
+    g_last_error = std::string(who) + ": needs the symmetric graph, not its oriented copy";
+    return GM_ERR_INVALID;
+  }
+  return GM_OK;
+}
+
+extern "C" int gm_clique_ktruss(const gm_graph *sym, int k, uint64_t c, const gm_launch *la, uint64_t *d_entry_cnt, uint64_t *n_edges,
+                                uint64_t *n_cliques, int32_t *rounds, gm_stats *st) {
+  if (int rc = clique_truss_refusals(sym, k, la, "gm_clique_ktruss")) return rc;
+  return run_clique_truss(sym, false, k, c, la, d_entry_cnt, nullptr, nullptr, n_edges, n_cliques, nullptr, rounds, st);
+}
+
+extern "C" int gm_clique_truss_decompose(const gm_graph *sym, int k, const gm_launch *la, uint64_t *d_entry_theta, uint32_t *d_entry_round,
+                                         uint64_t *c_max, int32_t *rounds, gm_stats *st) {
+  if (!d_entry_theta) return GM_ERR_INVALID;
+  if (int rc = clique_truss_refusals(sym, k, la, "gm_clique_truss_decompose")) return rc;
+  return run_clique_truss(sym, true, k, 0, la, nullptr, d_entry_theta, d_entry_round, nullptr, nullptr, c_max, rounds, st);
 }
 
 // ---- triangle listing (gm_list.hip; DESIGN.md "Triangle listing") -----------------------------------------------------------------------

@@ -365,6 +365,33 @@ def clique_core_decompose(g: DeviceGraph, k: int, *, chunk=0, return_stats=False
     return (*res, _stats(st)) if return_stats else res
 
 
+# ---- k-clique trusses (include/graphminer_amd.h: gm_clique_ktruss / gm_clique_truss_decompose) -------------------------------------------
+def clique_ktruss(g: DeviceGraph, k: int, c: int, *, chunk=0, return_stats=False, **kw):
+    """(undirected edges of the (k, c)-truss, its k-cliques, per entry K_e inside the truss or CORE_REMOVED as np.uint64[ne], peeling rounds)
+    of a SYMMETRIC graph: the largest edge set in which every edge lies in >= c k-cliques OF THAT SET.  3 <= k <= 8.  One GPU."""
+    import torch
+
+    la, st, nedges, ncl, rounds = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+    cnt = _dev_array(g, g.ne, torch.int64)
+    _lib.check(_lib.load().gm_clique_ktruss(g.handle, int(k), int(c), C.byref(la), cnt.data_ptr(), C.byref(nedges), C.byref(ncl), C.byref(rounds),
+                                            C.byref(st)), "gm_clique_ktruss")
+    res = (int(nedges.value), int(ncl.value), _to_numpy(cnt, g.ne, "uint64"), int(rounds.value))
+    return (*res, _stats(st)) if return_stats else res
+
+
+def clique_truss_decompose(g: DeviceGraph, k: int, *, chunk=0, return_stats=False, **kw):
+    """(k-clique trussness of every entry's edge as np.uint64[ne], the 1-based round whose frontier held it as np.uint32[ne], the largest
+    trussness, peeling rounds) of a SYMMETRIC graph; at k = 3 the ordinary trussness - 2.  3 <= k <= 8.  One GPU."""
+    import torch
+
+    la, st, cmax, rounds = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0), C.c_int32(0)
+    theta, rnd = _dev_array(g, g.ne, torch.int64), _dev_array(g, g.ne, torch.int32)
+    _lib.check(_lib.load().gm_clique_truss_decompose(g.handle, int(k), C.byref(la), theta.data_ptr(), rnd.data_ptr(), C.byref(cmax), C.byref(rounds),
+                                                     C.byref(st)), "gm_clique_truss_decompose")
+    res = (_to_numpy(theta, g.ne, "uint64"), _to_numpy(rnd, g.ne, "uint32"), int(cmax.value), int(rounds.value))
+    return (*res, _stats(st)) if return_stats else res
+
+
 # ---- local 4-cycle counts (include/graphminer_amd.h: gm_rect_local) -----------------------------------------------------------------------
 def rect_local(g: DeviceGraph, *, vertex=True, entries=True, chunk=0, return_stats=False, **kw):
     """(total, R_v as np.uint64[nv] or None, R_uv per entry as np.uint64[ne] or None) of a SYMMETRIC graph, in the caller's numbering and

@@ -487,6 +487,50 @@ int gm_clique_core_decompose(const gm_graph *sym, int k, const gm_launch *launch
                     uint32_t *d_vertex_round,   /* DEVICE uint32[nv] or NULL: the round whose frontier held v (>= 1) */
                     uint64_t *c_max, int32_t *rounds, gm_core_dense *dense /* may be NULL */, gm_stats *stats);
 
+/* ---- k-clique trusses (csrc/gm_kcl_truss.hip; DESIGN.md "k-clique trusses") ---------------------------------------------------------------
+ * The consumer of the per-edge k-clique counts: the (2,k)-nuclei.  SYMMETRIC graph with ascending rows and no self loops, 3 <= k <= 8.
+ * K_e(H) = the k-cliques, all of whose edges lie in the edge set H, that contain e.
+ *   The (k, c)-truss is the largest edge set H with K_e(H) >= c for every e of H (k = 3: the ordinary (c + 2)-truss).
+ *   The clique trussness theta_k(e) is the largest c whose (k, c)-truss holds e; it does not depend on the peeling order, and
+ *   theta_3(e) = trussness(e) - 2.
+ * The calls return numbers per edge, not the connected components of a nucleus nor a hierarchy of them.
+ * Rounds, the cores' scheme with edges in place of vertices; the state of an undirected edge sits at its canonical entry min(e, rev[e]): a
+ * round's frontier is every alive edge whose count is below the threshold; the host reads back 24 bytes -- the cliques destroyed so far, the
+ * frontier's size, the smallest count that stays alive --, the peel kernel runs, and the frontier becomes removed when the next round marks.
+ * The round that finds an empty frontier ends the level and is counted.  Decomposition: the level starts at the smallest count of the
+ * graph, the threshold is level + 1, an edge that enters the frontier gets theta = level and round = the 1-based index of that round, from
+ * an empty frontier the level goes to the smallest alive count; the call ends with the empty frontier that leaves nothing alive.
+ * The rule of the decrements: a k-clique counts only if none of its edges was removed before the round began.  Such a clique with at least
+ * one frontier edge is destroyed in this round: accounted once, by its frontier edge of the smallest canonical entry, and every edge of it
+ * outside the frontier loses one (the counts of frontier edges are not maintained).  Call an edge blocked for frontier edge e = (u, v) if
+ * it is removed, or in the frontier with a canonical entry below e's.  e works on S_e = the common neighbours w of u and v with neither
+ * (u, w) nor (v, w) blocked, and on the graph on S_e of the edges (w, x) that are not blocked: with c_i = the (k-2)-cliques of that graph
+ * that hold w_i it subtracts c_i from (u, w_i) and from (v, w_i), with c_ij = those that hold w_i and w_j (k >= 4) it subtracts c_ij from
+ * (w_i, w_j) -- each only outside the frontier -- and adds sum_i c_i / (k - 2) to the destroyed total: two 64-bit atomics per member of
+ * S_e, one per adjacent pair of members and one per frontier edge, nothing per clique.  The path follows |S_e|: up to 64 survivors a wave,
+ * up to 512 a workgroup with the matrix in LDS, beyond that a scratch slot per workgroup (sized by the longest row; a slot that does not
+ * fit the device refuses the call).  k = 3 runs through the same kernels with empty pair terms.
+ *
+ * gm_clique_ktruss: n_edges / n_cliques (may be NULL) = the undirected edges and the k-cliques of the (k, c)-truss (the graph's total minus
+ *   the destroyed; the call checks it against sum K_e / C(k, 2) over the truss), rounds (may be NULL) = the rounds run (>= 1).  c = 0
+ *   removes nothing.
+ * gm_clique_truss_decompose: c_max = max theta, rounds over all levels; the call checks that the rounds destroyed every clique.  An entry
+ *   that is not an edge (a self loop): theta 0, round 0, GM_CORE_REMOVED.
+ * The contract of the cores: one GPU, synchronous; a null handle -> GM_ERR_INVALID, k < 3 or k > GM_MAX_CLIQUE_K -> GM_ERR_INVALID,
+ * 9 <= k <= GM_MAX_CLIQUE_K -> GM_ERR_UNSUPPORTED, >= 2^31 entries -> GM_ERR_TOO_LARGE, world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED,
+ * unsorted rows or an oriented copy (gm_graph_orient) -> GM_ERR_INVALID; ne == 0 -> GM_OK, zeros, rounds = 1; launch->stream is honoured; launch->tune[6] & GM_T6_AS_NUMBERED is
+ * passed on to the initial count (gm_clique_local on the same handle, entry counts only) and to nothing else; stats->kernel_ms covers every
+ * kernel and the per-round read-backs, stats->tasks = the directed entries; before or after any other solver on the handle, whose arrays
+ * it leaves alone; state is initialised per call; ONE such call at a time per handle; everything it keeps on the handle is freed with the
+ * handle. */
+int gm_clique_ktruss(const gm_graph *sym, int k, uint64_t c, const gm_launch *launch,
+                     uint64_t *d_entry_cnt,   /* DEVICE uint64[ne] or NULL: K_e inside the (k,c)-truss, GM_CORE_REMOVED outside it; both directions of an edge equal */
+                     uint64_t *n_edges, uint64_t *n_cliques, int32_t *rounds, gm_stats *stats);
+int gm_clique_truss_decompose(const gm_graph *sym, int k, const gm_launch *launch,
+                     uint64_t *d_entry_theta, /* DEVICE uint64[ne], NULL -> GM_ERR_INVALID: theta_k of the entry's edge, both directions */
+                     uint32_t *d_entry_round, /* DEVICE uint32[ne] or NULL: the 1-based round whose frontier held the edge */
+                     uint64_t *c_max, int32_t *rounds, gm_stats *stats);
+
 /* ---- local 4-cycle counts (csrc/gm_rect_local.hip; DESIGN.md "Local 4-cycle counts") --------------------------------------------------
  * The 4-cycles (edge-induced, as the `rectangle` of gm_sgl counts them: src/sgl/cpu_kernels/rectangle.h) at every vertex and on every
  * edge, in the CALLER's numbering and entry order: the input of square clustering coefficients, of butterfly supports on bipartite data,
