@@ -126,6 +126,10 @@ SYMBOLS = [
     ("gm_clique_ktruss", C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(gm_launch), _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                    C.POINTER(gm_stats)]),
     ("gm_clique_truss_decompose", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(gm_stats)]),
+    ("gm_tri_clique4_local", C.c_int, [_P, C.POINTER(gm_launch), C.c_uint64, _P, C.POINTER(C.c_uint64), C.POINTER(gm_stats)]),
+    ("gm_nucleus34", C.c_int, [_P, C.c_uint32, C.POINTER(gm_launch), C.c_uint64, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                               C.POINTER(gm_stats)]),
+    ("gm_nucleus34_decompose", C.c_int, [_P, C.POINTER(gm_launch), C.c_uint64, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(gm_stats)]),
     ("gm_motif_formula", C.c_int, [_P, C.c_int, C.POINTER(gm_launch), C.POINTER(C.c_uint64), C.c_int, C.POINTER(gm_stats)]),
     ("gm_setop_batch", C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("gm_rmat_keys", C.c_int, [C.c_int, C.c_int64, C.c_uint64, _P, _P]),

@@ -1,9 +1,9 @@
 // gm_cli.cc -- one source for the whole command-line surface of the HIP solvers.
 //
-// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL|RECTLOCAL|MOTIFLOCAL|CLIQUELIST|CLIQUECORE|CLIQUETRUSS> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
+// Built with -DGM_APP=<TC|SGL|CLIQUE|MOTIF|TRUSS|SGL6|TCLIST|CLIQUELOCAL|RECTLOCAL|MOTIFLOCAL|CLIQUELIST|CLIQUECORE|CLIQUETRUSS|NUCLEUS34> (+ -DGM_APP_MULTIGPU, + -DGM_KCL_SPELLING) into
 //   tc_gpu_base tc_multigpu tc_multigpu_base | sgl_gpu_base sgl_multigpu | clique_gpu_base clique_multigpu kcl_gpu_base |
 //   motif_gpu_base motif_multigpu | truss_gpu_base | sgl6_gpu_base | tclist_gpu_base | cliquelocal_gpu_base | rectlocal_gpu_base | motiflocal_gpu_base |
-//   cliquelist_gpu_base | cliquecore_gpu_base | cliquetruss_gpu_base
+//   cliquelist_gpu_base | cliquecore_gpu_base | cliquetruss_gpu_base | nucleus34_gpu_base
 // The observable behaviour -- positional argv, defaults, usage text, banner and FINAL result lines -- is that of the
 // reference mains (src/triangle/main.cc:7-27, src/sgl/main.cc:9-35, src/clique/main.cc:8-28, src/motif/main.cc:9-31,
 // Pangolin spelling src/pangolin/clique/main.cc:20); scripts that grep those lines keep working.  truss_gpu_base <graph prefix> [k] has no
@@ -31,6 +31,12 @@
 // (gm_clique_ktruss): `truss_edges = N`, `truss_cliques = M`, `rounds = R`; with an out prefix the per-entry counts go to <out>.cnt.bin as raw
 // little-endian uint64.  Without c the decomposition (gm_clique_truss_decompose): `rounds = R`, last line `max_truss = C`; with an out prefix
 // the per-entry theta goes to <out>.theta.bin as uint64 and the rounds to <out>.round.bin as uint32.
+// nucleus34_gpu_base <graph prefix> [c] [out prefix] peels the per-triangle 4-clique counts into the (3,4)-nuclei: `total_num_triangles = T`
+// and `total_num_cliques = N` (gm_tc_list, gm_tri_clique4_local) first.  With c (a number) the c-nucleus set (gm_nucleus34):
+// `nucleus_triangles = N`, `nucleus_cliques = M`, `rounds = R`.  Without it the decomposition (gm_nucleus34_decompose): `rounds = R`, last
+// line `max_nucleus = C`.  With an out prefix the gm_tc_list rows go to <out>.tri.bin as raw little-endian int32 triples -- row t is the
+// triangle of every other file's value t --, the per-triangle counts to <out>.cnt.bin (with c) or theta to <out>.theta.bin and the rounds
+// to <out>.round.bin (without), all uint32.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -53,12 +59,13 @@
 #define GM_CLIQUELIST 11
 #define GM_CLIQUECORE 12
 #define GM_CLIQUETRUSS 13
+#define GM_NUCLEUS34 14
 #if defined(GM_APP) && (GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL || \
-                        GM_APP == GM_CLIQUELIST || GM_APP == GM_CLIQUECORE || GM_APP == GM_CLIQUETRUSS)
+                        GM_APP == GM_CLIQUELIST || GM_APP == GM_CLIQUECORE || GM_APP == GM_CLIQUETRUSS || GM_APP == GM_NUCLEUS34)
 #include <hip/hip_runtime_api.h>
 #endif
 #ifndef GM_APP
-#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL|GM_RECTLOCAL|GM_MOTIFLOCAL|GM_CLIQUELIST|GM_CLIQUECORE|GM_CLIQUETRUSS"
+#error "compile with -DGM_APP=GM_TC|GM_SGL|GM_CLIQUE|GM_MOTIF|GM_TRUSS|GM_SGL6|GM_TCLIST|GM_CLIQUELOCAL|GM_RECTLOCAL|GM_MOTIFLOCAL|GM_CLIQUELIST|GM_CLIQUECORE|GM_CLIQUETRUSS|GM_NUCLEUS34"
 #endif
 
 namespace {
@@ -72,7 +79,7 @@ struct Cli {
 };
 
 #if GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_CLIQUELOCAL && GM_APP != GM_RECTLOCAL && GM_APP != GM_MOTIFLOCAL && GM_APP != GM_CLIQUELIST && \
-    GM_APP != GM_CLIQUECORE && GM_APP != GM_CLIQUETRUSS
+    GM_APP != GM_CLIQUECORE && GM_APP != GM_CLIQUETRUSS && GM_APP != GM_NUCLEUS34
 // positional layout: TC has no <second>; the others do
 Cli parse(int argc, char **argv, bool has_second) {
   Cli c;
@@ -114,6 +121,9 @@ void usage_and_exit(const char *self) {
 #elif GM_APP == GM_CLIQUETRUSS
   std::printf("Usage: %s <graph prefix> <k> [c] [out prefix]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4 trusses\n", self);
+#elif GM_APP == GM_NUCLEUS34
+  std::printf("Usage: %s <graph prefix> [c] [out prefix]\n", self);
+  std::printf("Example: %s /graph_inputs/mico/graph nuclei\n", self);
 #elif GM_APP == GM_CLIQUELOCAL
   std::printf("Usage: %s <graph prefix> <k> [out prefix]\n", self);
   std::printf("Example: %s /graph_inputs/mico/graph 4 cliques\n", self);
@@ -155,10 +165,10 @@ static int strip_dev_options(int argc, char **argv) {
 
 int main(int argc, char **argv) {
   argc = strip_dev_options(argc, argv);
-  const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_RECTLOCAL);
+  const bool has_second = (GM_APP != GM_TC && GM_APP != GM_TRUSS && GM_APP != GM_TCLIST && GM_APP != GM_RECTLOCAL && GM_APP != GM_NUCLEUS34);
   if (argc < (has_second ? 3 : 2)) usage_and_exit(argv[0]);
 #if GM_APP == GM_TRUSS || GM_APP == GM_TCLIST || GM_APP == GM_CLIQUELOCAL || GM_APP == GM_RECTLOCAL || GM_APP == GM_MOTIFLOCAL || GM_APP == GM_CLIQUELIST || \
-    GM_APP == GM_CLIQUECORE || GM_APP == GM_CLIQUETRUSS
+    GM_APP == GM_CLIQUECORE || GM_APP == GM_CLIQUETRUSS || GM_APP == GM_NUCLEUS34
   Cli c;
   c.graph = argv[1];
   if (argc > 2) c.second = argv[2];  // [k] / [out.bin] / <k> / [out prefix]
@@ -461,6 +471,70 @@ int main(int argc, char **argv) {
   } else {
     std::printf("rounds = %d\n", (int)rounds);
     std::printf("max_truss = %llu\n", (unsigned long long)c_max);
+  }
+
+#elif GM_APP == GM_NUCLEUS34
+  std::printf("triangle nuclei (undirected graph only)\n");
+  std::fflush(stdout);
+  Graph g(c.graph);
+  g.print_meta_data();
+  const gm_csr csr = g.csr();
+  // [c] is a number, [out prefix] is not
+  const bool with_c = argc > 2 && argv[2][0] != '\0' && std::string(argv[2]).find_first_not_of("0123456789") == std::string::npos;
+  const uint32_t cc = with_c ? (uint32_t)std::strtoul(argv[2], nullptr, 10) : 0;
+  const std::string out = argc > (with_c ? 3 : 2) ? argv[with_c ? 3 : 2] : "";
+  gm_graph *h = nullptr;
+  int rc = gm_graph_upload(&csr, 0, &h);
+  uint64_t T = 0, written = 0, total_k4 = 0, n_tri = 0, n_cliques = 0;
+  uint32_t c_max = 0;
+  int32_t rounds = 0;
+  if (rc == GM_OK) rc = gm_tc_list(h, nullptr, 0, 0, nullptr, &T, nullptr, nullptr);  // (count only: sizes the per-triangle arrays)
+  const size_t nt = (size_t)T;
+  std::vector<int32_t> tri(3 * nt);
+  std::vector<uint32_t> val(nt), round(nt);  // the count inside the set, or theta
+  if (rc == GM_OK) {
+    // (the arrays are the calls' results and the caller's buffers)
+    int32_t *d_tri = nullptr;
+    uint32_t *d_val = nullptr, *d_round = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&d_tri), sizeof(int32_t) * 3 * (nt > 0 ? nt : 1)) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && hipMalloc(reinterpret_cast<void **>(&d_val), sizeof(uint32_t) * (nt > 0 ? nt : 1)) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && hipMalloc(reinterpret_cast<void **>(&d_round), sizeof(uint32_t) * (nt > 0 ? nt : 1)) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && nt > 0 && !out.empty()) rc = gm_tc_list(h, nullptr, 0, T, d_tri, &T, &written, nullptr);
+    if (rc == GM_OK) rc = gm_tri_clique4_local(h, nullptr, T, nullptr, &total_k4, nullptr);
+    if (rc == GM_OK && with_c) rc = gm_nucleus34(h, cc, nullptr, T, d_val, &n_tri, &n_cliques, &rounds, nullptr);
+    if (rc == GM_OK && !with_c) rc = gm_nucleus34_decompose(h, nullptr, T, d_val, d_round, &c_max, &rounds, nullptr);
+    if (rc == GM_OK && written > 0 && hipMemcpy(tri.data(), d_tri, sizeof(int32_t) * 3 * nt, hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && nt > 0 && hipMemcpy(val.data(), d_val, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+    if (rc == GM_OK && !with_c && nt > 0 && hipMemcpy(round.data(), d_round, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost) != hipSuccess) rc = GM_ERR_HIP;
+    if (d_tri) (void)hipFree(d_tri);
+    if (d_val) (void)hipFree(d_val);
+    if (d_round) (void)hipFree(d_round);
+  }
+  gm_graph_free(h);
+  if (rc == GM_OK && !out.empty()) {  // (the hosts this runs on are little-endian: the values go out as they lie in memory)
+    const struct { std::string path; const void *data; size_t n; } files[3] = {{out + ".tri.bin", tri.data(), 3 * nt},
+                                                                              {out + (with_c ? ".cnt.bin" : ".theta.bin"), val.data(), nt},
+                                                                              {out + ".round.bin", round.data(), nt}};
+    for (int i = 0; i < (with_c ? 2 : 3); ++i) {
+      FILE *f = std::fopen(files[i].path.c_str(), "wb");
+      const bool ok = f && std::fwrite(files[i].data, 4, files[i].n, f) == files[i].n;
+      if (f && std::fclose(f) != 0) rc = GM_ERR_IO;
+      if (!ok) rc = GM_ERR_IO;
+    }
+  }
+  if (rc != GM_OK) {
+    std::fprintf(stderr, "%s: %s %s\n", argv[0], gm_strerror(rc), gm_last_error());
+    return 1;
+  }
+  std::printf("total_num_triangles = %llu\n", (unsigned long long)T);
+  std::printf("total_num_cliques = %llu\n", (unsigned long long)total_k4);
+  if (with_c) {
+    std::printf("nucleus_triangles = %llu\n", (unsigned long long)n_tri);
+    std::printf("nucleus_cliques = %llu\n", (unsigned long long)n_cliques);
+    std::printf("rounds = %d\n", (int)rounds);
+  } else {
+    std::printf("rounds = %d\n", (int)rounds);
+    std::printf("max_nucleus = %u\n", (unsigned)c_max);
   }
 
 #elif GM_APP == GM_RECTLOCAL

@@ -283,6 +283,7 @@ int finish_handle(gm_graph *g) {
     gm_touch_kcl_local();
     gm_touch_kcl_core();
     gm_touch_kcl_truss();
+    gm_touch_nucleus34();
     gm_touch_clique_list();
     gm_touch_cbuild();
     gm_touch_cmma();

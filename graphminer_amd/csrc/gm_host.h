@@ -6,7 +6,7 @@
 //   gm_launch.hip  the launch layer (interface: gm_launch.h, for the three solver units only): launch prologue / epilogue, run_pattern,
 //                  gm_kernel_times, gm_tc / gm_clique / gm_motif, and every kernel of the layer
 //   gm_solve_sgl.hip    the SgL family: gm_sgl, the rectangle / house / pentagon map solvers, gm_diamond_support_*, gm_sgl4 / 5 / 6   (host code only)
-//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_clique_list, gm_rect_local, gm_clique_kcore, gm_clique_core_decompose, gm_clique_ktruss, gm_clique_truss_decompose                                 (host code only)
+//   gm_solve_local.hip  gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_local, gm_clique_list, gm_rect_local, gm_clique_kcore, gm_clique_core_decompose, gm_clique_ktruss, gm_clique_truss_decompose, gm_tri_clique4_local, gm_nucleus34, gm_nucleus34_decompose   (host code only)
 //   gm_tools.hip   set-op batch, R-MAT generator, PMC / issue-rate calibration kernels, self test
 // Host-side counterparts in the reference:
 //   GraphGPU::init / init_edgelist          include/graph_gpu.h:69-194
@@ -496,6 +496,19 @@ struct CliqueListOffsets {  // k-clique listing (gm_clique_list), one per k: the
   unsigned long long total = 0;
 };
 
+// triangle nuclei (gm_nucleus34.hip), on the SYMMETRIC handle.  The index: a triangle's id is its slot in gm_tc_list's order
+struct TriIndex {
+  DevOwn<unsigned long long> off;  // entries of the oriented copy + 1: the exclusive scan of |N+(u) & N+(v)|, the last one T
+  DevOwn<int> w, e;                // per triangle: the third vertex (ascending inside an entry's segment), the entry
+  unsigned long long total = 0;
+};
+struct Nucleus34State {  // the peel's state, initialised by every call: K4(t), the marks, the frontier list, the 64 bytes of round words
+  DevOwn<unsigned> cnt;
+  DevOwn<unsigned char> mark;
+  DevOwn<unsigned> front;
+  DevOwn<unsigned long long> words;
+};
+
 struct gm_graph {
   int device = 0;
   int nv = 0;
@@ -531,9 +544,11 @@ struct gm_graph {
   Once<RevIndex> lrev;
   Once<ListOffsets> list_off;
   Once<CliqueListOffsets> clique_list_off[6];  // k = 3 .. 8
+  Once<TriIndex> tri_index;
+  Once<Nucleus34State> nuc34;
   // gm_graph_sort_neighbors rewrites the rows: it refuses a handle on which one of these describes them already.  NOT checked (the list
   // predates them): core, core_blocks, long_rows, sup_corner, sup_masks, kst_entries, facts other than sum_c2, rect_lds, house_lds, wrect, rect_local,
-  // w5deg, lrev, list_off, clique_list_off, relabel_cache[2], clique_plans -- most of them cannot exist without one that is
+  // w5deg, lrev, list_off, clique_list_off, tri_index, nuc34, relabel_cache[2], clique_plans -- most of them cannot exist without one that is
   bool rows_in_use() const {
     return !tables.empty() || edesc.built() || tasklists.built() || kst.built() || dag_cache || relabel_cache[0] || relabel_cache[1] || rect_idx.built() ||
            wedge_blocks.built() || rect_tasks.built() || house_tables.built() || house_tasks.built() || house_blocks.built() || !bitmap_sets.empty() ||
@@ -762,6 +777,7 @@ void gm_touch_list();
 void gm_touch_kcl_local();
 void gm_touch_kcl_core();
 void gm_touch_kcl_truss();
+void gm_touch_nucleus34();
 void gm_touch_clique_list();
 void gm_touch_cbuild();
 void gm_touch_cmma();

@@ -895,6 +895,42 @@ struct KclListParams {
 // Synchronises the stream (the temporaries go back).
 hipError_t kcl_list_count_scan(const KclListParams &p, unsigned long long *off, int grid, int grid_wide, hipStream_t stream);
 hipError_t launch_kcl_list_fill(const KclListParams &p, int grid, int grid_wide, hipStream_t stream);
+// triangle nuclei (gm_nucleus34.hip): the triangle index of the oriented copy, the 4-cliques on every triangle and the rounds that peel
+// them.  A triangle's id is its slot in gm_tc_list's order: ascending entry (u, v) of the oriented copy, then ascending third vertex.  A
+// triangle (an entry of the index build) whose streamed row is below kNucWholeWave entries takes kNucGroup lanes, a longer one the wave.
+// Exported through gm_constant ("nuc_whole_wave").
+constexpr int kNucGroup = 8, kNucWholeWave = 64;
+enum NucWord : int { NW_TOTAL = 4 };  // beside CoreWord, in place of the queue words: the sum of K4(t) over all triangles (4 x the 4-cliques)
+struct NucIndexParams {
+  int nv;
+  long long ne;
+  const int *rp, *col;              // the oriented copy as numbered: it keeps the caller's ids
+  unsigned long long *cnt;          // count: per entry (u, v): |N+(u) & N+(v)|
+  const unsigned long long *off;    // fill: ne + 1 values, the exclusive scan of cnt ([ne] = T)
+  int *tri_w, *tri_e;               // fill: per triangle the third vertex (ascending inside an entry's segment) and the entry
+};
+struct Nuc34Params {
+  int nv;
+  unsigned long long nt;            // T < 2^32 - 1
+  const int *rp, *col;              // the caller's symmetric CSR
+  const int *drp, *dcol;            // the oriented copy
+  const unsigned long long *tri_off;
+  const int *tri_w, *tri_e;
+  unsigned *cnt;                    // per triangle: K4(t) among the triangles not removed (not maintained once t is in the frontier)
+  unsigned char *mark;              // per triangle: LocalMark
+  unsigned *front;                  // this round's frontier (T ids)
+  unsigned *theta, *round;          // nullptr, or per triangle: `level` / `round_no` are written when the triangle enters the frontier
+  unsigned thr, level, round_no;    // an alive triangle of count < thr enters the frontier
+  unsigned long long *words;        // 64 bytes: CoreWord, [NW_TOTAL]
+};
+hipError_t launch_nuc_index(const NucIndexParams &p, bool fill, int cu_count, hipStream_t stream);
+hipError_t nuc_index_scan(const unsigned long long *cnt, unsigned long long *off, size_t n, hipStream_t stream);  // exclusive, n values
+// out[t] = K4(t) (p.mark set: every triangle alive); [NW_TOTAL] += their sum, [CW_LEAST] of all triangles
+hipError_t launch_nuc_count(const Nuc34Params &p, unsigned *out, int cu_count, hipStream_t stream);
+hipError_t launch_nuc_mark(const Nuc34Params &p, int cu_count, hipStream_t stream);
+hipError_t launch_nuc_peel(const Nuc34Params &p, unsigned n_front, int cu_count, hipStream_t stream);
+// out[t] (may be nullptr): K4(t) inside the nucleus or GM_TRUSS_REMOVED; [CW_ALIVE] += the surviving triangles, [CW_SUM] += their counts
+hipError_t launch_nuc_out(const Nuc34Params &p, unsigned *out, int cu_count, hipStream_t stream);
 size_t mine_lds_bytes(Pattern pat);
 // the big-LDS classes (gm_mine_wide.hip): cls = 1 (mid rows) or 2 (big rows); DIAMOND, MOTIF3, MOTIF4E only
 hipError_t launch_mine_wide(Pattern pat, int cls, const MineParams &p, int grid_blocks, hipStream_t stream);

@@ -1,7 +1,7 @@
 // gm_solve_local.hip -- local counts, the k-truss, the triangle and k-clique listings, the local k-clique and 4-cycle counts over the launch layer (gm_launch.h):
 // gm_tc_local, gm_ktruss, gm_truss_decompose, gm_tc_list, gm_clique_list, gm_clique_local, gm_rect_local, gm_motif_local, gm_clique_kcore,
-// gm_clique_core_decompose, gm_clique_ktruss, gm_clique_truss_decompose.  Host code only: the kernels are
-// gm_local.hip's, gm_list.hip's, gm_clique_list.hip's, gm_kcl_local.hip's, gm_kcl_core.hip's, gm_kcl_truss.hip's, gm_rect_local.hip's and gm_orbit_local.hip's, so this unit has no code object and no warm-up.
+// gm_clique_core_decompose, gm_clique_ktruss, gm_clique_truss_decompose, gm_tri_clique4_local, gm_nucleus34, gm_nucleus34_decompose.  Host code only: the kernels are
+// gm_local.hip's, gm_list.hip's, gm_clique_list.hip's, gm_kcl_local.hip's, gm_kcl_core.hip's, gm_kcl_truss.hip's, gm_nucleus34.hip's, gm_rect_local.hip's and gm_orbit_local.hip's, so this unit has no code object and no warm-up.
 #include "gm_launch.h"
 #include "gm_orbit.h"
 
@@ -817,4 +817,168 @@ extern "C" int gm_clique_list(const gm_graph *sym, int k, const gm_launch *la, u
     st->grid = (uint32_t)grid;
   }
   return GM_OK;
+}
+
+// ---- triangle nuclei (gm_nucleus34.hip; DESIGN.md "Triangle nuclei") -------------------------------------------------------------------------
+// gm_tri_clique4_local (mode NUC_LOCAL), gm_nucleus34 (NUC_FIXED) and gm_nucleus34_decompose (NUC_DECOMPOSE): the triangle index of the
+// oriented copy (once per handle, kept on the SYMMETRIC handle), K4(t) of every triangle, then run_clique_truss's rounds with the triangle
+// ids in place of the canonical entries.  24 bytes come back per round: the cliques destroyed so far, the frontier's size and the smallest
+// count that stays alive.
+enum NucMode : int { NUC_LOCAL = 0, NUC_FIXED = 1, NUC_DECOMPOSE = 2 };
+static int run_nucleus34(const gm_graph *sym, NucMode mode, uint32_t c_in, const gm_launch *la, uint64_t n_tri, uint32_t *d_out, uint32_t *d_round,
+                         uint64_t *n_triangles, uint64_t *n_cliques, uint32_t *c_max, int32_t *rounds_out, gm_stats *st, const char *who) {
+  if (n_triangles) *n_triangles = 0;
+  if (n_cliques) *n_cliques = 0;
+  if (c_max) *c_max = 0;
+  if (rounds_out) *rounds_out = 0;
+  if (int rc = local_refusals(sym, la)) return rc;
+  if (sym->d_symdeg) {  // (the common neighbours of a triangle's corners are read off the symmetric rows)
+    g_last_error = std::string(who) + ": needs the symmetric graph, not its oriented copy";
+    return GM_ERR_INVALID;
+  }
+  gm_graph *g = const_cast<gm_graph *>(sym);
+  gm_launch l2 = launch_or_default(la);
+  fill_stats(st, 0, 0, 0, kWavesPerBlock * GM_WAVE);
+  uint64_t unused = 0;
+  LaunchCtx ctx;
+  if (int rc = begin_launch(sym, &l2, &unused, ctx)) return rc;  // (selects the device; refuses unsorted rows)
+  const auto wrong_length = [&](uint64_t T) {
+    g_last_error = std::string(who) + ": n_tri = " + std::to_string(n_tri) + ", the graph has " + std::to_string(T) + " triangles (the total of gm_tc_list)";
+    return GM_ERR_INVALID;
+  };
+  if (sym->ne == 0) {
+    if (n_tri != 0) return wrong_length(0);
+    if (rounds_out && mode != NUC_LOCAL) *rounds_out = 1;  // (the round that finds the frontier empty)
+    return GM_OK;
+  }
+  if (const int rc_dag = ensure_dag_cache(g)) return rc_dag;  // (the oriented copy, cached on the handle)
+  const gm_graph *dag = g->dag_cache;
+  if (int rc = reject_big(dag)) return rc;
+  if (int rc = start_timer(ctx)) return rc;
+  hipStream_t stream = ctx.stream;
+  if (int rc = g->tri_index.ensure(g->mu, [&](TriIndex &ti) -> int {  // (once per handle: built into a local value, moved in whole)
+        const size_t dne = (size_t)dag->ne;
+        HIP_TRY(ti.off.alloc(sizeof(unsigned long long) * (dne + 1)));
+        HIP_TRY(hipMemsetAsync(ti.off, 0, sizeof(unsigned long long) * (dne + 1), stream));
+        if (dne == 0) return kOnceBuilt;
+        NucIndexParams ip;
+        memset(&ip, 0, sizeof ip);
+        ip.nv = dag->nv; ip.ne = dag->ne; ip.rp = dag->d_rp; ip.col = dag->d_col;
+        {
+          DevBuf<unsigned long long> cnt;
+          HIP_TRY(cnt.alloc(dne + 1));
+          HIP_TRY(hipMemsetAsync(cnt.p + dne, 0, sizeof(unsigned long long), stream));
+          ip.cnt = cnt.p;
+          HIP_TRY(launch_nuc_index(ip, false, g->cu_count, stream));
+          HIP_TRY(nuc_index_scan(cnt.p, ti.off, dne + 1, stream));  // (synchronises the stream)
+        }
+        HIP_TRY(hipMemcpy(&ti.total, ti.off + dne, sizeof ti.total, hipMemcpyDeviceToHost));
+        if (ti.total >= 0xFFFFFFFFull) {
+          g_last_error = std::string(who) + ": " + std::to_string(ti.total) + " triangles (>= 2^32 - 1: beyond the 32-bit triangle ids)";
+          return GM_ERR_TOO_LARGE;
+        }
+        const size_t tz = (size_t)std::max<unsigned long long>(ti.total, 1);
+        HIP_TRY(ti.w.alloc(sizeof(int) * tz));
+        HIP_TRY(ti.e.alloc(sizeof(int) * tz));
+        ip.off = ti.off; ip.tri_w = ti.w; ip.tri_e = ti.e;
+        if (ti.total > 0) HIP_TRY(launch_nuc_index(ip, true, g->cu_count, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return kOnceBuilt;
+      })) return rc;
+  const uint64_t T = g->tri_index->total;
+  if (n_tri != T) return wrong_length(T);
+  if (st) st->tasks = T;
+  if (int rc = g->nuc34.ensure(g->mu, [&](Nucleus34State &ns) {
+        const size_t tz = (size_t)std::max<uint64_t>(T, 1);
+        HIP_TRY(ns.cnt.alloc(sizeof(unsigned) * tz));
+        HIP_TRY(ns.mark.alloc(tz));
+        HIP_TRY(ns.front.alloc(sizeof(unsigned) * tz));
+        HIP_TRY(ns.words.alloc(64));
+        return kOnceBuilt;
+      })) return rc;
+  const bool decompose = mode == NUC_DECOMPOSE;
+  Nuc34Params pp;
+  memset(&pp, 0, sizeof pp);
+  pp.nv = g->nv; pp.nt = T; pp.rp = g->d_rp; pp.col = g->d_col; pp.drp = dag->d_rp; pp.dcol = dag->d_col;
+  pp.tri_off = g->tri_index->off; pp.tri_w = g->tri_index->w; pp.tri_e = g->tri_index->e;
+  pp.cnt = g->nuc34->cnt; pp.mark = mode == NUC_LOCAL ? nullptr : g->nuc34->mark.get(); pp.front = g->nuc34->front; pp.words = g->nuc34->words;
+  pp.theta = decompose ? (unsigned *)d_out : nullptr;
+  pp.round = decompose ? (unsigned *)d_round : nullptr;
+  unsigned long long w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemsetAsync(pp.words, 0, 64, stream));
+  HIP_TRY(launch_nuc_count(pp, mode == NUC_LOCAL && d_out ? (unsigned *)d_out : pp.cnt, g->cu_count, stream));
+  HIP_TRY(hipMemcpyAsync(w, pp.words, sizeof w, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (w[NW_TOTAL] % 4ull != 0ull) {
+    g_last_error = std::string(who) + ": the sum of K4(t), " + std::to_string(w[NW_TOTAL]) + ", is not a multiple of 4 (internal error)";
+    return GM_ERR_INVALID;
+  }
+  const uint64_t total = w[NW_TOTAL] / 4ull;
+  int rounds = 0;
+  uint64_t removed = 0;
+  unsigned cmax = 0;
+  if (mode != NUC_LOCAL) {
+    unsigned long long h[3] = {0ull, 0ull, 0ull};  // [0] destroyed so far, [1] the frontier's size, [2] ~0 - the smallest count that stays (0: none)
+    unsigned level = decompose && w[CW_LEAST] ? (unsigned)(~0ull - w[CW_LEAST]) : 0u;  // the level the first round runs at: the smallest count
+    for (;;) {
+      pp.thr = decompose ? level + 1u : c_in;
+      pp.level = level;
+      pp.round_no = (unsigned)(rounds + 1);
+      HIP_TRY(hipMemsetAsync(pp.words + CW_FRONT, 0, 16, stream));  // (the frontier's size, the smallest count)
+      HIP_TRY(launch_nuc_mark(pp, g->cu_count, stream));
+      HIP_TRY(hipMemcpyAsync(h, pp.words + CW_DESTROYED, sizeof h, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      ++rounds;
+      if (h[0] > total || h[1] > T - removed) {
+        g_last_error = std::string(who) + ": a round's counters left their range (internal error)";
+        return GM_ERR_INVALID;
+      }
+      if (h[1] == 0ull) {
+        if (!decompose || h[2] == 0ull) break;  // (decompose: nothing is alive any more)
+        level = (unsigned)(~0ull - h[2]);       // every alive triangle has a count >= this: the first level that removes one
+        continue;
+      }
+      removed += h[1];
+      cmax = level;
+      HIP_TRY(launch_nuc_peel(pp, (unsigned)h[1], g->cu_count, stream));
+    }
+    HIP_TRY(launch_nuc_out(pp, decompose ? nullptr : (unsigned *)d_out, g->cu_count, stream));
+    HIP_TRY(hipMemcpyAsync(w, pp.words, sizeof w, hipMemcpyDeviceToHost, stream));
+  }
+  gm_stats s;
+  memset(&s, 0, sizeof s);
+  if (int rc = end_launch(ctx, FIN_COPY, 0, &unused, 1, &s)) return rc;  // (synchronises the stream)
+  if (st) st->kernel_ms = s.kernel_ms;
+  if (mode == NUC_LOCAL) {
+    if (n_cliques) *n_cliques = total;
+    return GM_OK;
+  }
+  const uint64_t left = total - w[CW_DESTROYED];
+  const bool sums_ok = decompose ? left == 0 && removed == T : w[CW_SUM] == 4ull * left && w[CW_ALIVE] == T - removed;  // (the decomposition destroys all)
+  if (w[CW_ERR] != 0 || w[CW_DESTROYED] > total || !sums_ok) {
+    g_last_error = std::string(who) + ": " + std::to_string(w[CW_ERR]) + " kernel errors, " + std::to_string(left) +
+                   " cliques left against the counts' sum " + std::to_string(w[CW_SUM]) + " / 4 (internal error)";
+    return GM_ERR_INVALID;
+  }
+  if (n_triangles) *n_triangles = w[CW_ALIVE];
+  if (n_cliques) *n_cliques = left;
+  if (c_max) *c_max = cmax;
+  if (rounds_out) *rounds_out = rounds;
+  return GM_OK;
+}
+
+extern "C" int gm_tri_clique4_local(const gm_graph *sym, const gm_launch *la, uint64_t n_tri, uint32_t *d_tri_cnt, uint64_t *total_k4, gm_stats *st) {
+  if (total_k4) *total_k4 = 0;
+  return run_nucleus34(sym, NUC_LOCAL, 0, la, n_tri, d_tri_cnt, nullptr, nullptr, total_k4, nullptr, nullptr, st, "gm_tri_clique4_local");
+}
+
+extern "C" int gm_nucleus34(const gm_graph *sym, uint32_t c, const gm_launch *la, uint64_t n_tri, uint32_t *d_tri_cnt, uint64_t *n_triangles,
+                            uint64_t *n_cliques, int32_t *rounds, gm_stats *st) {
+  return run_nucleus34(sym, NUC_FIXED, c, la, n_tri, d_tri_cnt, nullptr, n_triangles, n_cliques, nullptr, rounds, st, "gm_nucleus34");
+}
+
+extern "C" int gm_nucleus34_decompose(const gm_graph *sym, const gm_launch *la, uint64_t n_tri, uint32_t *d_tri_theta, uint32_t *d_tri_round,
+                                      uint32_t *c_max, int32_t *rounds, gm_stats *st) {
+  if (!d_tri_theta) return GM_ERR_INVALID;
+  return run_nucleus34(sym, NUC_DECOMPOSE, 0, la, n_tri, d_tri_theta, d_tri_round, nullptr, nullptr, c_max, rounds, st, "gm_nucleus34_decompose");
 }

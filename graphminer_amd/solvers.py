@@ -392,6 +392,56 @@ def clique_truss_decompose(g: DeviceGraph, k: int, *, chunk=0, return_stats=Fals
     return (*res, _stats(st)) if return_stats else res
 
 
+# ---- triangle nuclei (include/graphminer_amd.h: gm_tri_clique4_local / gm_nucleus34 / gm_nucleus34_decompose) ----------------------------
+def _triangle_total(g: DeviceGraph, la) -> int:
+    """T of a count-only gm_tc_list: the length of every per-triangle array, whose index is the row of tc_list's listing"""
+    total = C.c_uint64(0)
+    _lib.check(_lib.load().gm_tc_list(g.handle, C.byref(la), 0, 0, None, C.byref(total), None, None), "gm_tc_list")
+    return int(total.value)
+
+
+def tri_clique4_local(g: DeviceGraph, *, chunk=0, return_stats=False, **kw):
+    """(the 4-cliques of a SYMMETRIC graph, K4(t) as np.uint32[T]): the 4-cliques that contain triangle t, t = the row of tc_list(g).
+    One GPU."""
+    import torch
+
+    la, st, total = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0)
+    T = _triangle_total(g, la)
+    cnt = _dev_array(g, T, torch.int32)
+    _lib.check(_lib.load().gm_tri_clique4_local(g.handle, C.byref(la), T, cnt.data_ptr(), C.byref(total), C.byref(st)), "gm_tri_clique4_local")
+    res = (int(total.value), _to_numpy(cnt, T, "uint32"))
+    return (*res, _stats(st)) if return_stats else res
+
+
+def nucleus34(g: DeviceGraph, c: int, *, chunk=0, return_stats=False, **kw):
+    """(triangles of the (3,4)-c-nucleus set, its 4-cliques, per triangle its count inside the set or TRUSS_REMOVED as np.uint32[T], peeling
+    rounds) of a SYMMETRIC graph: the largest triangle set in which every triangle lies in >= c 4-cliques all of whose triangles are IN THAT
+    SET; t = the row of tc_list(g).  One GPU."""
+    import torch
+
+    la, st, ntri, ncl, rounds = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+    T = _triangle_total(g, la)
+    cnt = _dev_array(g, T, torch.int32)
+    _lib.check(_lib.load().gm_nucleus34(g.handle, int(c), C.byref(la), T, cnt.data_ptr(), C.byref(ntri), C.byref(ncl), C.byref(rounds), C.byref(st)),
+               "gm_nucleus34")
+    res = (int(ntri.value), int(ncl.value), _to_numpy(cnt, T, "uint32"), int(rounds.value))
+    return (*res, _stats(st)) if return_stats else res
+
+
+def nucleus34_decompose(g: DeviceGraph, *, chunk=0, return_stats=False, **kw):
+    """(theta of every triangle as np.uint32[T], the 1-based round whose frontier held it as np.uint32[T], the largest theta, peeling rounds)
+    of a SYMMETRIC graph: theta(t) = the largest c whose (3,4)-c-nucleus set holds t; t = the row of tc_list(g).  One GPU."""
+    import torch
+
+    la, st, cmax, rounds = _launch(0, 1, chunk, **kw), gm_stats(), C.c_uint32(0), C.c_int32(0)
+    T = _triangle_total(g, la)
+    theta, rnd = _dev_array(g, T, torch.int32), _dev_array(g, T, torch.int32)
+    _lib.check(_lib.load().gm_nucleus34_decompose(g.handle, C.byref(la), T, theta.data_ptr(), rnd.data_ptr(), C.byref(cmax), C.byref(rounds),
+                                                  C.byref(st)), "gm_nucleus34_decompose")
+    res = (_to_numpy(theta, T, "uint32"), _to_numpy(rnd, T, "uint32"), int(cmax.value), int(rounds.value))
+    return (*res, _stats(st)) if return_stats else res
+
+
 # ---- local 4-cycle counts (include/graphminer_amd.h: gm_rect_local) -----------------------------------------------------------------------
 def rect_local(g: DeviceGraph, *, vertex=True, entries=True, chunk=0, return_stats=False, **kw):
     """(total, R_v as np.uint64[nv] or None, R_uv per entry as np.uint64[ne] or None) of a SYMMETRIC graph, in the caller's numbering and

@@ -531,6 +531,52 @@ int gm_clique_truss_decompose(const gm_graph *sym, int k, const gm_launch *launc
                      uint32_t *d_entry_round, /* DEVICE uint32[ne] or NULL: the 1-based round whose frontier held the edge */
                      uint64_t *c_max, int32_t *rounds, gm_stats *stats);
 
+/* ---- triangle nuclei (csrc/gm_nucleus34.hip; DESIGN.md "Triangle nuclei") ---------------------------------------------------------------
+ * The third member of the nucleus line (Sariyuce et al.): triangles as the peeled unit, 4-cliques as what holds them together -- the
+ * (3,4)-nuclei.  SYMMETRIC graph with ascending rows.  Every per-triangle array is indexed by the triangle's ID = its row in gm_tc_list's
+ * listing on the same handle (ascending entry (u, v) of the oriented copy, then ascending third vertex): a caller lines values up with
+ * gm_tc_list rows, window by window.  n_tri is the length the caller allocated and must equal T, the total of a count-only gm_tc_list
+ * (else GM_ERR_INVALID); T >= 2^32 - 1 -> GM_ERR_TOO_LARGE.
+ * K4(t) = the 4-cliques that contain triangle t = |N(a) & N(b) & N(c)| of its corners, at most nv - 3.  For a triangle set H, K4_t(H) = the
+ * 4-cliques containing t all four of whose triangles lie in H; the (3,4)-c-nucleus set is the largest H with K4_t(H) >= c for every t of H,
+ * theta(t) the largest c whose set holds t.  The calls return numbers per triangle, not connected components nor a hierarchy.
+ * Rounds, the k-clique trusses' scheme with triangles in place of edges: a round's frontier is every alive triangle whose count is below
+ * the threshold; the host reads back 24 bytes -- the cliques destroyed so far, the frontier's size, the smallest count that stays alive --,
+ * the peel kernel runs, and the frontier becomes removed when the next round marks.  The round that finds an empty frontier is counted.
+ * Decomposition: the level starts at the smallest count, the threshold is level + 1, a triangle that enters the frontier gets theta = level
+ * and round = the 1-based index of that round, from an empty frontier the level goes to the smallest alive count; the call ends with the
+ * empty frontier that leaves nothing alive.
+ * The rule of the decrements: a 4-clique counts only if none of its four triangles was removed before the round began.  Such a clique with
+ * at least one frontier triangle is destroyed in this round: accounted once, by its frontier triangle of the smallest id, and every
+ * triangle of it outside the frontier loses one (the counts of frontier triangles are not maintained).  Frontier triangle t = (a, b, c)
+ * takes every common neighbour x of its corners, looks up the ids of (a, b, x), (a, c, x), (b, c, x), skips x if one of them is removed or
+ * in the frontier below t's id, and otherwise adds one to the destroyed total and subtracts one from each of the three outside the
+ * frontier: three 32-bit atomics per destroyed clique at most.  The marks do not change while a peel kernel runs: the result does not
+ * depend on the order of arrival.
+ *
+ * gm_tri_clique4_local: d_tri_cnt (DEVICE uint32[n_tri] or NULL) = K4(t); total_k4 (may be NULL) = sum K4(t) / 4 = the 4-cliques of the
+ *   graph (the call checks that the division is exact).
+ * gm_nucleus34: n_triangles / n_cliques (may be NULL) = the triangles and the 4-cliques of the c-nucleus set (the graph's total minus the
+ *   destroyed; the call checks it against sum of the surviving counts / 4), rounds (may be NULL) = the rounds run (>= 1).  c = 0 removes
+ *   nothing.
+ * gm_nucleus34_decompose: c_max = max theta, rounds over all levels; the call checks that the rounds destroyed every 4-clique.
+ * The contract of the k-clique trusses: one GPU, synchronous; a null handle -> GM_ERR_INVALID, >= 2^31 entries -> GM_ERR_TOO_LARGE,
+ * world > 1 or launch->d_counts -> GM_ERR_UNSUPPORTED, unsorted rows or an oriented copy (gm_graph_orient) -> GM_ERR_INVALID; T == 0 ->
+ * GM_OK, zeros, rounds = 1; launch->stream is honoured, launch->tune[6] is ignored; stats->kernel_ms covers every kernel and the per-round
+ * read-backs (a handle's first call also builds the triangle index), stats->tasks = T; before or after any other solver on the handle,
+ * whose arrays it leaves alone; state is initialised per call; ONE such call at a time per handle; the index (8 bytes per entry of the
+ * oriented copy + 8 per triangle) and the state (9 bytes per triangle) stay on the handle and are freed with it. */
+int gm_tri_clique4_local(const gm_graph *sym, const gm_launch *launch, uint64_t n_tri,
+                     uint32_t *d_tri_cnt,     /* DEVICE uint32[n_tri] or NULL: K4(t) */
+                     uint64_t *total_k4, gm_stats *stats);
+int gm_nucleus34(const gm_graph *sym, uint32_t c, const gm_launch *launch, uint64_t n_tri,
+                     uint32_t *d_tri_cnt,     /* DEVICE uint32[n_tri] or NULL: K4_t inside the c-nucleus set, GM_TRUSS_REMOVED outside it */
+                     uint64_t *n_triangles, uint64_t *n_cliques, int32_t *rounds, gm_stats *stats);
+int gm_nucleus34_decompose(const gm_graph *sym, const gm_launch *launch, uint64_t n_tri,
+                     uint32_t *d_tri_theta,   /* DEVICE uint32[n_tri], NULL -> GM_ERR_INVALID: theta of the triangle */
+                     uint32_t *d_tri_round,   /* DEVICE uint32[n_tri] or NULL: the 1-based round whose frontier held the triangle */
+                     uint32_t *c_max, int32_t *rounds, gm_stats *stats);
+
 /* ---- local 4-cycle counts (csrc/gm_rect_local.hip; DESIGN.md "Local 4-cycle counts") --------------------------------------------------
  * The 4-cycles (edge-induced, as the `rectangle` of gm_sgl counts them: src/sgl/cpu_kernels/rectangle.h) at every vertex and on every
  * edge, in the CALLER's numbering and entry order: the input of square clustering coefficients, of butterfly supports on bipartite data,
