@@ -85,6 +85,73 @@ def test_gadget_closed_forms(k):
             G.expected(G.hub_edge_gadget(a, p, m - 1, seed), a, p, m - 1, seed, k)
 
 
+def held_against_the_reference(label, g, k, want):
+    cnt, edges, ncl, rounds = R.ktruss(g, k, want["c"])
+    bad = np.flatnonzero(cnt != want["cnt"])
+    print(f"{label} k={k}: c {want['c']}; the reference: edges {edges} cliques {ncl} rounds {rounds}, the closed forms: {want['edges']} "
+          f"{want['cliques']} {want['rounds']}; {bad.size} of {cnt.size} entries differ", flush=True)
+    assert bad.size == 0, label
+    assert (edges, ncl, rounds) == (want["edges"], want["cliques"], want["rounds"]), label
+    return cnt
+
+
+@pytest.mark.parametrize("k", [3, 4, 5])
+def test_split_gadget_closed_forms(k):
+    """e and X leave in one frontier and G' = G - e - X is two one-sided gadgets: expected per half against the rounds of the reference"""
+    for a in range(12, 17):
+        p, q, seed = 0.5, 0.5, a
+        m = G.split_booster(a, p, q, seed, k)
+        g = G.split_hub_edge_gadget(a, p, q, m, seed)
+        want = G.split_expected(g, a, p, q, m, seed, k)
+        cnt = held_against_the_reference(f"split gadget a={a} m={m}", g, k, want)
+        assert int((cnt == R.REMOVED).sum()) == 2 * (want["x"] + 1) and want["x"] >= 8
+        d = R.decompose(g, k)
+        assert np.array_equal(d.theta < want["c"], cnt == R.REMOVED), "in the decomposition e and X are what lies below c"
+        if m > 2:  # one booster less: the closed forms themselves say that something else of G' falls below c
+            with pytest.raises(AssertionError):
+                G.split_expected(G.split_hub_edge_gadget(a, p, q, m - 1, seed), a, p, q, m - 1, seed, k)
+
+
+@pytest.mark.parametrize("k", [3, 4, 5])
+def test_three_hub_closed_forms(k):
+    """three hubs, in a triangle and with (h2, h3) left out: the closed forms extended by the number of hubs against the reference"""
+    a, p, seed = 12, 0.4, 12
+    for triangle in (True, False):
+        m = G.booster(a, p, seed, k, 3, triangle)
+        g = G.hub_edge_gadget(a, p, m, seed, 3, triangle)
+        want = G.expected(g, a, p, m, seed, k, 3, triangle)
+        cnt = held_against_the_reference(f"three hubs a={a} m={m} triangle={triangle}", g, k, want)
+        assert int((cnt == R.REMOVED).sum()) == (6 if triangle else 4)
+
+
+def test_preconditions_of_the_gpu_cells():
+    """every gadget cell of tests/test_gpu_clique_truss.py: split_expected / expected assert, from the closed forms alone, that exactly the
+    hub edge(s) and X enter the first frontier and that everything else ends at or above c -- pure arithmetic, no GPU"""
+    from common import kcl_row_constants
+
+    rc = kcl_row_constants()
+    for a, p, q, k in G.split_cells(rc):
+        m = G.split_booster(a, p, q, a, k)
+        want = G.split_expected(G.split_hub_edge_gadget(a, p, q, m, a), a, p, q, m, a, k)
+        assert want["x"] >= 8 and want["x_words"] == (0, want["words"] - 1) and want["x_most"] < want["c"]
+        assert len(want["spoke_decrements"]) >= 3
+    for a, p, k in G.triangle_cells(rc):
+        m = G.booster(a, p, a, k, 3, True)
+        want = G.expected(G.hub_edge_gadget(a, p, m, a, 3, True), a, p, m, a, k, 3, True)
+        assert int((want["cnt"] == R.REMOVED).sum()) == 6
+    for i, (a, p, k) in enumerate(G.second_group_cells(rc)):
+        m = G.booster(a, p, a, k)
+        want = G.expected(G.hub_edge_gadget(a, p, m, a), a, p, m, a, k)
+        one, both = G.a_edges_from(a, p, a, rc["lanes"])
+        print(f"a={a}: {one} edges of A reach position {rc['lanes']}, {both} with both ends", flush=True)
+        assert a > rc["lanes"] and one >= 1 and (i == 0 or both >= 1) and len(want["spoke_decrements"]) >= 3
+    a, p, k, least_m = G.long_row_cell(rc)
+    m = max(G.booster(a, p, a, k), least_m)
+    g = G.hub_edge_gadget(a, p, m, a)
+    G.expected(g, a, p, m, a, k)
+    assert int(np.diff(g.row_ptr)[:a].min()) > 4 * a and rc["regs2"] < a <= rc["lds"]
+
+
 def test_book_takes_every_page_from_the_spine_in_one_round():
     for k in (3, 4):
         d = R.decompose(G.book(6, k), k)

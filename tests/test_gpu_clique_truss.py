@@ -2,8 +2,10 @@
 tests/clique_truss_ref.py, the existing k-truss at k = 3 and the closed forms of tests/truss_gadgets.py: per entry, with the rounds and the
 clique totals -- on the five small graphs, on the shapes where a CONCURRENT round goes wrong (a whole clique in one frontier, two frontier
 edges over shared survivors, two disjoint frontier edges of one 4-clique, tens of thousands of decrements on one counter), and with a hub
-edge whose surviving common neighbours lie on both sides of every length at which the peel kernel changes path.  Every value is printed
-before it is asserted."""
+edge whose surviving common neighbours lie on both sides of every length at which the peel kernel changes path.  The blocked cells
+(DESIGN.md "k-clique trusses: blocked cells") put blocked spokes and blocked pairs on the workgroup path and in the wide kernel: K_n one
+past every boundary, the split gadget, three hubs in a triangle, matrix rows of more than 64 words, rows longer than four lists.  Every
+value is printed before it is asserted."""
 import ctypes as C
 import functools
 from math import comb
@@ -145,10 +147,16 @@ def test_ktruss_small_graphs(dev, name, k):
 
 
 # ---- 4. shapes where a concurrent round goes wrong ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,k", [(5, 3), (65, 3), (65, 4), (20, 8)])
+@pytest.mark.parametrize("n,k", [(5, 3), (65, 3), (65, 4), (20, 8)] + [(key, 3) for key in ("regs2", "regs8", "regs12", "lds")] +
+                         [(key, 4) for key in ("regs2", "regs8", "regs12", "lds")])
 def test_whole_clique_in_one_frontier(dev, n, k):
     """K_n: every edge is in the frontier, S_e runs through every length from n - 2 down to 0, nobody survives to take a decrement, and the
-    destroyed total must land on C(n, k) exactly (the call checks it)"""
+    destroyed total must land on C(n, k) exactly (the call checks it).  The survivors of (u, v) are the ids above v: every spoke to a lower
+    id is blocked, so the blocked entries are the low ids of the streamed row, on every path n - 2 reaches.  n = a boundary's name: n - 2,
+    the longest S_e, lies one past it"""
+    if isinstance(n, str):
+        key, n = n, kcl_row_constants()[n] + 3
+        check(f"K_{n}: the longest S_e, one past {key}", n - 2, kcl_row_constants()[key] + 1)
     g = T.graph("complete", (n,))
     each, ne = comb(n - 2, k - 2), n * (n - 1)
     want = R.Decomposition(np.full(ne, each, np.uint64), np.ones(ne, np.uint32), each, 2)
@@ -174,6 +182,68 @@ def test_two_frontier_edges_sharing_a_vertex_over_shared_survivors(dev):
         with g.to_device(dev) as sym:
             check_ktruss(f"three hubs a={a}", g, sym, k, c, want)
             check_decompose(f"three hubs a={a}", g, sym, k, R.decompose(g, k))
+
+
+TRIANGLE_IDS = ["regs2-k3", "regs2-k4", "lds-k3", "lds-k4"]
+
+
+@pytest.mark.parametrize("cell", range(len(TRIANGLE_IDS)), ids=TRIANGLE_IDS)
+def test_three_hubs_in_a_triangle_on_the_long_paths(dev, cell):
+    """the three-hub gadget with the edge (h2, h3): three frontier edges over the same a survivors.  (h1, h2), the lowest entry, keeps h3 --
+    a + 1 survivors, the cliques with two or three hubs are its own --; for (h1, h3) and (h2, h3) the spoke to the third hub is blocked, at
+    the END of the streamed row, behind a kept entries.  The closed forms (tests/test_clique_truss_host.py holds them against the reference
+    at a = 12); on the workgroup path the reference itself too"""
+    rc = kcl_row_constants()
+    a, p, k = G.triangle_cells(rc)[cell]
+    check(f"{TRIANGLE_IDS[cell]}: a one past the boundary", a, rc[TRIANGLE_IDS[cell].split("-")[0]] + 1)
+    m = G.booster(a, p, a, k, 3, True)
+    g = G.hub_edge_gadget(a, p, m, a, 3, True)
+    exp = G.expected(g, a, p, m, a, k, 3, True)
+    src, dst = endpoints(g)
+    gone = np.flatnonzero(exp["cnt"] == REMOVED)
+    h1 = a + 3 * m
+    check(f"a={a} k={k}: the three hub edges leave", sorted(zip(src[gone].tolist(), dst[gone].tolist())),
+          sorted((h1 + i, h1 + j) for i in range(3) for j in range(3) if i != j))
+    check(f"a={a} k={k}: the hubs' rows end with the other hubs", [g.col_idx[g.row_ptr[h + 1] - 1] for h in (h1, h1 + 1, h1 + 2)], [h1 + 2, h1 + 2, h1 + 1])
+    want = (exp["cnt"], exp["edges"], exp["cliques"], exp["rounds"])
+    if a <= rc["regs2"] + 1:
+        ref = R.ktruss(g, k, exp["c"])
+        check_arrays(f"a={a} k={k}: the closed forms against the reference", want[0], ref[0])
+        check(f"a={a} k={k}: (edges, cliques, rounds) against the reference", want[1:], tuple(ref[1:]))
+    with g.to_device(dev) as sym:
+        check_ktruss(f"hubs in a triangle a={a} m={m}", g, sym, k, exp["c"], want)
+        if a <= rc["regs2"] + 1:
+            check_decompose(f"hubs in a triangle a={a} m={m}", g, sym, k, R.decompose(g, k))
+
+
+SPLIT_IDS = ["regs2-k4", "regs2-k5", "regs8-k4", "regs12-k4", "lds-k4"]
+SPLIT_DECOMPOSE = ("regs2-k4", "regs2-k5")  # (where the plain reference finishes in seconds)
+
+
+@pytest.mark.parametrize("cell", range(len(SPLIT_IDS)), ids=SPLIT_IDS)
+def test_split_gadget_blocked_pairs_inside_a_long_list(dev, cell):
+    """the hub edge e with the edges X ACROSS the two halves of its survivors in the same frontier, at lower entries, all four spokes of each
+    alive: the cliques {w, x, h1, h2, ..} are the account of (w, x), and from e only the pair filter of the matrix hides them -- the
+    workgroup path's ktr_build_msym in three register widths and the wide kernel's own build.  Exactly e and X leave, in two rounds; what
+    stays has its count in G' = G - e - X, by the closed forms per half and by gm_clique_local on the surviving edges"""
+    rc = kcl_row_constants()
+    a, p, q, k = G.split_cells(rc)[cell]
+    check(f"{SPLIT_IDS[cell]}: a one past the boundary, k", (a, k), (rc[SPLIT_IDS[cell].split("-")[0]] + 1, int(SPLIT_IDS[cell][-1])))
+    m = G.split_booster(a, p, q, a, k)
+    g = G.split_hub_edge_gadget(a, p, q, m, a)
+    want = G.split_expected(g, a, p, q, m, a, k)  # (asserts, from the closed forms: X below c, everything else of G' at or above it)
+    check(f"a={a} k={k}: X has at least 8 edges, one of them over the first and the last word of a row",
+          (want["x"] >= 8, want["x_words"]), (True, (0, want["words"] - 1)))
+    check(f"a={a} k={k}: at least three different spoke decrements", len(want["spoke_decrements"]) >= 3, True)
+    with g.to_device(dev) as sym:
+        cnt = check_ktruss(f"split gadget a={a} m={m}", g, sym, k, want["c"], (want["cnt"], want["edges"], want["cliques"], want["rounds"]))
+        inside = cnt != REMOVED
+        check(f"a={a} k={k}: e and X are what left", int((~inside).sum()), 2 * (want["x"] + 1))
+        with edge_subgraph(g, inside).to_device(dev) as sub:
+            _, _, ent = clique_local(sub, k, vertex=False)
+        check_arrays(f"split gadget a={a} k={k} the counts against gm_clique_local on the surviving edges", cnt[inside], ent)
+        if SPLIT_IDS[cell] in SPLIT_DECOMPOSE:
+            check_decompose(f"split gadget a={a} m={m}", g, sym, k, R.decompose(g, k))
 
 
 def test_two_disjoint_frontier_edges_of_one_4_clique(dev):
@@ -222,9 +292,11 @@ def gadget_cells():
     return [(rc[key] + more, p) for key, p in density.items() for more in (0, 1)] + [(520, 0.05)], rc
 
 
-def run_gadget(dev, a, p, k):
-    m = G.booster(a, p, a, k)
+def run_gadget(dev, a, p, k, least_m=0, before=None):
+    m = max(G.booster(a, p, a, k), least_m)
     g = G.hub_edge_gadget(a, p, m, a)
+    if before:
+        before(g)
     want = G.expected(g, a, p, m, a, k)  # (asserts that the hub edge leaves alone and that everything else survives, from the closed forms)
     if k >= 4:
         check(f"a={a} k={k}: at least three different spoke decrements", len(want["spoke_decrements"]) >= 3, True)
@@ -245,6 +317,34 @@ def test_hub_edge_gadget_deeper_descents(dev):
     rc = kcl_row_constants()
     for k, a, p in ((5, rc["regs2"], 0.3), (5, rc["regs2"] + 1, 0.3), (6, rc["regs2"] + 1, 0.35)):
         run_gadget(dev, a, p, k)
+
+
+@pytest.mark.parametrize("cell", [0, 1], ids=["lanes+1", "lanes+65"])
+def test_hub_edge_gadget_beyond_the_first_64_words_of_a_row(dev, cell):
+    """the wide kernel walks the set pairs of a position through its matrix row 64 words at a time: position `lanes` = 64 x 32 is the first
+    of the second group.  At a = lanes + 1 every pair of that position is met from a position of the first group, in its second step; at
+    a = lanes + 65 the positions from `lanes` on have pairs among themselves, whose walk STARTS in the second group"""
+    rc = kcl_row_constants()
+    a, p, k = G.second_group_cells(rc)[cell]
+    check("a against lanes", a - rc["lanes"], (1, 65)[cell])
+    one, both = G.a_edges_from(a, p, a, rc["lanes"])
+    print(f"a={a} p={p}: {one} edges of A reach position {rc['lanes']} or beyond, {both} lie there with both ends", flush=True)
+    assert one >= 1 and (cell == 0 or both >= 1)
+    run_gadget(dev, a, p, k)
+
+
+def test_hub_edge_gadget_with_rows_longer_than_four_lists(dev):
+    """the workgroup path, every survivor's row longer than 4 |S_e|: the pair walk streams S_e against the row (the other branch of
+    ktr_walk_pairs), for the matrix and again for the pair decrements"""
+    rc = kcl_row_constants()
+    a, p, k, least_m = G.long_row_cell(rc)
+
+    def rows(g):
+        shortest = int(np.diff(g.row_ptr)[:a].min())
+        print(f"a={a}: the shortest row of a survivor {shortest}, 4 |S_e| = {4 * a}", flush=True)
+        assert rc["regs2"] < a <= rc["lds"] and shortest > 4 * a
+
+    run_gadget(dev, a, p, k, least_m, rows)
 
 
 # ---- 6. the contract -----------------------------------------------------------------------------------------------------------------------
