@@ -109,6 +109,63 @@ def test_planted_expectation_is_the_ref(members):
             assert len(got) == p.expected(k)[2]
 
 
+def _list_cell(base, off, ks, recipe):
+    """the graph of a cell of tests/test_gpu_clique_list.py (the same Cell, the constants read from the library: a host call)"""
+    from common import gm_constant
+
+    consts = {"l2": gm_constant("kcl_list_regs2_row"), "l8": gm_constant("kcl_list_regs8_row"), "lds": gm_constant("kcl_local_lds_row"), "big": 2048}
+    cell = P.Cell(f"{base}{off:+d}", "L", base, off, ks, True, recipe)
+    return P.cell_graph(cell, tuple(sorted(consts.items()))), consts[base] + off
+
+
+@pytest.mark.parametrize("base,off,ks,recipe,asked", [("l8", 0, (6, 7, 8), P.HIGH, (6, 7, 8)), ("lds", 0, (6, 7, 8), P.HIGH, (6, 7, 8)),
+                                                      ("big", 1, (3, 4, 5), P.LOW, (5,))], ids=["l8+0-high", "lds+0-high", "big+1 k=5"])
+def test_planted_listing_cells_are_feasible(base, off, ks, recipe, asked):
+    """what test_planted_rows_on_both_sides_of_every_constant asks of its inputs before it runs the GPU, for the cells whose row is AT a
+    constant at k = 6, 7, 8 and for the row of 2049 entries at k = 5"""
+    p, d = _list_cell(base, off, ks, recipe)
+    print(f"{base}{off:+d}: the longest row {p.max_row}, the roots' rows {p.root_rows()}, {p.nv} vertices", flush=True)
+    assert (p.max_row, max(p.root_rows())) == (d, d)
+    for k in asked:
+        cond, want = p.conditions(k), planted_expected(p, k)
+        print(f"{base}{off:+d} k={k}: {cond}, expected rows {len(want)}, total {p.expected(k)[2]}", flush=True)
+        assert cond["blocks_with_clique"] >= 0.9 and len(want) >= 1000 and len(want) == p.expected(k)[2]
+        assert len(np.unique(want, axis=0)) == len(want) and bool((want[:, 1:] > want[:, :-1]).all())
+
+
+def test_root_boundaries_on_a_reference_list():
+    """tests/list_windows.py root_boundaries on the reference's own list of a planted graph: the slots it names are where the root, the
+    entry and the pair change, and the windows it calls exact hold one root / entry / pair"""
+    from list_windows import out_list, root_boundaries
+
+    blocks = P.random_blocks(150, *P.LOW)
+    p = P.Planted(blocks, P._standard_members(blocks, 150), True)
+    rows = clique_list_ref(p.graph, 4)
+    keys = order_keys(p.graph, rows)
+    root = int(p.i_id[0])
+    L = out_list(p.graph, root)
+    bounds, exact, info = root_boundaries(p.graph, keys, root)
+    print(f"root {root}: {info}\n  {bounds}\n  {exact}", flush=True)
+    assert len(L) == 150 == info["row"] and info["cross pairs behind a carried base"] >= 1
+    i, l, before = info["cross pair"]
+    assert l // 64 > i // 64 and before >= 1
+    named = dict(bounds)
+    r0, r1 = named["the root's first slot"], named["the slot behind the root"]
+    assert bool((keys[r0:r1, 0] == root).all()) and (r0 == 0 or keys[r0 - 1, 0] != root) and (r1 == len(keys) or keys[r1, 0] != root)
+    for label, b in bounds:
+        if "entry" in label and "pair" not in label:
+            assert keys[b, 0] == root and (b == r0 or keys[b - 1, 1] != keys[b, 1]), label
+        elif "pair" in label and "rows into" not in label:
+            assert keys[b, 0] == root and (b == r0 or tuple(keys[b - 1, 1:3]) != tuple(keys[b, 1:3])), label
+    b = named["a pair in a later chunk than its entry"]
+    assert (int(np.searchsorted(L, keys[b, 1])), int(np.searchsorted(L, keys[b, 2]))) == (i, l) and keys[b - 1, 1] == keys[b, 1]
+    for (label, first, cap), cols in zip(exact, (1, 2, 3)):
+        inside = keys[first:first + cap, :cols]
+        assert cap >= 1 and bool((inside == inside[0]).all()), label
+        assert first == 0 or tuple(keys[first - 1, :cols]) != tuple(inside[0]), label
+        assert first + cap == len(keys) or tuple(keys[first + cap, :cols]) != tuple(inside[0]), label
+
+
 def test_abi_surface():
     import graphminer_amd
     from graphminer_amd import _lib

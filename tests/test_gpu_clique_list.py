@@ -13,11 +13,12 @@ import pytest
 
 import planted_cliques as P
 import twin_graphs as T
-from clique_list_ref import check_list, clique_list_ref, lex_window, planted_expected, sort_rows
+from clique_list_ref import check_list, clique_list_ref, lex_window, order_keys, planted_expected, sort_rows
 from common import GOLDEN, check_rows, load_graph
 from graphminer_amd import CliqueSolver, Graph, TCSolver, _lib, clique_list, clique_local, tc_list
 from graphminer_amd._lib import dev_live_blocks
 from graphminer_amd.rmat import csr_from_pairs
+from list_windows import U64_MAX, clique_call, guarded_window, root_boundaries
 
 pytestmark = pytest.mark.gpu
 SMALL = ["citeseer", "cora", "rmat6_ef4_s1", "rmat8_ef8_s42"]
@@ -139,21 +140,27 @@ def test_count_only_and_guard_words(dev):
     with load_graph(RMAT10).to_device(dev) as sym:
         check("count only", raw_call(sym, k, 0, 12345, None), (_lib.GM_OK, T_, 0))
         full = clique_list(sym, k)[0]
-        buf = torch.full((k * T_ + 64,), SENTINEL, dtype=torch.int32, device=f"cuda:{dev}")
-        check("cap = T - 5", raw_call(sym, k, 0, T_ - 5, buf), (_lib.GM_OK, T_, T_ - 5))
-        host = buf.cpu().numpy()
-        check("ints changed", int((host != SENTINEL).sum()), k * (T_ - 5))
-        check("ints behind the window untouched", bool((host[k * (T_ - 5):] == SENTINEL).all()), True)
-        check_rows("the first T - 5 rows", host[:k * (T_ - 5)].reshape(-1, k), full[:T_ - 5])
-        buf.fill_(SENTINEL)
-        check("a window in the middle", raw_call(sym, k, 1000, 77, buf), (_lib.GM_OK, T_, 77))
-        host = buf.cpu().numpy()
-        check_rows("rows 1000 .. 1076", host[:k * 77].reshape(-1, k), full[1000:1077])
-        check("ints behind it untouched", bool((host[k * 77:] == SENTINEL).all()), True)
-        buf.fill_(SENTINEL)
+        call = clique_call(sym, k)
+        # (guarded_window asserts: both pads all sentinel, exactly k n_written ints changed, nothing behind row n_written)
+        rc, total, n, rows = guarded_window(call, k, 0, T_ - 5, rows=T_ + 16, sentinel=SENTINEL)
+        check("cap = T - 5", (rc, total, n), (_lib.GM_OK, T_, T_ - 5))
+        check_rows("the first T - 5 rows", rows, full[:T_ - 5])
+        rc, total, n, rows = guarded_window(call, k, 1000, 77, sentinel=SENTINEL)
+        check("a window in the middle", (rc, total, n), (_lib.GM_OK, T_, 77))
+        check_rows("rows 1000 .. 1076", rows, full[1000:1077])
         for first in (T_, T_ + 1, 2**40):
-            check(f"first = {first}", raw_call(sym, k, first, 10, buf), (_lib.GM_OK, T_, 0))
-        check("cap = 0", raw_call(sym, k, 5, 0, buf), (_lib.GM_OK, T_, 0))
+            rc, total, n, rows = guarded_window(call, k, first, 10, sentinel=SENTINEL)
+            check(f"first = {first}", (rc, total, n, rows.shape), (_lib.GM_OK, T_, 0, (0, k)))
+        rc, total, n, rows = guarded_window(call, k, 5, 0, rows=10, sentinel=SENTINEL)
+        check("cap = 0", (rc, total, n, rows.shape), (_lib.GM_OK, T_, 0, (0, k)))
+        rc, total, n, rows = guarded_window(call, k, T_ - 5, U64_MAX, rows=10, sentinel=SENTINEL)
+        check("first = T - 5, cap = 2^64 - 1", (rc, total, n), (_lib.GM_OK, T_, 5))
+        check_rows("the last five rows", rows, full[T_ - 5:])
+        rc, total, n, rows = guarded_window(call, k, 0, U64_MAX, rows=T_, sentinel=SENTINEL)
+        check("first = 0, cap = 2^64 - 1", (rc, total, n), (_lib.GM_OK, T_, T_))
+        check_rows("the whole list", rows, full)
+        buf = torch.full((64,), SENTINEL, dtype=torch.int32, device=f"cuda:{dev}")
+        check("first = 2^64 - 1, cap = 2^64 - 1", raw_call(sym, k, U64_MAX, U64_MAX, buf), (_lib.GM_OK, T_, 0))
         check("nothing written", bool((buf.cpu().numpy() == SENTINEL).all()), True)
 
 
@@ -224,12 +231,19 @@ def test_slots_past_2_32(dev):
 def _cells():
     out = []
     for base, off in (("l2", 0), ("l2", 1), ("l8", 0), ("l8", 1), ("lds", 0), ("lds", 1), ("big", 1)):
-        ks = (3, 4, 5) if (base, off) == ("lds", 1) else (3, 4)
+        # (big + 1 at k = 5: a stride of 65 words, the second trip of KclListWalk's loop over 64 words at a time)
+        ks = (3, 4, 5) if (base, off) in (("lds", 1), ("big", 1)) else (3, 4)
         out.append(P.Cell(f"{base}{off:+d}", "L", base, off, ks, True, P.LOW))
+    # k = 6, 7, 8 from a long row of every class: blocks of 13 .. 18 vertices at p = 0.9 hold 8-cliques.  The pair values come from
+    # kcl_list_pair_small<M, 2 / 8 / 16> and kcl_list_pair_any<M> at M = 3, 4, 5, the walk is KclListWalk<M, K> at M = 3, 4, 5 over 3, 9, 16
+    # and 17 words
+    for base, off in (("l2", 1), ("l8", 0), ("l8", 1), ("lds", 0), ("lds", 1)):
+        out.append(P.Cell(f"{base}{off:+d}-high", "L", base, off, (6, 7, 8), True, P.HIGH))
     return out
 
 
 CELLS = _cells()
+CELL = {c.name: c for c in CELLS}
 
 
 def planted_cell(cell):
@@ -260,12 +274,13 @@ def test_planted_rows_on_both_sides_of_every_constant(dev, cell):
             check_rows(f"{cell.name} k={k} the expected set", sort_rows(rows), want)
             check_list(p.graph, k, rows, 0)
             mid = total // 2
-            part = clique_list(sym, k, first=mid, cap=300)[0]
-            check_rows(f"{cell.name} k={k} a window in the middle", part, rows[mid:mid + 300])
+            rc, total2, n, part = guarded_window(clique_call(sym, k), k, mid, 300, sentinel=SENTINEL)
+            check(f"{cell.name} k={k} a window in the middle", (rc, total2, n), (_lib.GM_OK, total, min(300, total - mid)))
+            check_rows(f"{cell.name} k={k} the window's rows", part, rows[mid:mid + 300])
 
 
-def test_planted_three_kinds_of_root_in_one_graph(dev):
-    """roots within the 2-register rows, within the LDS matrix and two beyond it (scratch slots), one call"""
+def mixed_graph():
+    """roots within the 2-register rows, within the LDS matrix and two beyond it (scratch slots) in one graph"""
     c = constants()
     rows_wanted = (c["l2"] - 4, c["l8"] + 44, c["lds"] + 1, 2 * c["lds"] + 76)
     consts = {"split": rows_wanted[0] + 28, "regs8": rows_wanted[1] - 44, "lds": c["lds"]}
@@ -273,6 +288,12 @@ def test_planted_three_kinds_of_root_in_one_graph(dev):
     check("the roots' rows", tuple(sorted(p.root_rows())), rows_wanted)
     check("the longest row", p.max_row, rows_wanted[3])
     assert rows_wanted[0] <= c["l2"] < rows_wanted[1] <= c["lds"] < rows_wanted[2]
+    return p
+
+
+def test_planted_three_kinds_of_root_in_one_graph(dev):
+    """roots within the 2-register rows, within the LDS matrix and two beyond it (scratch slots), one call"""
+    p = mixed_graph()
     with p.graph.to_device(dev) as sym:
         for k in (4, 5):
             cond, want = p.conditions(k), planted_expected(p, k)
@@ -283,6 +304,61 @@ def test_planted_three_kinds_of_root_in_one_graph(dev):
             check_rows(f"mixed k={k} the expected set", sort_rows(rows), want)
             check_list(p.graph, k, rows, 0)
             check_rows(f"mixed k={k} windows of 997", np.concatenate([clique_list(sym, k, first=f, cap=997)[0] for f in range(0, total, 997)]), rows)
+
+
+# ---- windows at root, entry and pair boundaries --------------------------------------------------------------------------------------------
+EDGE_CASES = [("l2+1", 4), ("l2+1-high", 6), ("l8+1", 5), ("l8+1-high", 8), ("lds+1", 4), ("lds+1", 5), ("lds+1-high", 6), ("lds+1-high", 8),
+              ("mixed", 5)]
+EDGE_STARTS, EDGE_CAPS = (-1, 0), (1, 63, 64, 65, 129)
+
+
+@pytest.mark.parametrize("name,k", EDGE_CASES, ids=[f"{n}-k{k}" for n, k in EDGE_CASES])
+def test_windows_at_root_entry_and_pair_boundaries(dev, name, k):
+    """a window that starts or ends exactly on the first slot of a long root, of one of its entries or of one of its pairs, a slot before
+    it, and on either side of a flush of 64 rows inside a pair: the root filter of the WIDE fill, the root and entry skips of the LDS
+    fill, the pair filter with a carried base and a seek, in every register class.  The reference is the one-call list once the expected
+    set and the checker have pinned it; every window has guard words on both sides."""
+    p = mixed_graph() if name == "mixed" else planted_cell(CELL[name])
+    want = planted_expected(p, k)
+    cond = p.conditions(k)
+    print(f"{name} k={k}: {cond}, expected rows {len(want)}", flush=True)
+    assert cond["blocks_with_clique"] >= 0.9 and len(want) >= 1000 and len(want) == p.expected(k)[2]
+    roots = sorted((int(p.row_len[p.i_id[x]]), int(p.i_id[x])) for x, m in enumerate(p.members) if not m.top)
+    targets = [roots[-1]] + ([roots[-2]] if name == "mixed" else [])  # the longest root; mixed: also the shorter WIDE root
+    assert name != "mixed" or roots[-2][0] > constants()["lds"]
+    with p.graph.to_device(dev) as sym:
+        rows, total = clique_list(sym, k)
+        check(f"{name} k={k} total", total, len(want))
+        check_rows(f"{name} k={k} the expected set", sort_rows(rows), want)
+        check_list(p.graph, k, rows, 0)
+        rows.setflags(write=False)
+        keys = order_keys(p.graph, rows)
+        call = clique_call(sym, k)
+        calls = 0
+        for d, root in targets:
+            bounds, exact, info = root_boundaries(p.graph, keys, root)
+            print(f"{name} k={k} root {root} (row of {d}): {info}\n  boundaries {bounds}\n  exact {exact}", flush=True)
+            # (two windows of the largest cap fit inside the root: a window at one of its inner boundaries stays inside it)
+            assert info["row"] == d and info["rows"] >= 2 * max(EDGE_CAPS) and info["entries"] >= 3 and info["pairs of the fattest entry"] >= 3
+            if d >= 128:  # (in a row of 65 entries the second chunk holds the last position alone, and nothing lies above it: no such pair)
+                assert info["cross pairs behind a carried base"] >= 1 and info["cross pair"][1] // 64 > info["cross pair"][0] // 64
+                assert info["cross pair"][2] >= 1, "an earlier pair of the same entry holds rows"
+            else:
+                assert info["cross pairs"] == 0
+            for label, b in bounds:
+                for first in sorted({min(max(b + o, 0), total - 1) for o in EDGE_STARTS}):
+                    for cap in EDGE_CAPS:
+                        rc, total2, n, part = guarded_window(call, k, first, cap, sentinel=SENTINEL)
+                        calls += 1
+                        assert (rc, total2, n) == (_lib.GM_OK, total, min(cap, total - first)), (label, first, cap, rc, total2, n)
+                        if not np.array_equal(part, rows[first:first + cap]):
+                            check_rows(f"{name} k={k} {label}: first={first} cap={cap}", part, rows[first:first + cap])
+            for label, first, cap in exact:
+                rc, total2, n, part = guarded_window(call, k, first, cap, sentinel=SENTINEL)
+                calls += 1
+                check(f"{name} k={k} {label}: first={first} cap={cap}", (rc, total2, n), (_lib.GM_OK, total, cap))
+                check_rows(f"{name} k={k} {label}: rows", part, rows[first:first + cap])
+        print(f"{name} k={k}: {calls} windows, every one the list's slice", flush=True)
 
 
 # ---- the caller's numbering -------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """Triangle listing on the GPU (gm_tc_list, csrc/gm_list.hip): every triangle once, as a < b < c of the caller's numbering, against the plain
 numpy list of tests/list_ref.py; the windows of one handle tile its fixed order; the 64-lane tile, the flattened / whole-wave threshold,
-rows of more than 2048 entries, slots past 2^32, shuffled and offset numberings, the other solvers of the handle, the refusals.
+rows of more than 2048 entries, slots past 2^32, shuffled and offset numberings, the other solvers of the handle, the refusals; the
+one-call list row for row against the ordered reference (list_ref_ordered: the documented order by a walk of its own); windows that start
+and end on batch and ring-flush boundaries, every one with guard words in front of it and behind it (tests/list_windows.py).
 Every value is printed before it is asserted."""
 import ctypes as C
 import functools
@@ -14,7 +16,8 @@ import twin_graphs as T
 from common import GOLDEN, check_rows, list_windows, load_graph
 from graphminer_amd import Graph, SglSolver, TCSolver, _lib, ktruss, tc_list, tc_local
 from graphminer_amd.rmat import csr_from_pairs
-from list_ref import list_ref, sort_rows
+from list_ref import list_ref, list_ref_ordered, sort_rows
+from list_windows import U64_MAX, guarded_window, tc_call
 
 pytestmark = pytest.mark.gpu
 AS_NUMBERED = 0x200
@@ -93,15 +96,25 @@ def test_count_only_and_guard_words(dev):
     with load_graph(name).to_device(dev) as sym:
         check("count only", raw_call(sym, 0, 12345, None), (_lib.GM_OK, T_, 0))
         full = tc_list(sym)[1]
-        buf = torch.full((3 * T_ + 64,), SENTINEL, dtype=torch.int32, device=f"cuda:{dev}")
-        check("cap = T - 5", raw_call(sym, 0, T_ - 5, buf), (_lib.GM_OK, T_, T_ - 5))
-        host = buf.cpu().numpy()
-        check("ints changed", int((host != SENTINEL).sum()), 3 * (T_ - 5))
-        check("ints behind the window untouched", bool((host[3 * (T_ - 5):] == SENTINEL).all()), True)
-        check_rows("the first T - 5 rows", host[:3 * (T_ - 5)].reshape(-1, 3), full[:T_ - 5])
-        buf.fill_(SENTINEL)
+        call = tc_call(sym)
+        # (guarded_window asserts: both pads all sentinel, exactly 3 n_written ints changed, nothing behind row n_written)
+        rc, total, n, rows = guarded_window(call, 3, 0, T_ - 5, rows=T_ + 20, sentinel=SENTINEL)
+        check("cap = T - 5", (rc, total, n), (_lib.GM_OK, T_, T_ - 5))
+        check_rows("the first T - 5 rows", rows, full[:T_ - 5])
+        rc, total, n, rows = guarded_window(call, 3, 1000, 77, sentinel=SENTINEL)
+        check("a window in the middle", (rc, total, n), (_lib.GM_OK, T_, 77))
+        check_rows("rows 1000 .. 1076", rows, full[1000:1077])
         for first in (T_, T_ + 1, 2**40):
-            check(f"first = {first}", raw_call(sym, first, 10, buf), (_lib.GM_OK, T_, 0))
+            rc, total, n, rows = guarded_window(call, 3, first, 10, sentinel=SENTINEL)
+            check(f"first = {first}", (rc, total, n, rows.shape), (_lib.GM_OK, T_, 0, (0, 3)))
+        rc, total, n, rows = guarded_window(call, 3, T_ - 5, U64_MAX, rows=10, sentinel=SENTINEL)
+        check("first = T - 5, cap = 2^64 - 1", (rc, total, n), (_lib.GM_OK, T_, 5))
+        check_rows("the last five rows", rows, full[T_ - 5:])
+        rc, total, n, rows = guarded_window(call, 3, 0, U64_MAX, rows=T_, sentinel=SENTINEL)
+        check("first = 0, cap = 2^64 - 1", (rc, total, n), (_lib.GM_OK, T_, T_))
+        check_rows("the whole list", rows, full)
+        buf = torch.full((64,), SENTINEL, dtype=torch.int32, device=f"cuda:{dev}")
+        check("first = 2^64 - 1, cap = 2^64 - 1", raw_call(sym, U64_MAX, U64_MAX, buf), (_lib.GM_OK, T_, 0))
         check("nothing written", bool((buf.cpu().numpy() == SENTINEL).all()), True)
 
 
@@ -128,13 +141,22 @@ def test_complete_graphs_cross_the_tile_and_the_threshold(dev, n):
         check_rows(f"K_{n} windows of 50", windows(sym, 50, upto), tri[:upto])
 
 
+KAB = (2100, 2101)
+KAB_INNER = [(0, 1), (1, 2), (0, 2)]
+
+
+def kab_plus_triangle():
+    n, s, d = T.pairs("kab", KAB)
+    return csr_from_pairs(n, np.concatenate([s, [x for x, _ in KAB_INNER]]).astype(np.uint64),
+                          np.concatenate([d, [y for _, y in KAB_INNER]]).astype(np.uint64))
+
+
 def test_rows_beyond_2048_entries(dev):
     """K_{2100,2101} + one triangle inside the 2100 side: the DAG rows of the 2101 side have 2100 entries, more than the 2048-entry LDS stage
     of the other triangle kernels; the listing stages no row (the longer list is bisected in global memory), so no size is special to it"""
-    a, b = 2100, 2101
-    n, s, d = T.pairs("kab", (a, b))
-    inner = [(0, 1), (1, 2), (0, 2)]
-    g = csr_from_pairs(n, np.concatenate([s, [x for x, _ in inner]]).astype(np.uint64), np.concatenate([d, [y for _, y in inner]]).astype(np.uint64))
+    a, b = KAB
+    g = kab_plus_triangle()
+    n, inner = g.V(), KAB_INNER
     want = np.array([(0, 1, 2)] + [(x, y, w) for x, y in inner for w in range(a, n)], dtype=np.int32)
     want = sort_rows(want)
     check("expected triangles", len(want), 6304)
@@ -178,6 +200,103 @@ def test_the_callers_numbering(dev, which):
             total, tri = tc_list(sym, tune=tune)
             check(f"{which} tune={tune} total", total, len(want))
             check_rows(f"{which} tune={tune} rows", sort_rows(tri), want)
+
+
+# ---- the documented order, against a reference that walks it itself -------------------------------------------------------------------------
+NUMBERED = ["rmat10 permuted", "multipartite (3, 40) at 517 of 1000"]
+ORDERED = SMALL + ["K_66", "K_200"] + NUMBERED + ["K_{2100,2101} + triangle"]
+
+
+def named_graph(name):
+    if name in SMALL:
+        return load_graph(name)
+    if name.startswith("K_{"):
+        return kab_plus_triangle()
+    if name.startswith("K_"):
+        return T.graph("complete", (int(name[2:]),))
+    return permuted_rmat10() if name.startswith("rmat10") else T.graph("multipartite", (3, 40), nv=1000, offset=517)
+
+
+@functools.lru_cache(maxsize=None)
+def ordered(name):
+    """(the list in the documented order, the first slot of every oriented entry): tests/list_ref.py, computed once, read-only"""
+    tri, off = list_ref_ordered(named_graph(name))
+    tri.setflags(write=False)
+    off.setflags(write=False)
+    return tri, off
+
+
+@pytest.mark.parametrize("name", ORDERED)
+def test_the_documented_order(dev, name):
+    """the one-call list row for row: ascending entry (u, v) of the oriented copy as numbered, then ascending w"""
+    want, off = ordered(name)
+    print(f"{name}: {len(want)} rows over {len(off) - 1} oriented entries", flush=True)
+    with named_graph(name).to_device(dev) as sym:
+        for tune in (None, t6(AS_NUMBERED)) if name in NUMBERED else (None,):
+            total, tri = tc_list(sym, tune=tune)
+            check(f"{name} tune={tune} total", total, len(want))
+            check_rows(f"{name} tune={tune} rows in the documented order", tri, want)
+
+
+# ---- windows at batch and flush boundaries ---------------------------------------------------------------------------------------------------
+WINDOW_CAPS = (1, 2, 63, 64, 65, 127, 128, 129)
+
+
+def batch_slots(off):
+    """the first slot of every batch of 64 consecutive oriented entries (and T behind the last one)"""
+    ne = len(off) - 1
+    return off[np.minimum(np.arange((ne + 63) // 64 + 1) * 64, ne)]
+
+
+@pytest.mark.parametrize("name", ["rmat10_ef16_s42", "K_200", "K_{2100,2101} + triangle"])
+def test_windows_at_batch_and_flush_boundaries(dev, name):
+    """list_kernel<true> walks a batch from its first slot whatever the window: a window that starts or ends on a batch's first slot, one
+    slot to either side, or on a slot at which the ring flushes 64 rows, with guard words in front of it and behind it"""
+    want, off = ordered(name)
+    T_ = len(want)
+    boff = batch_slots(off)
+    rows_of = np.diff(boff)
+    full = np.flatnonzero(rows_of > 0)
+    fat = int(np.argmax(rows_of))
+    empty_next_to_full = [int(b) for b in np.flatnonzero(rows_of == 0) if 0 < b < len(rows_of) - 1 and rows_of[b - 1] > 0 and rows_of[b + 1] > 0]
+    print(f"{name}: T {T_}, {len(rows_of)} batches, {len(full)} non-empty, the fattest {fat} holds {int(rows_of[fat])} rows, "
+          f"empty between two non-empty: {empty_next_to_full[:5]}", flush=True)
+    assert boff[-1] == T_
+    if name.startswith("rmat10"):  # irregular: no batch is empty (its 165 batches hold 61 .. 1034 rows), the ring flushes a different number of times in each
+        assert rows_of[fat] >= 256 and rows_of[full].min() * 8 <= rows_of[fat]
+    elif name.startswith("K_{"):  # a row of 2100 entries is 33 batches and only its first two entries hold rows: runs of empty batches
+        assert len(empty_next_to_full) == 0 and len(full) * 16 <= len(rows_of)
+        empty_next_to_full = [int(b) + 1 for b in full[:-1] if rows_of[b + 1] == 0][1:4]  # (the empty batch behind a non-empty one)
+        assert len(empty_next_to_full) == 3 and all(0 < boff[b] < T_ for b in empty_next_to_full)
+    else:
+        assert rows_of[fat] >= 2000 and len(full) == len(rows_of), "K_200: batches of thousands of rows, none empty"
+    seeded = np.random.default_rng(11).choice(len(rows_of), 3, replace=False)
+    s = int(boff[fat])
+    bounds = [int(boff[full[0]]), s, int(boff[full[-1]])] + [int(boff[b]) for b in seeded]
+    if rows_of[fat] >= 256:  # the ring's flushes inside the fattest batch
+        bounds += [s + 64, s + 128, s + 64 * (int(rows_of[fat]) // 128)]
+    starts = sorted({min(max(b + o, 0), T_ - 1) for b in bounds for o in (-1, 0, 1)})
+    print(f"{name}: boundaries {bounds}, {len(starts)} starts x {len(WINDOW_CAPS)} caps", flush=True)
+    with named_graph(name).to_device(dev) as sym:
+        call = tc_call(sym)
+
+        def window(label, first, cap):
+            rc, total, n, rows = guarded_window(call, 3, first, cap, sentinel=SENTINEL)
+            assert (rc, total, n) == (_lib.GM_OK, T_, min(cap, T_ - first)), (label, first, cap, rc, total, n)
+            if not np.array_equal(rows, want[first:first + cap]):
+                check_rows(f"{name} {label} first={first} cap={cap}", rows, want[first:first + cap])
+
+        for first in starts:
+            for cap in WINDOW_CAPS:
+                window("boundary window", first, cap)
+        window("exactly the fattest batch", s, int(rows_of[fat]))
+        window("the fattest batch and a row on either side", max(s - 1, 0), int(rows_of[fat]) + 2)
+        for b in empty_next_to_full[:3]:  # the last row before an empty batch and the first one behind it, and nothing else
+            assert boff[b] == boff[b + 1] and 0 < boff[b] < T_
+            window(f"around the empty batch {b}", int(boff[b]) - 1, 2)
+            window(f"behind the empty batch {b}", int(boff[b]), 1)
+            window(f"before the empty batch {b}", int(boff[b]) - 1, 1)
+    print(f"{name}: every window is the reference's slice", flush=True)
 
 
 def test_neighbours_on_the_handle(dev):
