@@ -898,7 +898,7 @@ hipError_t launch_kcl_list_fill(const KclListParams &p, int grid, int grid_wide,
 // triangle nuclei (gm_nucleus34.hip): the triangle index of the oriented copy, the 4-cliques on every triangle and the rounds that peel
 // them.  A triangle's id is its slot in gm_tc_list's order: ascending entry (u, v) of the oriented copy, then ascending third vertex.  A
 // triangle (an entry of the index build) whose streamed row is below kNucWholeWave entries takes kNucGroup lanes, a longer one the wave.
-// Exported through gm_constant ("nuc_whole_wave").
+// Exported through gm_constant ("nuc_whole_wave", "nuc_group").
 constexpr int kNucGroup = 8, kNucWholeWave = 64;
 enum NucWord : int { NW_TOTAL = 4 };  // beside CoreWord, in place of the queue words: the sum of K4(t) over all triangles (4 x the 4-cliques)
 struct NucIndexParams {

@@ -149,7 +149,7 @@ extern "C" int gm_constant(const char *name, int64_t *value) {
               {"wide_max_deg", kWideMaxDeg},           {"bit_words", kBitWords},
       {"kcl_local_lds_row", kKclLocalLdsRow}, {"kcl_local_regs2_row", kKclLocalRegs2Row}, {"kcl_local_regs8_row", kKclLocalRegs8Row}, {"kcl_local_regs12_row", kKclLocalRegs12Row},
       {"kcl_local_split_row", kKclLocalSplitRow}, {"kcl_list_regs2_row", kKclListRegs2Row}, {"kcl_list_regs8_row", kKclListRegs8Row},
-      {"orbit_wave_row", kOrbitWaveRow},     {"chouse_lds_keys", kChouseCap},         {"nuc_whole_wave", kNucWholeWave},
+      {"orbit_wave_row", kOrbitWaveRow},     {"chouse_lds_keys", kChouseCap},         {"nuc_whole_wave", kNucWholeWave}, {"nuc_group", kNucGroup},
       {"rect_local_range", kRectLocalRange}, {"rect_local_one_task", kRectLocalThreads}, {"rect_local_long_row", kRectLocalLong},
       {"map_rect_block", kRectLdsWords}, {"map_one_task_rows", kRectLdsWaves * GM_WAVE}, {"map_long_row", kRectLdsLong}, {"map_tile_group", kRectLdsTiles * GM_WAVE},
       {"map_mark_window", kMarkWindow}, {"map_house_ids", kHouseLdsIds}, {"map_house_wg_row", kHouseLongWg}, {"map_house_wg_queue", kHouseLongQ},

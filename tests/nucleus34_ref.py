@@ -61,11 +61,11 @@ class _State:
         self.mark = np.zeros(len(self.tris), dtype=np.int8)
         self.destroyed = 0
 
-    def round(self, thr):
+    def round(self, thr, census=None):
         """steps 1 - 3 of a round: last round's frontier becomes removed, the alive triangles below thr become the frontier, the peel.
         Returns the frontier.  The rule: a 4-clique counts only if none of its triangles was removed before the round began; with at
         least one frontier triangle it is destroyed, accounted once by its frontier triangle of the smallest id, and every triangle of it
-        outside the frontier loses one."""
+        outside the frontier loses one.  With a Counter `census` the round also records what the blocked rule met (round_census)."""
         self.mark[self.mark == FRONTIER] = GONE
         front = np.flatnonzero((self.mark == ALIVE) & (self.cnt < thr))
         self.mark[front] = FRONTIER
@@ -73,6 +73,21 @@ class _State:
         for t in front.tolist():
             for q in self.on[t]:
                 four = self.cliques[q]
+                if census is not None:
+                    # the siblings of t in this clique are numbered as the peel kernel looks them up, with the ids in place of the
+                    # orientation: `four` lists the triangles of the sorted quadruple by the corner left out, the largest first, so
+                    # of the other three the first keeps t's two smallest corners (sibling 0), the second its smallest and its largest
+                    # (sibling 1), the third its two largest (sibling 2)
+                    blocked = False
+                    for sib, s in enumerate(s for s in four if s != t):
+                        if mark[s] == GONE:
+                            census[("skipped: a sibling removed earlier", sib)] += 1
+                            blocked = True
+                        elif mark[s] == FRONTIER and s < t:
+                            census[("skipped: a sibling in the frontier at a smaller id", sib)] += 1
+                            blocked = True
+                    if not blocked:
+                        census[("destroyed: frontier triangles", sum(1 for s in four if mark[s] == FRONTIER))] += 1
                 if any(mark[s] == GONE or (mark[s] == FRONTIER and s < t) for s in four if s != t):
                     continue  # (blocked: it was destroyed in an earlier round, or a frontier triangle of a smaller id accounts it)
                 self.destroyed += 1
@@ -90,14 +105,14 @@ def prepare(g):
     return _State(g)
 
 
-def decompose(g):
+def decompose(g, census=None):
     s = _State(g)
     n = len(s.tris)
     theta, rnd = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
     rounds, c_max = 0, 0
     level = int(s.cnt.min()) if n else 0
     while True:
-        front = s.round(level + 1)
+        front = s.round(level + 1, census)
         rounds += 1
         if front.size == 0:
             alive = s.alive()
@@ -108,6 +123,17 @@ def decompose(g):
         theta[front], rnd[front], c_max = level, rounds, level
     assert (s.cnt >= 0).all()
     return Decomposition({t: int(theta[i]) for i, t in enumerate(s.tris)}, {t: int(rnd[i]) for i, t in enumerate(s.tris)}, c_max, rounds, s.destroyed)
+
+
+def round_census(g):
+    """what the blocked rule meets over the rounds of decompose(g), a Counter: ("destroyed: frontier triangles", 1 .. 4) per destroyed
+    clique, and per frontier triangle that skips a clique ("skipped: a sibling removed earlier", sibling) or ("skipped: a sibling in the
+    frontier at a smaller id", sibling), once for every sibling 0 .. 2 that blocks it (numbered as in _State.round)"""
+    from collections import Counter
+
+    census = Counter()
+    decompose(g, census)
+    return census
 
 
 def nucleus(g, c):

@@ -34,3 +34,4 @@ def test_constant():
     from common import gm_constant
 
     assert gm_constant("nuc_whole_wave") == 64
+    assert gm_constant("nuc_group") == 8
